@@ -12,8 +12,10 @@ started plainly; the driver's own torchrun command works as well).  Weak scaling
 global index i = k*N + r (round-robin, no data-path collective); with N > 1 every GPU holds 125 000 chunks
 (8 x 125 000 = BASELINE configs[3]), with N = 1 100 000 (configs[1]).
 
-Every run verifies its whole output outside the timed region: decoded chunks are compared with the generated data on the
-device; `--op compress` / `--op roundtrip` (configs[2]) decode every compressed chunk again and compare it with its input.
+A plain run sets up, warms up, times `--steps` steps and prints its line.  `--full` adds, outside the timed region: the whole
+output verified (decoded chunks are compared with the generated data on the device; `--op compress` / `--op roundtrip`
+(configs[2]) decode every compressed chunk again and compare it with its input), `cpu_baseline`, and the roofline's `traffic` /
+`kernels_ms` from rocprofv3 child runs.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 
 `--workload mixed256k` is BASELINE configs[4]: 256 KiB chunks, even chunk indices LZ4-block / odd Snappy-raw,
 one engine (= one HIP stream) per codec per GPU running concurrently.
@@ -22,8 +24,8 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task description)
   value        = uncompressed GB/s over all ranks (sum of bytes / max wall time over ranks)
   roofline     = algorithmic bytes (compressed read + uncompressed written) per step / mean step duration measured
                  with HIP events on the engine's stream, vs the 8 TB/s HBM peak; `traffic` = HBM bytes per step from
-                 two extra rocprofv3 passes of this same command (--pmc FETCH_SIZE / --pmc WRITE_SIZE), or null
-  cpu_baseline = CPU decoders on this host's cores over the same unique chunks (rank 0, N=1 only): the oracle's C
+                 two extra rocprofv3 passes of this same command (--pmc FETCH_SIZE / --pmc WRITE_SIZE; --full), or null
+  cpu_baseline = (--full; else null) CPU decoders on this host's cores over the same unique chunks (rank 0, N=1 only): the oracle's C
                  restatement ("port") and, when the host has it, liblz4's LZ4_decompress_safe ("liblz4"), each with
                  all cores and with one
 """
@@ -67,7 +69,15 @@ def parse():
     ap.add_argument("--parse", default="auto", choices=["auto", "fused", "kernel"], help="debug: the workgroup decoder's parse stage inside the decoder kernel / as its own kernel at any batch size (CJ_FLAG_FORCE_FUSED_PARSE / _PARSE_KERNEL)")
     ap.add_argument("--lz4-mode", default="auto", choices=["auto", "wave", "lane", "lds"],
                     help="LZ4 decoder mapping override (results identical; auto = engine default)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: every result and output byte compared on the device, cpu_baseline, and the "
+                         "HBM traffic / per-kernel times of roofline (rocprofv3 child runs); a plain run only sets up, warms up and times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, under 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def load_liblz4():
@@ -276,6 +286,50 @@ def verify_compressed(N, L, b, torch, dev, np):
     return clen
 
 
+DUMP_LIMIT = 60 << 20          # bytes of .npy files a --dump-outputs run writes over all batches and ranks (at most 64 MB)
+
+
+def dump_outputs(d, named, rank, world, N, torch, np):
+    """--dump-outputs: what a caller of the device batch receives from the last timed step, for every (batch, out, meta) of `named`:
+      <name>_results.npy      float64 [n]     result of each chunk (decoded length / compressed size, or a negative error code)
+      <name>_checksums.npy    float64 [n]     sum over each chunk's output bytes [0, result) of (position + 1) * byte, computed on the device
+      <name>_sample.npy       float32 [k, W]  k whole output chunks (W = output stride), zero from the chunk's result on
+      <name>_chunks.npy       float64 [n]     the chunks the first two cover (all of them unless the batch is very large)
+      <name>_sample_chunks.npy float64 [k]    the chunks of the sample
+    Chunk choices are fixed (seeded), so two runs with the same arguments write comparable files.  <name> = codec_op, plus _rank<r>
+    when more than one rank runs."""
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_LIMIT // (len(named) * world)
+    rng = np.random.default_rng(0x5EED)
+    for b, out, meta in named:
+        NCH, W = b.NCH, (b.S if b.dec else b.stride_c)
+        name = "%s_%s%s" % ("lz4" if b.codec == N.CODEC_LZ4_BLOCK else "snappy", "decompress" if b.dec else "compress",
+                            "_rank%d" % rank if world > 1 else "")
+        res = meta[4 * NCH:].cpu().numpy().view(np.int64)
+        n = min(NCH, budget // 2 // 24)                               # results + checksums + chunk ids: 24 bytes per chunk
+        ids = np.arange(NCH) if n == NCH else np.sort(rng.choice(NCH, size=n, replace=False))
+        k = max(1, min(NCH, budget // 2 // (4 * W + 8)))              # the sample: the other half
+        sample_ids = np.sort(rng.choice(NCH, size=k, replace=False))
+        rows = out[:NCH * W].view(NCH, W)
+        lens = torch.from_numpy(np.clip(res, 0, W)).to(out.device)
+        weight = torch.arange(1, W + 1, dtype=torch.int64, device=out.device)
+        sums = torch.empty(n, dtype=torch.int64, device=out.device)
+        ids_d = torch.from_numpy(ids.astype(np.int64)).to(out.device)
+        step = max(1, (64 << 20) // W)                                # chunks at a time: int64 temporaries of 512 MB
+        for s0 in range(0, n, step):
+            sel = ids_d[s0:s0 + step]
+            x = rows[sel].to(torch.int64) * weight
+            x.masked_fill_(weight[None, :] > lens[sel][:, None], 0)
+            sums[s0:s0 + len(sel)] = x.sum(dim=1)
+        sample = rows[torch.from_numpy(sample_ids.astype(np.int64)).to(out.device)].cpu().numpy().astype(np.float32)
+        sample[np.arange(W)[None, :] >= np.clip(res[sample_ids], 0, W)[:, None]] = 0
+        np.save(os.path.join(d, name + "_results.npy"), res[ids].astype(np.float64))
+        np.save(os.path.join(d, name + "_checksums.npy"), sums.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(d, name + "_chunks.npy"), ids.astype(np.float64))
+        np.save(os.path.join(d, name + "_sample.npy"), sample)
+        np.save(os.path.join(d, name + "_sample_chunks.npy"), sample_ids.astype(np.float64))
+
+
 def main():
     args = parse()
     in_torchrun = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -395,13 +449,22 @@ def main():
             print("LDS decoder cycles/chunk: S0 %d  D1 %d  D2 %d  D3 %d  D4 %d  (blocks %d)  sub-marks 6.. %s" % (
                 ph[0] // nb, ph[1] // nb, ph[2] // nb, ph[3] // nb, ph[4] // nb, nb, [round(ph[i] / nb, 2) for i in range(6, 16)]), file=sys.stderr)
 
-    # ---- verify at full size: every chunk's result and every output byte ----
+    if args.dump_outputs:
+        # the buffers the last timed step wrote: step k went to lane k mod (batches in flight); the round trip's compress half is its own batch
+        last = (args.steps - 1) % len(lanes)
+        named = [(b, *((b.out, b.meta) if last == 0 else extra[last - 1])) for b in batches]
+        if rt is not None:
+            named.append((rt, rt.out, rt.meta))
+        dump_outputs(args.dump_outputs, named, rank, world, N, torch, np)
+
+    # ---- --full: verify at full size, every chunk's result and every output byte ----
+    verify = args.full and not args.experiment_no_verify
     bytes_in = sum(b.bytes_in for b in batches)
     if dec:
         for b in batches:
-            if not args.experiment_no_verify:
+            if verify:
                 verify_decoded(N, L, b, torch, dev)
-        for out2, meta2 in extra[:max(0, min(len(extra), args.steps + args.warmup - 1))]:
+        for out2, meta2 in (extra[:max(0, min(len(extra), args.steps + args.warmup - 1))] if args.full else []):
             res_k = meta2[4 * NCH:].cpu().numpy()
             assert (res_k == S).all()
             mism = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -412,12 +475,13 @@ def main():
         ratio = bytes_out / bytes_in
         algo = bytes_in + bytes_out
     else:
-        res = (b0.meta[4 * b0.NCH:].cpu().numpy().view(np.int64) if args.experiment_no_verify else verify_compressed(N, L, b0, torch, dev, np))
+        res = verify_compressed(N, L, b0, torch, dev, np) if verify else b0.meta[4 * b0.NCH:].cpu().numpy().view(np.int64)
         bytes_out = int(res.sum())
         ratio = bytes_in / bytes_out
         algo = bytes_in + bytes_out
     if rt is not None:
-        res = verify_compressed(N, L, rt, torch, dev, np)       # the compress half of the round trip
+        # the compress half of the round trip
+        res = verify_compressed(N, L, rt, torch, dev, np) if args.full else rt.meta[4 * rt.NCH:].cpu().numpy().view(np.int64)
         algo += rt.bytes_in + int(res.sum())
     unc_bytes = sum(b.NCH for b in batches) * S
 
@@ -426,11 +490,12 @@ def main():
 
     cpu = None
     default_case = (not mixed and dec and rt is None and args.codec == "lz4" and S == 65536 and args.lz4_mode == "auto" and args.in_flight == 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, batches, args.op, rt)
     traffic = None
     kernels_ms = None
-    if rank == 0 and world == 1 and (args.traffic == "on" or (args.traffic == "auto" and default_case)) and not os.environ.get("CJ_BENCH_CHILD"):
+    if (args.full and rank == 0 and world == 1 and (args.traffic == "on" or (args.traffic == "auto" and default_case))
+            and not os.environ.get("CJ_BENCH_CHILD")):
         traffic = measure_traffic()
         kernels_ms = measure_kernels()
 
@@ -469,6 +534,7 @@ def main():
                        **({"big_chunk_scratch_bytes": int(sum(L.cj_debug_big_scratch_bytes(b.eng.h) for b in batches)), "output_bytes_per_step": int(total_unc // world)} if S > 65536 and dec else {}),
                        "sharding": "chunk i -> gpu (i mod N), no collective; " + ("rank r generates synth-v1 indices r*%d .. r*%d+%d" % (U, U, U - 1) if corpus_files is None else "every rank tiles the same corpus chunks"),
                        "verified": "NOT VERIFIED (--experiment-no-verify): this line is INVALID as a result" if args.experiment_no_verify else
+                                   "not checked by a plain run (--full compares every result and output byte)" if not args.full else
                                    ("all results + all output bytes compared on device" if dec and rt is None else
                                     "every compressed chunk decoded again by the GPU decoder and compared with its input on device"
                                     + ("; decode half: all results + all output bytes compared on device" if rt is not None else ""))},
@@ -633,8 +699,8 @@ def measure_kernels():
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(prof):
         return None
-    base = [a for a in sys.argv[1:]]
-    for flag in ("--steps", "--warmup", "--cpu-seconds", "--traffic"):
+    base = [a for a in sys.argv[1:] if not a.startswith("--dump-outputs=")]      # (the child runs write no outputs)
+    for flag in ("--steps", "--warmup", "--cpu-seconds", "--traffic", "--dump-outputs"):
         while flag in base:
             i = base.index(flag)
             del base[i:i + 2]
@@ -674,9 +740,9 @@ def measure_traffic():
     if not os.path.exists(prof):
         return None
     steps, warm = 2, 1
-    base = [a for a in sys.argv[1:]]
+    base = [a for a in sys.argv[1:] if not a.startswith("--dump-outputs=")]      # (the child runs write no outputs)
     encodes = any(a in ("compress", "roundtrip") for a in base)
-    for flag in ("--steps", "--warmup", "--cpu-seconds", "--traffic"):
+    for flag in ("--steps", "--warmup", "--cpu-seconds", "--traffic", "--dump-outputs"):
         while flag in base:
             i = base.index(flag)
             del base[i:i + 2]

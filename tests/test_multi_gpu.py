@@ -85,7 +85,7 @@ def test_bench_control_plane_on_rccl_with_one_rank():
     cramjam_amd/shard.py:aggregate — runs on RCCL with a world of ONE rank, so it is exercised on a 1-GPU box too"""
     env = {"CJ_FORCE_DIST": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port()),
            "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
-    r = _run(["--gpus", "1", "--chunks", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--traffic", "off"], env=env, timeout=900)
+    r = _run(["--gpus", "1", "--chunks", "8192", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--traffic", "off"], env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert r.stdout.strip().splitlines()[-1].startswith('{"metric"'), r.stdout[-1500:]          # the JSON line is the LAST line (the driver reads it)
     line = json.loads(r.stdout.strip().splitlines()[-1])

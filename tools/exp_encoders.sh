@@ -4,7 +4,7 @@ for v in "$@"; do
   export CJ_HIP_LIB=$GRAFT_REPO_ROOT/cramjam_amd/variants/libcramjam_hip_$v.so
   [ "$v" = "product" ] && unset CJ_HIP_LIB
   for codec in lz4 snappy; do
-    timeout 300 python bench.py --op compress --codec $codec --no-cpu-baseline --traffic off --steps 5 --warmup 2 > $O/${v}_$codec.json 2> $O/${v}_$codec.err
+    timeout 300 python bench.py --full --op compress --codec $codec --no-cpu-baseline --traffic off --steps 5 --warmup 2 > $O/${v}_$codec.json 2> $O/${v}_$codec.err
     python -c "
 import json,sys
 t=open('$O/${v}_$codec.json').read().strip()

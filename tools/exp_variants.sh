@@ -8,7 +8,7 @@ for v in "$@"; do
   export CJ_HIP_LIB=$GRAFT_REPO_ROOT/cramjam_amd/variants/libcramjam_hip_$v.so
   [ "$v" = "product" ] && unset CJ_HIP_LIB
   echo "== $v" | tee -a $O/summary.txt
-  timeout 300 python bench.py --phase-profile --no-cpu-baseline --steps 10 $BENCH_ARGS > $O/$v.json 2> $O/$v.err
+  timeout 300 python bench.py --full --phase-profile --no-cpu-baseline --steps 10 $BENCH_ARGS > $O/$v.json 2> $O/$v.err
   grep "cycles/chunk" $O/$v.err | cut -c1-200 | tee -a $O/summary.txt
   python -c "
 import json,sys

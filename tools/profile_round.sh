@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -3 | tee $O/pytest_gpu.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --no-cpu-baseline --traffic off > $O/stats.log 2>&1
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv; head -8 $O/kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_enc -- python bench.py --op compress --no-cpu-baseline --traffic off --steps 10 > $O/stats_enc.log 2>&1
@@ -29,10 +29,10 @@ for d in sys.argv[1:]:
         print(k, ' '.join('%s=%.0f' % (c.replace('SQ_',''), max(v)/1e5) for c,v in sorted(agg[k].items())), '(per chunk of the 100 k; the launch over the full batch)')
 PY
 # the corpus lines carry their own traffic and cpu_baseline (all 20 files, liblz4 / libsnappy streams)
-python bench.py --data corpus64k --steps 20 --traffic on --cpu-seconds 10 2>/dev/null | tail -1 >> $O/other_paths.jsonl
-python bench.py --data corpus64k --codec snappy --steps 20 --traffic on --cpu-seconds 10 2>/dev/null | tail -1 >> $O/other_paths.jsonl
+python bench.py --full --data corpus64k --steps 20 --traffic on --cpu-seconds 10 2>/dev/null | tail -1 >> $O/other_paths.jsonl
+python bench.py --full --data corpus64k --codec snappy --steps 20 --traffic on --cpu-seconds 10 2>/dev/null | tail -1 >> $O/other_paths.jsonl
 for args in "--codec snappy" "--op compress" "--op compress --codec snappy" "--codec snappy --op roundtrip" "--chunks 1000000 --steps 20" "--workload mixed256k --steps 20" "--codec lz4 --chunk-bytes 262144 --chunks 8192 --unique 2048 --steps 20" "--codec snappy --chunk-bytes 262144 --chunks 8192 --unique 2048 --steps 20" "--chunks 16384 --unique 2048" "--chunks 8192 --unique 2048" "--chunks 1024 --unique 1024" "--codec snappy --chunks 8192 --unique 2048" "--codec snappy --chunks 1024 --unique 1024" "--chunk-bytes 32768 --chunks 4096 --unique 2048" "--chunk-bytes 16384 --chunks 4096 --unique 2048" "--codec snappy --chunk-bytes 32768 --chunks 4096 --unique 2048" "--codec snappy --chunk-bytes 16384 --chunks 4096 --unique 2048" "--data corpus64k --chunks 8192" "--chunk-bytes 32768 --chunks 200000" "--chunk-bytes 16384 --chunks 400000" "--codec snappy --chunk-bytes 32768 --chunks 200000" "--codec snappy --chunk-bytes 16384 --chunks 400000" "--chunk-bytes 32768 --chunks 16384 --unique 2048" "--chunk-bytes 16384 --chunks 16384 --unique 2048" "--op compress --data corpus64k --steps 10" "--op compress --data corpus64k --codec snappy --steps 10"; do
-  python bench.py --cpu-seconds 6 --traffic off $args 2>/dev/null | tail -1 >> $O/other_paths.jsonl
+  python bench.py --full --cpu-seconds 6 --traffic off $args 2>/dev/null | tail -1 >> $O/other_paths.jsonl
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_mixed -- python bench.py --workload mixed256k --no-cpu-baseline --traffic off --steps 10 > $O/stats_mixed.log 2>&1
 cp $(find $O/stats_mixed -name "*kernel_stats.csv" | head -1) $O/kernel_stats_mixed256k.csv; head -8 $O/kernel_stats_mixed256k.csv | cut -c1-70,200-300
