@@ -18,7 +18,8 @@ struct BatchArgs {
     int64_t* result;
     uint32_t n_chunks;
     uint32_t flags;
-    const uint32_t* hist;       // linked LZ4-frame blocks only (frame.hip): bytes of history before out_off[i]; nullptr = none
+    const uint32_t* hist;       // linked LZ4-frame blocks only: bytes of history before out_off[i] (decoders, frame.hip) / before in_off[i]
+                                // (the encoder with kFlagLinkedEnc); nullptr = none
 };
 
 // internal flag bits (never part of the C-ABI; CJ_FLAG_DEBUG_PROFILE 0x1000 is public): 0x2000 = linked-frame parse
@@ -30,6 +31,8 @@ constexpr uint32_t kFlagSplitPieces = 0x8000u;     // encoders (large.hip): the 
 constexpr uint32_t kFlagSplitShift = 16;
 __host__ __device__ inline uint32_t split_per(uint32_t flags) { return 1u << ((flags >> kFlagSplitShift) & 15u); }
 constexpr uint32_t kFlagReportTail = 0x4000u;      // LZ4 encoder (large.hip): result = size | length of the final literal run << 32
+constexpr uint32_t kFlagLinkedEnc = 1u << 20;      // LZ4 encoder (frame.hip: linked-block frames): chunk i may refer to hist[i] <= 65536 bytes of input
+                                                   // directly before in_off[i] (batch chunks only, not with kFlagSplitPieces)
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = 64 * kWavesPerBlock;

@@ -41,6 +41,50 @@ struct HashTab {
     __device__ __forceinline__ void preindex(const uint8_t* in, uint32_t q0) const {
         for (uint32_t pos = lane_id(); pos < q0; pos += 64u) set(hash_slot(ld32u(in + pos)), pos);
     }
+    // linked LZ4-frame blocks: index the history, positions [0, q0) with q0 <= 65536, so that every slot ends up with the LATEST position
+    // that hashes to it — what entering them one by one in ascending order leaves (tests/hostsim/enc2_linked_model.c) —
+    // by all `threads` threads of the chunk's workgroup at once.  A thread takes 16 consecutive positions per step from ONE 16-byte load
+    // and the dword after it (v_alignbyte, as the probe does) instead of a dword load per position: 64 KiB of history is 32 steps of a
+    // two-wavefront workgroup, not 1024 of one wavefront.  Positions from one step, other lanes and the other wavefront reach a slot in
+    // any order, so a slot is raised to its maximum by a compare-and-swap on the dword that holds it: exact, whatever
+    // the order (positions below 65536: the 16-bit value IS the position).  n = end of the chunk: no load reaches past it.
+    __device__ __forceinline__ void preindex_latest(const uint8_t* in, uint32_t q0, uint32_t n, uint32_t tid, uint32_t threads) const {
+        typedef uint32_t u32_una __attribute__((aligned(1)));
+        typedef uint32_t v4_una __attribute__((ext_vector_type(4), aligned(1)));
+        __attribute__((address_space(3))) uint32_t* t32 = (__attribute__((address_space(3))) uint32_t*)(reinterpret_cast<uint32_t*>(p));
+        for (uint32_t b = 16u * tid; b < q0; b += 16u * threads) {
+            uint32_t D[5];
+            if (b + 20u <= n) {
+                const v4_una x = *reinterpret_cast<const v4_una*>(in + b);
+                D[0] = x.x; D[1] = x.y; D[2] = x.z; D[3] = x.w;
+                D[4] = *reinterpret_cast<const u32_una*>(in + b + 16u);
+            } else {                                             // the last few positions before the block's end: dword by dword
+#pragma unroll
+                for (int j = 0; j < 5; j++) D[j] = b + 4u * j + 4u <= n ? *reinterpret_cast<const u32_una*>(in + b + 4u * j) : 0u;
+            }
+            uint32_t w[16], sh[16], old[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const uint32_t v = __builtin_amdgcn_alignbyte(D[(k >> 2) + 1], D[k >> 2], k & 3);
+                const uint32_t h = hash_slot(v);
+                w[k] = h >> 1; sh[k] = (h & 1u) * 16u;
+            }
+#pragma unroll
+            for (int k = 0; k < 16; k++) old[k] = t32[w[k]];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const uint32_t q = b + k;
+                if (q >= q0) break;
+                for (;;) {
+                    const uint32_t have = (old[k] >> sh[k]) & 0xffffu;
+                    if (have >= q) break;                                // a later position (or this one) holds the slot
+                    const uint32_t nw = (old[k] & ~(0xffffu << sh[k])) | (q << sh[k]);
+                    if (__hip_atomic_compare_exchange_strong(t32 + w[k], &old[k], nw, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+                        break;                                           // (on failure old[k] holds what the slot's dword is now)
+                }
+            }
+        }
+    }
 };
 
 // backward extension ("catch-up"): how many bytes before a / b also match, limited to `room` (bytes back to the anchor) and to b

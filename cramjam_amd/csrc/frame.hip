@@ -449,39 +449,53 @@ int64_t cj_lz4_frame_decompress_bound(const uint8_t* in, size_t n) {
     return (int64_t)total;
 }
 
-// the block sequence of a frame (u32 size word + data per 64 KiB of input, no header, no EndMark) written to out
-int64_t cj_lz4_frame_compress_blocks(const uint8_t* in, size_t n, uint8_t* out, size_t cap) {
-    if ((n && !in) || (cap && !out)) return CJ_E_BAD_ARG;
+namespace {
+// The block sequence of a frame (u32 size word + data per 64 KiB of input, no header, no EndMark) written to out.  Linked blocks: block
+// k may refer to the 64 KiB of input before it — the last <= 64 KiB of hist for block 0 — staged as hist | in on the device, so every
+// block still is one independent chunk of the batch (kFlagLinkedEnc: its history is indexed before its walk).  Linked blocks always take
+// the batch kernel: the split pieces (large.hip) restart their walk every 4 KiB, and a sub-piece whose matches lie ~64 KiB back rarely
+// finds them — their hash slots have gone to the 64 K positions after them — where one walk through the block needs a single hit (64 KiB
+// of random bytes twice: 0.502 of the independent frame in one walk, ~0.57 in sub-pieces).
+int64_t lz4_frame_blocks(const uint8_t* hist, size_t hist_len, const uint8_t* in, size_t n, uint8_t* out, size_t cap, bool linked) {
+    if ((n && !in) || (cap && !out) || (hist_len && !hist)) return CJ_E_BAD_ARG;
     cj_engine* e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
     const size_t np = (n + kLz4fBlock - 1) / kLz4fBlock;
     if (np > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
     if (np == 0) return 0;
+    const size_t H = linked ? std::min(hist_len, kLz4fBlock) : 0;        // only the last 64 KiB before the block can be referred to
+    if (H) hist += hist_len - H;
     // up to 32 MiB: sixteen (above 16 MiB: four) wavefronts per 64 KiB block (sub-pieces joined into one LZ4 block, large.hip) —
     // one wavefront per block would make every call at least the 1.7 ms it needs for 64 KiB
-    if (n > 8192 && n <= cj::large_split_max()) return cj::large_lz4_frame_blocks(in, n, out, cap);
+    if (!linked && n > 8192 && n <= cj::large_split_max()) return cj::large_lz4_frame_blocks(in, n, out, cap);
     uint64_t fpos = 0;
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    // rows: in_off|in_len|tmp_off|tmp_cap|result | src|dst_off|len|hdr (np each)
-    const size_t rows = 9 * np;
-    if (!e->d_in.reserve(n + 16) || !e->d_out.reserve(np * kLz4fTmpStride + 16) || !e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
+    // rows: in_off|in_len|tmp_off|tmp_cap|result | src|dst_off|len|hdr | hist (u32) (np each)
+    const size_t rows = (linked ? 10 : 9) * np;
+    if (!e->d_in.reserve(H + n + 16) || !e->d_out.reserve(np * kLz4fTmpStride + 16) || !e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
     uint8_t* d_in = (uint8_t*)e->d_in.p;
+    uint8_t* d_blk = d_in + H;                       // block i starts at d_blk + i * 64 KiB
     uint8_t* d_tmp = (uint8_t*)e->d_out.p;
     uint64_t* d_meta = (uint64_t*)e->d_meta.p;
     std::vector<uint64_t>& m = e->h_meta;
     m.assign(rows, 0);
+    uint32_t* mh = reinterpret_cast<uint32_t*>(m.data() + 9 * np);
     for (size_t i = 0; i < np; i++) {
-        m[i] = i * kLz4fBlock;
+        m[i] = H + i * kLz4fBlock;
         m[np + i] = std::min(kLz4fBlock, n - i * kLz4fBlock);
         m[2 * np + i] = i * kLz4fTmpStride;
         m[3 * np + i] = kLz4fTmpStride;
+        if (linked) mh[i] = i ? (uint32_t)kLz4fBlock : (uint32_t)H;
     }
     hipStream_t s = e->stream;
-    HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    if (H) HIP_TRY(hipMemcpyAsync(d_in, hist, H, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d_blk, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    if (linked) HIP_TRY(hipMemcpyAsync(d_meta + 9 * np, mh, np * 4, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     cj::BatchArgs a;
-    cj::fill_args(a, 0, np, d_in, d_meta, d_meta + np, d_tmp, d_meta + 2 * np, d_meta + 3 * np, (int64_t*)(d_meta + 4 * np));
+    cj::fill_args(a, linked ? cj::kFlagLinkedEnc : 0u, np, d_in, d_meta, d_meta + np, d_tmp, d_meta + 2 * np, d_meta + 3 * np, (int64_t*)(d_meta + 4 * np));
+    if (linked) a.hist = reinterpret_cast<const uint32_t*>(d_meta + 9 * np);
     const int rc = cj::launch(e, CJ_CODEC_LZ4_BLOCK, CJ_OP_COMPRESS, a, s);
     if (rc != 0) return rc;
     std::vector<int64_t> res(np);
@@ -493,7 +507,7 @@ int64_t cj_lz4_frame_compress_blocks(const uint8_t* in, size_t n, uint8_t* out, 
         const uint64_t len = m[np + i], cl = (uint64_t)res[i];
         const bool stored = cl >= len;
         const uint64_t body = stored ? len : cl;
-        m[5 * np + i] = (uint64_t)(uintptr_t)(stored ? d_in + i * kLz4fBlock : d_tmp + i * kLz4fTmpStride);
+        m[5 * np + i] = (uint64_t)(uintptr_t)(stored ? d_blk + i * kLz4fBlock : d_tmp + i * kLz4fTmpStride);
         m[6 * np + i] = fpos + 4;
         m[7 * np + i] = body;
         m[8 * np + i] = body | (stored ? 0x80000000ull : 0ull);
@@ -510,23 +524,41 @@ int64_t cj_lz4_frame_compress_blocks(const uint8_t* in, size_t n, uint8_t* out, 
     return (int64_t)fpos;
 }
 
-int64_t cj_lz4_frame_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, int level) {
-    (void)level;                           // the GPU matcher has one mode; any level yields a valid frame (see header)
+// header + blocks + EndMark + content checksum; FLG 0x64 (independent blocks) or 0x44 (linked), BD 0x40 (64 KiB blocks)
+int64_t lz4_frame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, bool linked) {
     if ((n && !in) || (cap && !out)) return CJ_E_BAD_ARG;
     if (!cj::default_engine()) return CJ_E_NO_DEVICE;
     if (cap < 15) return CJ_E_FRAME_WRITE;
-    // frame header: version 01, independent blocks, content checksum, 64 KiB blocks (FLG 0x64, BD 0x40)
-    uint8_t hdr[7] = { 0x04, 0x22, 0x4D, 0x18, 0x64, 0x40, 0 };
+    uint8_t hdr[7] = { 0x04, 0x22, 0x4D, 0x18, (uint8_t)(linked ? 0x44 : 0x64), 0x40, 0 };
     hdr[6] = (uint8_t)(xxh32(hdr + 4, 2, 0) >> 8);
     std::memcpy(out, hdr, 7);
     uint32_t content_sum = 0;
     std::thread summer([&] { content_sum = xxh32(in, n, 0); });          // overlaps the device batch
-    const int64_t r = cj_lz4_frame_compress_blocks(in, n, out + 7, cap - 15);
+    const int64_t r = lz4_frame_blocks(nullptr, 0, in, n, out + 7, cap - 15, linked);
     summer.join();
     if (r < 0) return r;
     xwr32(out + 7 + r, 0u);                  // EndMark
     xwr32(out + 11 + r, content_sum);
     return r + 15;
+}
+}  // namespace
+
+int64_t cj_lz4_frame_compress_blocks(const uint8_t* in, size_t n, uint8_t* out, size_t cap) {
+    return lz4_frame_blocks(nullptr, 0, in, n, out, cap, false);
+}
+
+int64_t cj_lz4_frame_compress_blocks_linked(const uint8_t* hist, size_t hist_len, const uint8_t* in, size_t n, uint8_t* out, size_t cap) {
+    return lz4_frame_blocks(hist, hist_len, in, n, out, cap, true);
+}
+
+int64_t cj_lz4_frame_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, int level) {
+    (void)level;                           // the GPU matcher has one mode; any level yields a valid frame (see header)
+    return lz4_frame(in, n, out, cap, false);
+}
+
+int64_t cj_lz4_frame_compress_linked(const uint8_t* in, size_t n, uint8_t* out, size_t cap, int level) {
+    (void)level;
+    return lz4_frame(in, n, out, cap, true);
 }
 
 int64_t cj_lz4_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap) {

@@ -69,10 +69,17 @@ struct Lz4Fmt {
 // piece is cut into split_per(flags) = 16 or 4 consecutive sub-pieces, one wavefront each — the chunks of the batch ARE the sub-pieces,
 // position 0 of a walk = the start of its piece.  Each wavefront first indexes the data BEFORE its sub-piece (HashTab::preindex), so it
 // finds what a serial walk over the piece would; each writes its own stream, and the streams are stitched like any other pieces.
-template <bool kSplit, int kW>
+//
+// Linked blocks (kLinked, kFlagLinkedEnc: the blocks of a linked-block LZ4 frame, batch chunks only): position 0 moves back by hist[i]
+// <= 65536 bytes of the input before the chunk, and both wavefronts index them (HashTab::preindex_latest) before the first round.  All
+// of that input is on the device before any block is encoded, so linked blocks are encoded exactly as independently as the others; only
+// their decoding is sequential.  The bytes are tests/hostsim/enc2_linked_model.c's.
+template <bool kSplit, int kW, bool kLinked = false>
 __device__ __forceinline__ void lz4_encode_chunk(const BatchArgs& a, uint32_t chunk, const HashTab& ht, uint32_t* scr, uint32_t wave) {
-    const uint64_t base_off = kSplit ? a.in_off[chunk & ~(split_per(a.flags) - 1u)] : a.in_off[chunk];      // the piece's first sub-piece
-    const uint8_t* in = a.in_base + base_off;               // position 0 = start of the piece
+    const uint32_t first_sub = kSplit ? chunk & ~(split_per(a.flags) - 1u) : chunk;      // the piece's first sub-piece
+    const uint32_t hist = kLinked ? uni(a.hist[first_sub]) : 0u;
+    const uint64_t base_off = a.in_off[first_sub] - hist;
+    const uint8_t* in = a.in_base + base_off;               // position 0 = start of the piece (minus the history of a linked block)
     const uint32_t q0 = (uint32_t)(a.in_off[chunk] - base_off);      // this wave's range = [q0, n)
     const uint64_t n64 = q0 + a.in_len[chunk];
     uint8_t* out = a.out_base + a.out_off[chunk];
@@ -92,8 +99,14 @@ __device__ __forceinline__ void lz4_encode_chunk(const BatchArgs& a, uint32_t ch
     }
     uint32_t anchor = q0, op = 0;
     if (n - q0 >= 13u) {
-        ht.clear(threadIdx.x, 64u * kW);
-        if constexpr (kSplit) ht.preindex(in, q0);
+        if constexpr (kLinked) {
+            ht.clear(threadIdx.x, 64u * kW);
+            __syncthreads();                                // every dword cleared before either wavefront raises one
+            ht.preindex_latest(in, q0, n, threadIdx.x, 64u * kW);
+        } else {
+            ht.clear(threadIdx.x, 64u * kW);
+            if constexpr (kSplit) ht.preindex(in, q0);
+        }
         ht.settle();
         enc2::Walk<Lz4Fmt, kW> w{enc2::uniform_gptr(in), (enc2::gptr)enc2::uniform_gptr(out), n, Lz4Fmt::last_start(n), Lz4Fmt::limit(n), scr, ht, 0u, 0u, wave};
         anchor = w.run(q0);
@@ -113,13 +126,13 @@ __device__ __forceinline__ void lz4_encode_chunk(const BatchArgs& a, uint32_t ch
     if (lane == 0) a.result[chunk] = (int64_t)(((uint64_t)op + (prefix ? 4u : 0u)) | tail_report);
 }
 
-template <bool kSplit, int kW>
+template <bool kSplit, int kW, bool kLinked = false>
 __global__ __launch_bounds__(64 * kW) void lz4_encode_kernel(BatchArgs a) {
     __shared__ uint16_t ht_lds[kHashSize];
     __shared__ uint32_t scr[enc2::Walk<Lz4Fmt, kW>::kWords];
     const uint32_t chunk = blockIdx.x;
     if (chunk >= a.n_chunks) return;
-    lz4_encode_chunk<kSplit, kW>(a, chunk, HashTab{ht_lds}, scr, uni(threadIdx.x >> 6));
+    lz4_encode_chunk<kSplit, kW, kLinked>(a, chunk, HashTab{ht_lds}, scr, uni(threadIdx.x >> 6));
 }
 
 // Two wavefronts per chunk (cj_enc2.hpp): a CU's LDS holds nine tables, a wavefront issues one instruction per ~5 cycles — two per
@@ -143,9 +156,13 @@ hipError_t launch_lz4_encode(const BatchArgs& a, hipStream_t s) {
     for (uint32_t start = 0; start < a.n_chunks; start += kEncGrid) {
         BatchArgs b = a;
         b.in_off += start; b.in_len += start; b.out_off += start; b.out_cap += start; b.result += start;
+        if (b.hist) b.hist += start;
         b.n_chunks = a.n_chunks - start < kEncGrid ? a.n_chunks - start : kEncGrid;
         // (sub-pieces of a split piece are indexed from their piece's first one: a slice starts on a piece boundary — kEncGrid is a multiple of every split)
+        const bool linked = (a.flags & kFlagLinkedEnc) != 0;
+        if (linked && (a.hist == nullptr || (a.flags & kFlagSplitPieces))) return hipErrorInvalidValue;
         if (a.flags & kFlagSplitPieces) hipLaunchKernelGGL((lz4_encode_kernel<true, 1>), dim3(b.n_chunks), dim3(64), 0, s, b);
+        else if (linked) hipLaunchKernelGGL((lz4_encode_kernel<false, kEncWaves, true>), dim3(b.n_chunks), dim3(64 * kEncWaves), 0, s, b);
         else hipLaunchKernelGGL((lz4_encode_kernel<false, kEncWaves>), dim3(b.n_chunks), dim3(64 * kEncWaves), 0, s, b);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;

@@ -1055,8 +1055,10 @@ struct CompressorObject {
     int codec;                   // 0 snappy, 1 lz4
     bool finished, started, content_checksum;
     bool busy;                   // a flush()/finish() of this object is running with the GIL released
+    bool linked;                 // lz4: block_linked=True — linked blocks, `hist` = the last <= 64 KiB of input already compressed
     int level;
     ByteVec* pending;
+    ByteVec* hist;
     cj::Xxh32* hash;
 };
 // pyo3 guards &mut self with a borrow flag and raises "Already borrowed" on re-entry (src/io.rs:761-814 take &mut self);
@@ -1075,7 +1077,9 @@ PyObject* Compressor_new_common(PyTypeObject* type, int codec) {
     CompressorObject* self = (CompressorObject*)type->tp_alloc(type, 0);
     if (!self) return nullptr;
     self->codec = codec; self->finished = false; self->started = false; self->content_checksum = true; self->level = -1; self->busy = false;
+    self->linked = false;
     self->pending = new ByteVec();
+    self->hist = new ByteVec();
     self->hash = new cj::Xxh32(0);
     return (PyObject*)self;
 }
@@ -1093,11 +1097,12 @@ int Lz4Compressor_init(CompressorObject* self, PyObject* args, PyObject* kw) {  
     self->level = opt_int(lvl, -1);
     if (self->level == -2) return -1;
     if (cs != Py_None) { int t = PyObject_IsTrue(cs); if (t < 0) return -1; self->content_checksum = t != 0; }
-    if (bl != Py_None && PyObject_IsTrue(bl) < 0) return -1;     // accepted; blocks are always independent here
+    // block_linked: None / False keep independent blocks (the library's fastest frames to decode); True links them
+    if (bl != Py_None) { int t = PyObject_IsTrue(bl); if (t < 0) return -1; self->linked = t != 0; }
     return 0;
 }
 void Compressor_dealloc(CompressorObject* self) {
-    delete self->pending; delete self->hash;
+    delete self->pending; delete self->hist; delete self->hash;
     Py_TYPE(self)->tp_free((PyObject*)self);
 }
 
@@ -1129,7 +1134,7 @@ int64_t compressor_emit(CompressorObject* self, ByteVec& out, bool finish) {
         }
     } else {
         if (!self->started) {                  // LZ4F_compressBegin: the header exists before any data
-            uint8_t hdr[7] = { 0x04, 0x22, 0x4D, 0x18, (uint8_t)(0x60 | (self->content_checksum ? 0x04 : 0)), 0x40, 0 };
+            uint8_t hdr[7] = { 0x04, 0x22, 0x4D, 0x18, (uint8_t)(0x40 | (self->linked ? 0 : 0x20) | (self->content_checksum ? 0x04 : 0)), 0x40, 0 };
             hdr[6] = (uint8_t)(cj::xxh32(hdr + 4, 2, 0) >> 8);
             out.insert(out.end(), hdr, hdr + 7);
             self->started = true;
@@ -1137,9 +1142,17 @@ int64_t compressor_emit(CompressorObject* self, ByteVec& out, bool finish) {
         if (!pend.empty()) {
             if (self->content_checksum) self->hash->update(pend.data(), pend.size());
             ByteVec tmp(pend.size() + 4 * ((pend.size() + 65535) / 65536));
-            const int64_t r = cj_lz4_frame_compress_blocks(pend.data(), pend.size(), tmp.data(), tmp.size());
+            const int64_t r = self->linked ? cj_lz4_frame_compress_blocks_linked(self->hist->data(), self->hist->size(), pend.data(), pend.size(), tmp.data(), tmp.size())
+                                           : cj_lz4_frame_compress_blocks(pend.data(), pend.size(), tmp.data(), tmp.size());
             if (r < 0) return r;
             out.insert(out.end(), tmp.begin(), tmp.begin() + (long)r);
+            if (self->linked) {                // the next flush's blocks may refer to the last 64 KiB compressed so far
+                ByteVec& h = *self->hist;
+                const size_t keep = pend.size() >= 65536 ? 0 : std::min(h.size(), 65536 - pend.size());
+                h.erase(h.begin(), h.end() - (long)keep);
+                const size_t take = std::min<size_t>(pend.size(), 65536);
+                h.insert(h.end(), pend.end() - (long)take, pend.end());
+            }
         }
         if (finish) {
             uint8_t tail[8] = {0};
