@@ -105,7 +105,7 @@ struct cj_engine {
 };
 
 namespace cj {
-cj_engine* default_engine();     // lazily created on device $CJ_DEVICE (default 0); nullptr when no device is usable
+cj_engine* default_engine();     // lazily created on device 0 (tuning builds: $CJ_DEVICE); nullptr when no device is usable
 // submit one batch on stream s (slices very large decode batches); 0 or CJ_E_*
 int launch(cj_engine* e, cj_codec codec, cj_op op, const BatchArgs& a, hipStream_t s);
 void fill_args(BatchArgs& a, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off,

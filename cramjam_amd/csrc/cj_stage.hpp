@@ -1,0 +1,83 @@
+// cj_stage.hpp — the staging steps the framed (frame.hip) and large-buffer (large.hip) host paths share: named batch rows, the piece
+// compressor, the segment assembler and the slab decoder's tables.  The format rules stay with their callers.  Not part of the C-ABI.
+#pragma once
+#include "cj_engine.hpp"
+
+#include <initializer_list>
+
+namespace cj {
+
+void launch_crc32c_pieces(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint32_t* out, uint32_t n, hipStream_t s);
+void launch_copy_segments(const uint64_t* src, uint8_t* dst_base, const uint64_t* dst_off, const uint64_t* len,
+                          const uint64_t* hdr, uint32_t hdr_len, uint32_t n, hipStream_t s);      // frame_kernels.hip
+
+// The u64 rows of a batch of n chunks, one after another from a base pointer (the host copy in e->h_meta or the device one in e->d_meta)
+struct BatchRows {
+    uint64_t* in_off; uint64_t* in_len; uint64_t* out_off; uint64_t* out_cap; int64_t* result;
+    uint64_t* end;               // the first row after them
+    size_t n;
+};
+inline BatchRows batch_rows(uint64_t* base, size_t n) {
+    return {base, base + n, base + 2 * n, base + 3 * n, reinterpret_cast<int64_t*>(base + 4 * n), base + 5 * n, n};
+}
+inline void fill_args(BatchArgs& a, uint32_t flags, const uint8_t* in_base, uint8_t* out_base, const BatchRows& r) {
+    fill_args(a, flags, r.n, in_base, r.in_off, r.in_len, out_base, r.out_off, r.out_cap, r.result);
+}
+
+// Compress in[0, n), cut into pieces of `piece` bytes, as ONE batch into e->d_out (`stride` bytes apart), the input staged at e->d_in + H
+// behind the last H bytes before it (hist: linked LZ4 blocks, kFlagLinkedEnc — piece 0 may refer to those H bytes, every other piece to
+// the piece before it).  Queues the results' copy into res and, with `first`, the stitch plan kernel (first[i] = literal length of piece
+// i's first sequence); the caller synchronizes.  The batch rows lie at e->d_meta (device) / e->h_meta (host); 12 rows per piece are
+// reserved, the ones past batch_rows(.., np).end are the caller's.
+int compress_pieces(cj_engine* e, cj_codec codec, uint32_t flags, const uint8_t* in, size_t n, size_t piece, size_t stride,
+                    std::vector<int64_t>& res, std::vector<uint32_t>* first = nullptr, const uint8_t* hist = nullptr, size_t H = 0);
+
+// One list of copy_segments rows: segment i = len bytes from the device address src to offset dst of the stream, behind the low
+// hdr_len bytes of hdr
+struct Segments {
+    size_t n;
+    uint32_t hdr_len;
+    std::vector<uint64_t> rows;           // src | dst | len [| hdr], n each
+    Segments(size_t n_, uint32_t hdr_len_) : n(n_), hdr_len(hdr_len_), rows((hdr_len_ ? 4 : 3) * n_, 0) {}
+    void set(size_t i, const void* src, uint64_t dst, uint64_t len, uint64_t hdr = 0) {
+        rows[i] = (uint64_t)(uintptr_t)src; rows[n + i] = dst; rows[2 * n + i] = len;
+        if (hdr_len) rows[3 * n + i] = hdr;
+    }
+};
+
+// The output of a compress path, assembled in e->d_frame and copied to out: `lead` bytes at offset 0 (the Snappy stream identifier,
+// the varint of a raw stream), then every list by one upload and one copy_segments launch.  `extra` bytes behind the stream are the
+// caller's: more(d_extra) queues what else writes the stream (the LZ4 stitch kernel).  Returns 0 or CJ_E_*.
+template <class F>
+int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lead_len, std::initializer_list<const Segments*> lists,
+             size_t extra, F&& more, uint8_t* out) {
+    hipStream_t s = e->stream;
+    const size_t tail = (size + 15u) & ~(uint64_t)15u;
+    size_t rows = 0;
+    for (const Segments* l : lists) rows += l->rows.size();
+    if (!e->d_frame.reserve(tail + extra + rows * 8 + 64)) return CJ_E_OOM;
+    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
+    uint64_t* d_rows = reinterpret_cast<uint64_t*>(d_frame + tail + extra);
+    if (lead_len) HIP_TRY(hipMemcpyAsync(d_frame, lead, lead_len, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    for (const Segments* l : lists) {
+        HIP_TRY(hipMemcpyAsync(d_rows, l->rows.data(), l->rows.size() * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+        launch_copy_segments(d_rows, d_frame, d_rows + l->n, d_rows + 2 * l->n, l->hdr_len ? d_rows + 3 * l->n : nullptr, l->hdr_len,
+                             (uint32_t)l->n, s);
+        d_rows += l->rows.size();
+    }
+    const int rc = more(d_frame + tail);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(out, d_frame, size, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    return 0;
+}
+inline int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lead_len, std::initializer_list<const Segments*> lists, uint8_t* out) {
+    return assemble(e, size, lead, lead_len, lists, 0, [](uint8_t*) { return 0; }, out);
+}
+
+// The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
+struct SlabTabs { uint32_t grid, tab_stride, cross_stride; void* tabs; void* cross; };
+int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);
+
+}  // namespace cj

@@ -6,16 +6,13 @@
 // pieces, which is exactly the batch the block engine wants: the host walks the 4-byte chunk headers (a serial
 // but trivial scan), the GPU decodes/encodes every piece in one batch, checksums every piece (crc32c_pieces) and
 // assembles the stream (copy_segments).  No codec or checksum arithmetic runs on the host.
-#include "cj_engine.hpp"
+#include "cj_stage.hpp"
 #include "xxh32_host.hpp"
 #include "lz4_lane_walk.hpp"
 
 #include <atomic>
 
 namespace cj {
-void launch_crc32c_pieces(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint32_t* out, uint32_t n, hipStream_t s);
-void launch_copy_segments(const uint64_t* src, uint8_t* dst_base, const uint64_t* dst_off, const uint64_t* len,
-                          const uint64_t* hdr, uint32_t hdr_len, uint32_t n, hipStream_t s);
 void launch_lz4_frame_chain(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint32_t nblk, uint8_t* out,
                             uint64_t out_cap, uint32_t block_max, int64_t* result, hipStream_t s);
 }
@@ -133,13 +130,14 @@ int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, si
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
     // device meta rows (u64): compressed pieces in_off|in_len|out_off|out_cap|result (nc each), stored pieces
     // src|dst_off|len (ns each), all pieces off|len (np each), then np u32 checksums
-    const size_t r_c = 0, r_s = 5 * nc, r_p = r_s + 3 * ns, r_crc = r_p + 2 * np, rows = r_crc + (np + 1) / 2;
+    const size_t r_s = 5 * nc, r_p = r_s + 3 * ns, r_crc = r_p + 2 * np, rows = r_crc + (np + 1) / 2;
     if (!e->d_frame.reserve(n + 16) || !e->d_out.reserve(total + 16) || !e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
     uint8_t* d_in = (uint8_t*)e->d_frame.p;
     uint8_t* d_out = (uint8_t*)e->d_out.p;
     uint64_t* d_meta = (uint64_t*)e->d_meta.p;
     std::vector<uint64_t>& m = e->h_meta;
     m.assign(rows, 0);
+    const cj::BatchRows mc = cj::batch_rows(m.data(), nc), dc = cj::batch_rows(d_meta, nc);
     size_t ci = 0, si = 0;
     for (size_t i = 0; i < np; i++) {
         const Piece& p = pieces[i];
@@ -149,10 +147,10 @@ int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, si
             m[r_s + 2 * ns + si] = p.dst_len;
             si++;
         } else {
-            m[r_c + ci] = p.src_off;
-            m[r_c + nc + ci] = p.src_len;
-            m[r_c + 2 * nc + ci] = p.dst_off;
-            m[r_c + 3 * nc + ci] = p.dst_len;       // snap decodes into dst[..decompress_len]
+            mc.in_off[ci] = p.src_off;
+            mc.in_len[ci] = p.src_len;
+            mc.out_off[ci] = p.dst_off;
+            mc.out_cap[ci] = p.dst_len;             // snap decodes into dst[..decompress_len]
             ci++;
         }
         m[r_p + i] = p.dst_off;
@@ -163,8 +161,7 @@ int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, si
     HIP_TRY(hipMemcpyAsync(d_meta, m.data(), r_crc * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     if (nc) {
         cj::BatchArgs a;
-        cj::fill_args(a, 0, nc, d_in, d_meta + r_c, d_meta + r_c + nc, d_out, d_meta + r_c + 2 * nc, d_meta + r_c + 3 * nc,
-                      (int64_t*)(d_meta + r_c + 4 * nc));
+        cj::fill_args(a, 0, d_in, d_out, dc);
         const int rc = cj::launch(e, CJ_CODEC_SNAPPY_RAW, CJ_OP_DECOMPRESS, a, s);
         if (rc != 0) return rc;
     }
@@ -173,7 +170,7 @@ int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, si
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<int64_t> res(nc);
     std::vector<uint32_t> crc(np);
-    if (nc) HIP_TRY(hipMemcpyAsync(res.data(), d_meta + r_c + 4 * nc, nc * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    if (nc) HIP_TRY(hipMemcpyAsync(res.data(), dc.result, nc * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(crc.data(), d_meta + r_crc, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
 
@@ -206,58 +203,34 @@ int64_t cj_snappy_frame_compress(const uint8_t* in, size_t n, uint8_t* out, size
 
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    // rows: in_off|in_len|tmp_off|tmp_cap|result | src|dst_off|len|hdr (np each) | np u32 checksums
-    const size_t r_crc = 9 * np, rows = r_crc + (np + 1) / 2;
-    if (!e->d_in.reserve(n + 16) || !e->d_out.reserve(np * kTmpStride + 16) || !e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    std::vector<uint64_t>& m = e->h_meta;
-    m.assign(rows, 0);
-    for (size_t i = 0; i < np; i++) {
-        m[i] = i * kPiece;
-        m[np + i] = std::min(kPiece, n - i * kPiece);
-        m[2 * np + i] = i * kTmpStride;
-        m[3 * np + i] = kTmpStride;
-    }
     hipStream_t s = e->stream;
-    HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    cj::BatchArgs a;
-    cj::fill_args(a, 0, np, d_in, d_meta, d_meta + np, d_tmp, d_meta + 2 * np, d_meta + 3 * np, (int64_t*)(d_meta + 4 * np));
-    const int rc = cj::launch(e, CJ_CODEC_SNAPPY_RAW, CJ_OP_COMPRESS, a, s);
+    std::vector<int64_t> res;
+    int rc = cj::compress_pieces(e, CJ_CODEC_SNAPPY_RAW, 0u, in, n, kPiece, kTmpStride, res);
     if (rc != 0) return rc;
-    cj::launch_crc32c_pieces(d_in, d_meta, d_meta + np, (uint32_t*)(d_meta + r_crc), (uint32_t)np, s);
+    const uint8_t* d_in = (const uint8_t*)e->d_in.p;
+    const uint8_t* d_tmp = (const uint8_t*)e->d_out.p;
+    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, np);
+    uint32_t* d_crc = reinterpret_cast<uint32_t*>(d.end);
+    cj::launch_crc32c_pieces(d_in, d.in_off, d.in_len, d_crc, (uint32_t)np, s);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    std::vector<int64_t> res(np);
     std::vector<uint32_t> crc(np);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_meta + 4 * np, np * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(crc.data(), d_meta + r_crc, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(crc.data(), d_crc, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
 
     // chunk layout (snap frame.rs compress_frame): stored when compressed_len >= len - len/8
+    cj::Segments seg(np, 8);
     uint64_t fpos = 10;
     for (size_t i = 0; i < np; i++) {
         if (res[i] < 0) return res[i];
-        const uint64_t len = m[np + i], cl = (uint64_t)res[i];
+        const uint64_t len = std::min(kPiece, n - i * kPiece), cl = (uint64_t)res[i];
         const bool stored = cl >= len - len / 8;
         const uint64_t body = stored ? len : cl;
-        m[5 * np + i] = (uint64_t)(uintptr_t)(stored ? d_in + i * kPiece : d_tmp + i * kTmpStride);
-        m[6 * np + i] = fpos + 8;
-        m[7 * np + i] = body;
-        m[8 * np + i] = (stored ? 1ull : 0ull) | ((body + 4) << 8) | ((uint64_t)crc[i] << 32);
+        seg.set(i, stored ? d_in + i * kPiece : d_tmp + i * kTmpStride, fpos + 8, body, (stored ? 1ull : 0ull) | ((body + 4) << 8) | ((uint64_t)crc[i] << 32));
         fpos += 8 + body;
     }
     if (fpos > cap) return CJ_E_FRAME_WRITE;
-    if (!e->d_frame.reserve(fpos + 16)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    HIP_TRY(hipMemcpyAsync(d_frame, kIdent, 10, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_meta + 5 * np, m.data() + 5 * np, 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    cj::launch_copy_segments(d_meta + 5 * np, d_frame, d_meta + 6 * np, d_meta + 7 * np, d_meta + 8 * np, 8, (uint32_t)np, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, d_frame, fpos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)fpos;
+    rc = cj::assemble(e, fpos, kIdent, 10, {&seg}, out);
+    return rc != 0 ? rc : (int64_t)fpos;
 }
 
 // =====================================================================================================================
@@ -358,16 +331,17 @@ int lz4_frame_linked_lds(cj_engine* e, const Lz4Frame& f, const uint8_t* d_in, s
     uint64_t* d_meta = (uint64_t*)e->d_meta.p;
     std::vector<uint64_t>& m = e->h_meta;
     m.assign(rows, 0);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(m.data() + 5 * nb);
+    const cj::BatchRows mb = cj::batch_rows(m.data(), nb), d = cj::batch_rows(d_meta, nb);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(mb.end);
     for (size_t i = 0; i < nb; i++) {
         const Lz4Block& b = f.blocks[i];
-        m[i] = b.src_off;
-        m[nb + i] = (uint64_t)(b.word & 0x7FFFFFFFu) | ((b.word & 0x80000000u) ? (1ull << 63) : 0ull);
-        m[2 * nb + i] = i * B;
-        m[3 * nb + i] = B;
+        mb.in_off[i] = b.src_off;
+        mb.in_len[i] = (uint64_t)(b.word & 0x7FFFFFFFu) | ((b.word & 0x80000000u) ? (1ull << 63) : 0ull);
+        mb.out_off[i] = i * B;
+        mb.out_cap[i] = B;
         hist[i] = i ? 65536u : 0u;
     }
-    uint32_t* fr = reinterpret_cast<uint32_t*>(m.data() + 5 * nb + hw);
+    uint32_t* fr = reinterpret_cast<uint32_t*>(mb.end + hw);
     fr[0] = 0u; fr[1] = (uint32_t)nb;
     uint32_t* first = reinterpret_cast<uint32_t*>(m.data() + r_first);
     for (size_t i = 0; i < nb; i++) { first[2 * i] = (uint32_t)(i * cj::kSyncPitch); first[2 * i + 1] = 0u; }
@@ -375,13 +349,12 @@ int lz4_frame_linked_lds(cj_engine* e, const Lz4Frame& f, const uint8_t* d_in, s
     HIP_TRY(hipMemsetAsync(e->d_pmeta.p, 0, cj::lz4_lds_scratch_meta_bytes(nb), s), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemsetAsync(e->d_lanelist.p, 0, 16, s), CJ_E_NO_DEVICE);
     cj::BatchArgs a;
-    cj::fill_args(a, cj::kFlagLinkedFrame, nb, d_in, d_meta, d_meta + nb, (uint8_t*)e->d_out.p, d_meta + 2 * nb, d_meta + 3 * nb,
-                  (int64_t*)(d_meta + 4 * nb));
-    a.hist = reinterpret_cast<const uint32_t*>(d_meta + 5 * nb);
+    cj::fill_args(a, cj::kFlagLinkedFrame, d_in, (uint8_t*)e->d_out.p, d);
+    a.hist = reinterpret_cast<const uint32_t*>(d.end);
     cj::launch_lz4_parse(a, e->d_sync.p, e->d_pmeta.p, s);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<uint64_t> pmeta(nb);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_meta + 4 * nb, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(res.data(), d.result, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(pmeta.data(), e->d_pmeta.p, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
     for (size_t i = 0; i < nb; i++) {
@@ -398,22 +371,19 @@ int lz4_frame_linked_lds(cj_engine* e, const Lz4Frame& f, const uint8_t* d_in, s
     if (one_wg) {
         // one workgroup walks the frame's blocks in order, the previous block in a second LDS window
         cj::launch_lz4_decode_lds2_linked(a, e->d_sync.p, e->d_pmeta.p, e->d_tab.p, (uint32_t*)e->d_lanelist.p + 2,
-                                          d_meta + 5 * nb + hw, 1u, 1u, s);
+                                          d.end + hw, 1u, 1u, s);
     } else {
         // every block is a slab of the large-stream decoder (large.hip / DESIGN 5.6): two workgroups per CU take the blocks in
         // order, a match that reaches into earlier blocks is copied from their finished output once the predecessor's
         // completion flag is up, everything else is resolved meanwhile
-        if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-        const uint32_t grid = (uint32_t)std::min<size_t>(2u * (size_t)e->n_cu, nb);
-        const uint32_t cross_stride = 3u * cj::kSyncStride * cj::kSyncEvery, tab_stride = 4u * cj::kSyncStride * cj::kSyncEvery;
-        const size_t tab_bytes = (size_t)grid * tab_stride * 16;
-        if (!e->d_bigtab.reserve(tab_bytes + (size_t)grid * cross_stride * 16 + (size_t)grid * (tab_stride + 512u) * 4)) return CJ_E_OOM;
-        cj::launch_lz4_decode_lds2_slabs(a, e->d_sync.p, e->d_pmeta.p, e->d_bigtab.p, (uint32_t*)(d_meta + r_cnt), d_meta + r_first, 0u,
-                                         (uint32_t*)(d_meta + r_done), (uint8_t*)e->d_bigtab.p + tab_bytes, tab_stride, cross_stride,
-                                         grid, s, CJ_CODEC_LZ4_BLOCK, true);
+        cj::SlabTabs tt;
+        const int rc = cj::reserve_slab_tabs(e, nb, cj::kSyncStride * cj::kSyncEvery, tt);
+        if (rc != 0) return rc;
+        cj::launch_lz4_decode_lds2_slabs(a, e->d_sync.p, e->d_pmeta.p, tt.tabs, (uint32_t*)(d_meta + r_cnt), d_meta + r_first, 0u,
+                                         (uint32_t*)(d_meta + r_done), tt.cross, tt.tab_stride, tt.cross_stride, tt.grid, s, CJ_CODEC_LZ4_BLOCK, true);
     }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_meta + 4 * nb, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);     // the decoder's stall guard reports here
+    HIP_TRY(hipMemcpyAsync(res.data(), d.result, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);     // the decoder's stall guard reports here
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
     *d_final = (uint8_t*)e->d_out.p;
     g_linked_lds_frames.fetch_add(1);
@@ -468,60 +438,28 @@ int64_t lz4_frame_blocks(const uint8_t* hist, size_t hist_len, const uint8_t* in
     // up to 32 MiB: sixteen (above 16 MiB: four) wavefronts per 64 KiB block (sub-pieces joined into one LZ4 block, large.hip) —
     // one wavefront per block would make every call at least the 1.7 ms it needs for 64 KiB
     if (!linked && n > 8192 && n <= cj::large_split_max()) return cj::large_lz4_frame_blocks(in, n, out, cap);
-    uint64_t fpos = 0;
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    // rows: in_off|in_len|tmp_off|tmp_cap|result | src|dst_off|len|hdr | hist (u32) (np each)
-    const size_t rows = (linked ? 10 : 9) * np;
-    if (!e->d_in.reserve(H + n + 16) || !e->d_out.reserve(np * kLz4fTmpStride + 16) || !e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint8_t* d_blk = d_in + H;                       // block i starts at d_blk + i * 64 KiB
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    std::vector<uint64_t>& m = e->h_meta;
-    m.assign(rows, 0);
-    uint32_t* mh = reinterpret_cast<uint32_t*>(m.data() + 9 * np);
-    for (size_t i = 0; i < np; i++) {
-        m[i] = H + i * kLz4fBlock;
-        m[np + i] = std::min(kLz4fBlock, n - i * kLz4fBlock);
-        m[2 * np + i] = i * kLz4fTmpStride;
-        m[3 * np + i] = kLz4fTmpStride;
-        if (linked) mh[i] = i ? (uint32_t)kLz4fBlock : (uint32_t)H;
-    }
-    hipStream_t s = e->stream;
-    if (H) HIP_TRY(hipMemcpyAsync(d_in, hist, H, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_blk, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    if (linked) HIP_TRY(hipMemcpyAsync(d_meta + 9 * np, mh, np * 4, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    cj::BatchArgs a;
-    cj::fill_args(a, linked ? cj::kFlagLinkedEnc : 0u, np, d_in, d_meta, d_meta + np, d_tmp, d_meta + 2 * np, d_meta + 3 * np, (int64_t*)(d_meta + 4 * np));
-    if (linked) a.hist = reinterpret_cast<const uint32_t*>(d_meta + 9 * np);
-    const int rc = cj::launch(e, CJ_CODEC_LZ4_BLOCK, CJ_OP_COMPRESS, a, s);
+    std::vector<int64_t> res;
+    int rc = cj::compress_pieces(e, CJ_CODEC_LZ4_BLOCK, linked ? cj::kFlagLinkedEnc : 0u, in, n, kLz4fBlock, kLz4fTmpStride, res, nullptr, hist, H);
     if (rc != 0) return rc;
-    std::vector<int64_t> res(np);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_meta + 4 * np, np * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
+    const uint8_t* d_blk = (const uint8_t*)e->d_in.p + H;            // block i starts at d_blk + i * 64 KiB
+    const uint8_t* d_tmp = (const uint8_t*)e->d_out.p;
     // LZ4F_makeBlock: a block that does not shrink is stored (bit 31 of the size word)
+    cj::Segments seg(np, 4);
+    uint64_t fpos = 0;
     for (size_t i = 0; i < np; i++) {
         if (res[i] < 0) return res[i];
-        const uint64_t len = m[np + i], cl = (uint64_t)res[i];
+        const uint64_t len = std::min(kLz4fBlock, n - i * kLz4fBlock), cl = (uint64_t)res[i];
         const bool stored = cl >= len;
         const uint64_t body = stored ? len : cl;
-        m[5 * np + i] = (uint64_t)(uintptr_t)(stored ? d_blk + i * kLz4fBlock : d_tmp + i * kLz4fTmpStride);
-        m[6 * np + i] = fpos + 4;
-        m[7 * np + i] = body;
-        m[8 * np + i] = body | (stored ? 0x80000000ull : 0ull);
+        seg.set(i, stored ? d_blk + i * kLz4fBlock : d_tmp + i * kLz4fTmpStride, fpos + 4, body, body | (stored ? 0x80000000ull : 0ull));
         fpos += 4 + body;
     }
     if (fpos > cap) return CJ_E_FRAME_WRITE;
-    if (!e->d_frame.reserve(fpos + 16)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    HIP_TRY(hipMemcpyAsync(d_meta + 5 * np, m.data() + 5 * np, 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    cj::launch_copy_segments(d_meta + 5 * np, d_frame, d_meta + 6 * np, d_meta + 7 * np, d_meta + 8 * np, 4, (uint32_t)np, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, d_frame, fpos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)fpos;
+    rc = cj::assemble(e, fpos, nullptr, 0, {&seg}, out);
+    return rc != 0 ? rc : (int64_t)fpos;
 }
 
 // header + blocks + EndMark + content checksum; FLG 0x64 (independent blocks) or 0x44 (linked), BD 0x40 (64 KiB blocks)
@@ -634,20 +572,21 @@ int64_t cj_lz4_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, size_
             uint64_t* d_meta = (uint64_t*)e->d_meta.p;
             std::vector<uint64_t>& m = e->h_meta;
             m.assign(rows, 0);
+            const cj::BatchRows mc = cj::batch_rows(m.data(), nc), dc = cj::batch_rows(d_meta, nc);
             size_t ci = 0;
             for (const Lz4Block& b : f.blocks) {
                 if (b.word & 0x80000000u) continue;
-                m[ci] = b.src_off; m[nc + ci] = b.word; m[2 * nc + ci] = ci * B; m[3 * nc + ci] = B;
+                mc.in_off[ci] = b.src_off; mc.in_len[ci] = b.word; mc.out_off[ci] = ci * B; mc.out_cap[ci] = B;
                 ci++;
             }
             std::vector<int64_t> cres(nc);
             if (nc) {
                 HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * nc * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
                 cj::BatchArgs a;
-                cj::fill_args(a, 0, nc, d_in, d_meta, d_meta + nc, d_tmp, d_meta + 2 * nc, d_meta + 3 * nc, (int64_t*)(d_meta + 4 * nc));
+                cj::fill_args(a, 0, d_in, d_tmp, dc);
                 const int rc = cj::launch(e, CJ_CODEC_LZ4_BLOCK, CJ_OP_DECOMPRESS, a, s);
                 if (rc != 0) return rc;
-                HIP_TRY(hipMemcpyAsync(cres.data(), d_meta + 4 * nc, nc * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+                HIP_TRY(hipMemcpyAsync(cres.data(), dc.result, nc * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
             }
             HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
             ci = 0;

@@ -16,12 +16,9 @@
 #include "cj_engine.hpp"
 #include "lz4_lane_walk.hpp"
 #include "big_parse.hpp"
+#include "cj_stage.hpp"
 
 namespace cj {
-
-void launch_copy_segments(const uint64_t* src, uint8_t* dst_base, const uint64_t* dst_off, const uint64_t* len,
-                          const uint64_t* hdr, uint32_t hdr_len, uint32_t n, hipStream_t s);      // frame_kernels.hip
-void launch_crc32c_pieces(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint32_t* out, uint32_t n, hipStream_t s);
 
 namespace {
 
@@ -87,32 +84,60 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_stitch_kernel(const Stitch*
 }
 
 inline uint32_t varint_len(uint64_t v) { uint32_t k = 1; while (v >= 0x80u) { v >>= 7; k++; } return k; }
+inline uint32_t put_varint(uint8_t* p, uint64_t v) {       // Snappy's length header; returns its length
+    uint32_t k = 0;
+    for (; v >= 0x80u; v >>= 7) p[k++] = (uint8_t)(v | 0x80u);
+    p[k++] = (uint8_t)v;
+    return k;
+}
 
 }  // namespace
 
-// compress the np pieces of d_in as one batch into d_tmp (stride bytes apart); results -> res
-static int compress_pieces(cj_engine* e, cj_codec codec, uint32_t flags, const uint8_t* in, size_t n, size_t piece, size_t np, size_t stride,
-                           std::vector<int64_t>& res) {
+int compress_pieces(cj_engine* e, cj_codec codec, uint32_t flags, const uint8_t* in, size_t n, size_t piece, size_t stride,
+                    std::vector<int64_t>& res, std::vector<uint32_t>* first, const uint8_t* hist, size_t H) {
     hipStream_t s = e->stream;
-    if (!e->d_in.reserve(n + 16) || !e->d_out.reserve(np * stride + 16) || !e->d_meta.reserve(12 * np * 8)) return CJ_E_OOM;
+    const size_t np = (n + piece - 1) / piece;
+    const bool linked = flags & kFlagLinkedEnc;
+    if (!e->d_in.reserve(H + n + 16) || !e->d_out.reserve(np * stride + 16) || !e->d_meta.reserve(12 * np * 8)) return CJ_E_OOM;
     uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    std::vector<uint64_t>& m = e->h_meta;
-    m.assign(12 * np, 0);
+    e->h_meta.assign(12 * np, 0);
+    const BatchRows m = batch_rows(e->h_meta.data(), np), d = batch_rows((uint64_t*)e->d_meta.p, np);
+    uint32_t* m_hist = reinterpret_cast<uint32_t*>(m.end);                 // linked: bytes of history before every piece
+    uint32_t* d_first = reinterpret_cast<uint32_t*>(d.end + np);
     for (size_t i = 0; i < np; i++) {
-        m[i] = i * piece;
-        m[np + i] = std::min(piece, n - i * piece);
-        m[2 * np + i] = i * stride;
-        m[3 * np + i] = stride;
+        m.in_off[i] = H + i * piece;
+        m.in_len[i] = std::min(piece, n - i * piece);
+        m.out_off[i] = i * stride;
+        m.out_cap[i] = stride;
+        if (linked) m_hist[i] = i ? (uint32_t)piece : (uint32_t)H;
     }
-    HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    if (H) HIP_TRY(hipMemcpyAsync(d_in, hist, H, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d_in + H, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d.in_off, m.in_off, 4 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    if (linked) HIP_TRY(hipMemcpyAsync(d.end, m_hist, np * 4, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     BatchArgs a;
-    fill_args(a, flags, np, d_in, d_meta, d_meta + np, (uint8_t*)e->d_out.p, d_meta + 2 * np, d_meta + 3 * np, (int64_t*)(d_meta + 4 * np));
+    fill_args(a, flags, d_in, (uint8_t*)e->d_out.p, d);
+    if (linked) a.hist = reinterpret_cast<const uint32_t*>(d.end);
     const int rc = launch(e, codec, CJ_OP_COMPRESS, a, s);
     if (rc != 0) return rc;
     res.resize(np);
-    HIP_TRY(hipMemcpyAsync(res.data(), d_meta + 4 * np, np * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(res.data(), d.result, np * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    if (first) {
+        hipLaunchKernelGGL(lz4_stitch_plan_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const uint8_t*)e->d_out.p, (uint32_t)stride,
+                           d_first, (uint32_t)np);
+        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+        first->resize(np);
+        HIP_TRY(hipMemcpyAsync(first->data(), d_first, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    }
+    return 0;
+}
+
+// the plan to d_plan, then the stitch kernel that writes it into the stream at e->d_frame
+static int stitch(cj_engine* e, const std::vector<Stitch>& plan, uint8_t* d_plan) {
+    const size_t nq = plan.size();
+    HIP_TRY(hipMemcpyAsync(d_plan, plan.data(), nq * sizeof(Stitch), hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
+    hipLaunchKernelGGL(lz4_stitch_kernel, dim3((unsigned)((nq + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlockThreads), 0, e->stream,
+                       reinterpret_cast<const Stitch*>(d_plan), (const uint8_t*)e->d_in.p, (uint8_t*)e->d_frame.p, (uint32_t)nq);
     return 0;
 }
 
@@ -162,38 +187,26 @@ int64_t large_snappy_compress(const uint8_t* in, size_t n, uint8_t* out, size_t 
     const size_t np = (n + piece - 1) / piece;
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    hipStream_t s = e->stream;
     std::vector<int64_t> res;
-    int rc = compress_pieces(e, CJ_CODEC_SNAPPY_RAW, split ? sp.flags : 0u, in, n, piece, np, stride, res);
+    int rc = compress_pieces(e, CJ_CODEC_SNAPPY_RAW, split ? sp.flags : 0u, in, n, piece, stride, res);
     if (rc != 0) return rc;
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
 
-    std::vector<uint64_t>& m = e->h_meta;
     uint8_t hdr[10];
-    uint32_t hl = 0;
-    for (uint64_t v = n;; ) { if (v < 0x80u) { hdr[hl++] = (uint8_t)v; break; } hdr[hl++] = (uint8_t)(v | 0x80u); v >>= 7; }
+    const uint32_t hl = put_varint(hdr, n);
+    const uint8_t* d_tmp = (const uint8_t*)e->d_out.p;
+    Segments seg(np, 0);
     uint64_t pos = hl;
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
     for (size_t i = 0; i < np; i++) {
         if (res[i] < 0) return res[i];
-        const uint32_t ph = varint_len(m[np + i]);             // the piece's own length header is dropped
+        const uint32_t ph = varint_len(std::min(piece, n - i * piece));      // the piece's own length header is dropped
         const uint64_t body = (uint64_t)res[i] - ph;
-        m[5 * np + i] = (uint64_t)(uintptr_t)(d_tmp + i * stride + ph);
-        m[6 * np + i] = pos;
-        m[7 * np + i] = body;
+        seg.set(i, d_tmp + i * stride + ph, pos, body);
         pos += body;
     }
     if (pos > cap) return CJ_E_SNAPPY_BUF_SMALL;
-    if (!e->d_frame.reserve(pos + 16)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    HIP_TRY(hipMemcpyAsync(d_frame, hdr, hl, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_meta + 5 * np, m.data() + 5 * np, 3 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_copy_segments(d_meta + 5 * np, d_frame, d_meta + 6 * np, d_meta + 7 * np, nullptr, 0, (uint32_t)np, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, d_frame, pos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)pos;
+    rc = assemble(e, pos, hdr, hl, {&seg}, out);
+    return rc != 0 ? rc : (int64_t)pos;
 }
 
 int64_t large_lz4_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, bool prefix) {
@@ -207,34 +220,19 @@ int64_t large_lz4_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap
     if (cap < pre) return CJ_E_COMPRESS_FAILED;
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    hipStream_t s = e->stream;
     std::vector<int64_t> res;
-    int rc = compress_pieces(e, CJ_CODEC_LZ4_BLOCK, kFlagReportTail | (split ? sp.flags : 0u), in, n, piece, np, stride, res);
+    std::vector<uint32_t> first;
+    int rc = compress_pieces(e, CJ_CODEC_LZ4_BLOCK, kFlagReportTail | (split ? sp.flags : 0u), in, n, piece, stride, res, &first);
     if (rc != 0) return rc;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
-    uint32_t* d_first = (uint32_t*)(d_meta + 5 * np);
-    hipLaunchKernelGGL(lz4_stitch_plan_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, d_tmp, (uint32_t)stride, d_first, (uint32_t)np);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    std::vector<uint32_t> first(np);
-    HIP_TRY(hipMemcpyAsync(first.data(), d_first, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
 
     std::vector<Stitch> plan(np);
     for (size_t i = 0; i < np; i++) if (res[i] < 0) return res[i];
-    const uint64_t pos = plan_stitch(plan, 0, np, 0, n, piece, stride, d_tmp, res, first);
+    const uint64_t pos = plan_stitch(plan, 0, np, 0, n, piece, stride, (const uint8_t*)e->d_out.p, res, first);
     if (pos + pre > cap) return CJ_E_COMPRESS_FAILED;
-    if (!e->d_frame.reserve(pos + np * sizeof(Stitch) + 64)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    Stitch* d_plan = reinterpret_cast<Stitch*>(d_frame + ((pos + 15u) & ~(uint64_t)15u));
-    HIP_TRY(hipMemcpyAsync(d_plan, plan.data(), np * sizeof(Stitch), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    hipLaunchKernelGGL(lz4_stitch_kernel, dim3((unsigned)((np + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlockThreads), 0, s,
-                       d_plan, (const uint8_t*)e->d_in.p, d_frame, (uint32_t)np);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     if (prefix) { const uint32_t v = (uint32_t)n; std::memcpy(out, &v, 4); }
-    HIP_TRY(hipMemcpyAsync(out + pre, d_frame, pos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)(pos + pre);
+    rc = assemble(e, pos, nullptr, 0, {}, np * sizeof(Stitch), [&](uint8_t* d_plan) { return stitch(e, plan, d_plan); }, out + pre);
+    return rc != 0 ? rc : (int64_t)(pos + pre);
 }
 
 
@@ -249,52 +247,31 @@ int64_t large_lz4_frame_blocks(const uint8_t* in, size_t n, uint8_t* out, size_t
     const size_t nq = (n + sub - 1) / sub, nb = (n + kPiece - 1) / kPiece;
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    hipStream_t s = e->stream;
     std::vector<int64_t> res;
-    int rc = compress_pieces(e, CJ_CODEC_LZ4_BLOCK, kFlagReportTail | sp.flags, in, n, sub, nq, sub_stride, res);
+    std::vector<uint32_t> first;
+    int rc = compress_pieces(e, CJ_CODEC_LZ4_BLOCK, kFlagReportTail | sp.flags, in, n, sub, sub_stride, res, &first);
     if (rc != 0) return rc;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint32_t* d_first = (uint32_t*)(d_meta + 5 * nq);
-    hipLaunchKernelGGL(lz4_stitch_plan_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, d_tmp, (uint32_t)sub_stride, d_first, (uint32_t)nq);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    std::vector<uint32_t> first(nq);
-    HIP_TRY(hipMemcpyAsync(first.data(), d_first, nq * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
     for (size_t i = 0; i < nq; i++) if (res[i] < 0) return res[i];
 
+    const uint8_t* d_in = (const uint8_t*)e->d_in.p;
     std::vector<Stitch> plan(nq);
-    std::vector<uint64_t> seg(4 * nb);                     // src | dst_off | len | hdr per block (copy_segments)
+    Segments seg(nb, 4);
     uint64_t fpos = 0;
     for (size_t b = 0; b < nb; b++) {
         const size_t q0 = sp.per * b, q1 = std::min(nq, q0 + sp.per);
         const uint64_t len = std::min(kPiece, n - b * kPiece);
-        const uint64_t cl = plan_stitch(plan, q0, q1, fpos + 4, n, sub, sub_stride, d_tmp, res, first);
+        const uint64_t cl = plan_stitch(plan, q0, q1, fpos + 4, n, sub, sub_stride, (const uint8_t*)e->d_out.p, res, first);
         const bool stored = cl >= len;                     // LZ4F_makeBlock: a block that does not shrink is stored
         if (stored) for (size_t q = q0; q < q1; q++) plan[q] = Stitch{0, 0, 0, 0, 0, 0};
         const uint64_t body = stored ? len : cl;
-        seg[b] = (uint64_t)(uintptr_t)(d_in + b * kPiece);
-        seg[nb + b] = fpos + 4;
-        seg[2 * nb + b] = stored ? len : 0;               // compressed blocks: the size word only, the stitch kernel writes the body
-        seg[3 * nb + b] = body | (stored ? 0x80000000ull : 0ull);
+        // compressed blocks: the size word only, the stitch kernel writes the body
+        seg.set(b, d_in + b * kPiece, fpos + 4, stored ? len : 0, body | (stored ? 0x80000000ull : 0ull));
         fpos += 4 + body;
     }
     if (fpos > cap) return CJ_E_FRAME_WRITE;
-    const size_t plan_bytes = nq * sizeof(Stitch), seg_bytes = 4 * nb * 8, tail_off = (fpos + 15u) & ~(uint64_t)15u;
-    if (!e->d_frame.reserve(tail_off + plan_bytes + seg_bytes + 64)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    Stitch* d_plan = reinterpret_cast<Stitch*>(d_frame + tail_off);
-    uint64_t* d_seg = reinterpret_cast<uint64_t*>(d_frame + tail_off + plan_bytes);
-    HIP_TRY(hipMemcpyAsync(d_plan, plan.data(), plan_bytes, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_seg, seg.data(), seg_bytes, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_copy_segments(d_seg, d_frame, d_seg + nb, d_seg + 2 * nb, d_seg + 3 * nb, 4, (uint32_t)nb, s);
-    hipLaunchKernelGGL(lz4_stitch_kernel, dim3((unsigned)((nq + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlockThreads), 0, s,
-                       d_plan, (const uint8_t*)d_in, d_frame, (uint32_t)nq);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, d_frame, fpos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)fpos;
+    rc = assemble(e, fpos, nullptr, 0, {&seg}, nq * sizeof(Stitch), [&](uint8_t* d_plan) { return stitch(e, plan, d_plan); }, out);
+    return rc != 0 ? rc : (int64_t)fpos;
 }
 
 // A Snappy framed stream (frame.hip: cj_snappy_frame_compress) for inputs of up to kSplitMax bytes: every 64 KiB piece is
@@ -311,68 +288,54 @@ int64_t large_snappy_frame(const uint8_t* in, size_t n, uint8_t* out, size_t cap
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
     hipStream_t s = e->stream;
     std::vector<int64_t> res;
-    int rc = compress_pieces(e, CJ_CODEC_SNAPPY_RAW, sp.flags, in, n, sub, nq, sub_stride, res);
+    int rc = compress_pieces(e, CJ_CODEC_SNAPPY_RAW, sp.flags, in, n, sub, sub_stride, res);
     if (rc != 0) return rc;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;             // 12 nq rows reserved; 0 .. 5 nq in use
-    uint8_t* d_tmp = (uint8_t*)e->d_out.p;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    std::vector<uint64_t> pm(2 * np);
-    for (size_t p = 0; p < np; p++) { pm[p] = p * kPiece; pm[np + p] = std::min(kPiece, n - p * kPiece); }
-    HIP_TRY(hipMemcpyAsync(d_meta + 6 * nq, pm.data(), 2 * np * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_crc32c_pieces(d_in, d_meta + 6 * nq, d_meta + 6 * nq + np, (uint32_t*)(d_meta + 9 * nq), (uint32_t)np, s);
+    // behind the batch rows: off | len per piece, varint(len) per piece (u32), the pieces' checksums (u32)
+    uint64_t* d_pm = batch_rows((uint64_t*)e->d_meta.p, nq).end;
+    const uint32_t* d_vint = reinterpret_cast<const uint32_t*>(d_pm + 2 * np);
+    uint32_t* d_crc = reinterpret_cast<uint32_t*>(d_pm + 3 * np);
+    std::vector<uint64_t> pm(2 * np + (np + 1) / 2, 0);
+    uint64_t* lens = pm.data() + np;
+    std::vector<uint32_t> vl(np);
+    for (size_t p = 0; p < np; p++) {
+        pm[p] = p * kPiece;
+        lens[p] = std::min(kPiece, n - p * kPiece);
+        vl[p] = put_varint(reinterpret_cast<uint8_t*>(pm.data() + 2 * np) + 4 * p, lens[p]);
+    }
+    HIP_TRY(hipMemcpyAsync(d_pm, pm.data(), pm.size() * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    launch_crc32c_pieces((const uint8_t*)e->d_in.p, d_pm, d_pm + np, d_crc, (uint32_t)np, s);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<uint32_t> crc(np);
-    HIP_TRY(hipMemcpyAsync(crc.data(), d_meta + 9 * nq, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(crc.data(), d_crc, np * 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
     for (size_t i = 0; i < nq; i++) if (res[i] < 0) return res[i];
 
-    std::vector<uint64_t> sa(4 * np), sb(3 * nq, 0);       // with header: src | dst | len | hdr per piece; without: src | dst | len per quarter
-    std::vector<uint32_t> vints(np, 0);
+    const uint8_t* d_in = (const uint8_t*)e->d_in.p;
+    const uint8_t* d_tmp = (const uint8_t*)e->d_out.p;
+    Segments heads(np, 8), bodies(nq, 0);                  // chunk header + stored piece or varint | the sub-pieces' element streams
     uint64_t fpos = 10;
     for (size_t p = 0; p < np; p++) {
         const size_t q0 = sp.per * p, q1 = std::min(nq, q0 + sp.per);
-        const uint64_t len = pm[np + p];
-        uint32_t vl = 0, v = 0;
-        for (uint64_t x = len;; ) { if (x < 0x80u) { v |= (uint32_t)x << (8 * vl); vl++; break; } v |= (uint32_t)((x & 0x7f) | 0x80u) << (8 * vl); vl++; x >>= 7; }
-        vints[p] = v;
-        uint64_t comp = vl;
+        const uint64_t len = lens[p];
+        uint64_t comp = vl[p];
         for (size_t q = q0; q < q1; q++) comp += (uint64_t)res[q] - varint_len(std::min(sub, n - q * sub));
         const bool stored = comp >= len - len / 8;
         const uint64_t body = stored ? len : comp;
-        sa[p] = stored ? (uint64_t)(uintptr_t)(d_in + p * kPiece) : 0ull;       // compressed: the varint (address patched below)
-        sa[np + p] = fpos + 8;
-        sa[2 * np + p] = stored ? len : vl;
-        sa[3 * np + p] = (stored ? 1ull : 0ull) | ((body + 4) << 8) | ((uint64_t)crc[p] << 32);
+        heads.set(p, stored ? (const void*)(d_in + p * kPiece) : (const void*)(d_vint + p), fpos + 8, stored ? len : vl[p],
+                  (stored ? 1ull : 0ull) | ((body + 4) << 8) | ((uint64_t)crc[p] << 32));
         if (!stored) {
-            uint64_t pos = fpos + 8 + vl;
+            uint64_t pos = fpos + 8 + vl[p];
             for (size_t q = q0; q < q1; q++) {
                 const uint32_t ph = varint_len(std::min(sub, n - q * sub));
-                sb[q] = (uint64_t)(uintptr_t)(d_tmp + q * sub_stride + ph);
-                sb[nq + q] = pos;
-                sb[2 * nq + q] = (uint64_t)res[q] - ph;
-                pos += sb[2 * nq + q];
+                bodies.set(q, d_tmp + q * sub_stride + ph, pos, (uint64_t)res[q] - ph);
+                pos += (uint64_t)res[q] - ph;
             }
         }
         fpos += 8 + body;
     }
     if (fpos > cap) return CJ_E_FRAME_WRITE;
-    const size_t tail_off = (fpos + 15u) & ~(uint64_t)15u, sa_bytes = sa.size() * 8, sb_bytes = sb.size() * 8;
-    if (!e->d_frame.reserve(tail_off + sa_bytes + sb_bytes + np * 4 + 64)) return CJ_E_OOM;
-    uint8_t* d_frame = (uint8_t*)e->d_frame.p;
-    uint64_t* d_sa = reinterpret_cast<uint64_t*>(d_frame + tail_off);
-    uint64_t* d_sb = d_sa + sa.size();
-    uint32_t* d_v = reinterpret_cast<uint32_t*>(d_sb + sb.size());
-    for (size_t p = 0; p < np; p++) if (sa[p] == 0ull) sa[p] = (uint64_t)(uintptr_t)(d_v + p);
-    HIP_TRY(hipMemcpyAsync(d_frame, kIdent, 10, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_sa, sa.data(), sa_bytes, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_sb, sb.data(), sb_bytes, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d_v, vints.data(), np * 4, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_copy_segments(d_sa, d_frame, d_sa + np, d_sa + 2 * np, d_sa + 3 * np, 8, (uint32_t)np, s);
-    launch_copy_segments(d_sb, d_frame, d_sb + nq, d_sb + 2 * nq, nullptr, 0, (uint32_t)nq, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, d_frame, fpos, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    return (int64_t)fpos;
+    rc = assemble(e, fpos, kIdent, 10, {&heads, &bodies}, out);
+    return rc != 0 ? rc : (int64_t)fpos;
 }
 
 size_t large_split_max() { return kSplitMax; }
@@ -482,105 +445,58 @@ static uint64_t g_dbg_nseq = 0;
 int64_t large_decompress(int codec, uint32_t flags, const uint8_t* in, size_t n, uint8_t* out, size_t cap) {
     cj_engine* e = default_engine();
     if (!e) return CJ_E_NO_DEVICE;
-    const bool snappy = codec == CJ_CODEC_SNAPPY_RAW;
-    const int64_t corrupt = snappy ? CJ_E_SNAPPY_CORRUPT : CJ_E_CORRUPT;
     uint64_t skip = 0, start = 0, cap64 = cap;
-    {
-        int64_t early = 0;
-        if (!large_prologue(codec, flags, in, n, cap, skip, start, cap64, early)) return early;
-    }
-    const uint32_t iend = (uint32_t)(n - skip);
-    const uint32_t piece = big_piece_for(iend);
-    const uint32_t np = (uint32_t)((iend - start + piece - 1) / piece);
+    int64_t r = 0;
+    if (!large_prologue(codec, flags, in, n, cap, skip, start, cap64, r)) return r;
+    // the prologue leaves 0 < n - skip <= 0x7FFFFFF0, 0 < cap64 <= 0xFFFFFFFF and start < n - skip: large_decompress_many's checks pass
+    const uint8_t* ins[1] = {in + skip};
+    const size_t lens[1] = {n - skip}, starts[1] = {start}, caps[1] = {cap64};
+    uint8_t* outs[1] = {out};
+    const int rc = large_decompress_many(e, codec, 1, ins, lens, starts, outs, caps, &r);
+    return rc != 0 ? rc : r;
+}
 
-    std::lock_guard<std::mutex> lock(e->mu);
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    hipStream_t s = e->stream;
-    // parse scratch, 256 B aligned regions
+// The parse scratch of one stream: 256-byte aligned regions from `base` on (base 0: offsets only); returns its size
+static size_t big_parse_layout(BigParse& bp, uintptr_t base) {
     size_t off = 0;
-    const auto region = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_status = region(64), o_bits = region((size_t)np * (piece / 8)), o_merge = region((size_t)np * 256),
-                 o_exit = region((size_t)np * 256), o_next = region((size_t)np * 256), o_fe = region((size_t)np * 256), o_entry = region((size_t)np * 8), o_lidx = region((size_t)np * 256),
-                 o_lop = region((size_t)np * 512), o_tot = region((size_t)np * 16), o_sync = region(((size_t)iend / 16 + 2) * 8);
-    if (!e->d_in.reserve(n + 64) || !e->d_big.reserve(off)) return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint8_t* b = (uint8_t*)e->d_big.p;
-    HIP_TRY(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemsetAsync(b + o_status, 0, 64, s), CJ_E_NO_DEVICE);
-    BigParse bp = {};
-    bp.in = d_in + skip; bp.iend = iend; bp.start = (uint32_t)start; bp.piece = piece; bp.np = np; bp.cap = cap64;
-    bp.bits = (uint32_t*)(b + o_bits); bp.merge = (uint32_t*)(b + o_merge); bp.exitp = (uint32_t*)(b + o_exit); bp.next_tab = (uint32_t*)(b + o_next); bp.fe_tab = (uint32_t*)(b + o_fe);
-    bp.entry = (uint2*)(b + o_entry); bp.lane_idx = (uint32_t*)(b + o_lidx); bp.lane_op = (uint64_t*)(b + o_lop);
-    bp.totals = (uint64_t*)(b + o_tot); bp.sync = (uint2*)(b + o_sync); bp.status = (uint32_t*)(b + o_status);
-    launch_big_parse(bp, codec, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    uint32_t st[16];
-    HIP_TRY(hipMemcpyAsync(st, b + o_status, 64, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    if (st[0] != 0 || st[1] != 0 || st[8] != 1) return corrupt;
-    const uint64_t n_seq = ((uint64_t)st[3] << 32) | st[2], total = ((uint64_t)st[7] << 32) | st[6];
-    if (total == 0) return 0;
-    const uint32_t n_sync = (uint32_t)((n_seq + kSyncEvery - 1) / kSyncEvery);
-    const uint32_t n_slabs = (uint32_t)((total + 65535) / 65536);
-    if (g_dbg_sync) {                                       // test hook (cj_debug_big_parse): hand the sync points to the host
-        g_dbg_nseq = n_seq;
-        g_dbg_sync->resize((size_t)n_sync * 2);
-        HIP_TRY(hipMemcpy(g_dbg_sync->data(), bp.sync, (size_t)n_sync * 8, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-    }
+    const auto region = [&](size_t bytes) { const uintptr_t p = base + off; off += (bytes + 255) & ~(size_t)255; return p; };
+    const size_t np = bp.np;
+    bp.bits = (uint32_t*)region(np * (bp.piece / 8)); bp.merge = (uint32_t*)region(np * 256); bp.exitp = (uint32_t*)region(np * 256);
+    bp.next_tab = (uint32_t*)region(np * 256); bp.fe_tab = (uint32_t*)region(np * 256); bp.entry = (uint2*)region(np * 8);
+    bp.lane_idx = (uint32_t*)region(np * 256); bp.lane_op = (uint64_t*)region(np * 512); bp.totals = (uint64_t*)region(np * 16);
+    bp.sync = (uint2*)region(((size_t)bp.iend / 16 + 2) * 8);
+    return off;
+}
 
-    // slab descriptors: 5 u64 rows | meta | first | max_rec, counter | done flags
-    const size_t r_meta = 5 * (size_t)n_slabs, r_first = r_meta + n_slabs, r_misc = r_first + n_slabs, r_done = r_misc + 2,
-                 rows = r_done + (n_slabs + 1) / 2 + 1;
-    if (!e->d_meta.reserve(rows * 8)) return CJ_E_OOM;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
-    HIP_TRY(hipMemsetAsync(d_meta + r_misc, 0, (rows - r_misc) * 8, s), CJ_E_NO_DEVICE);
-    BigSlabs sd;
-    sd.sync = bp.sync; sd.n_sync = n_sync; sd.n_seq = n_seq; sd.total = total; sd.iend = iend; sd.in_base_off = skip; sd.out_base_off = 0; sd.sync_index_base = 0; sd.n_slabs = n_slabs;
-    sd.in_off = d_meta; sd.in_len = d_meta + n_slabs; sd.out_off = d_meta + 2 * (size_t)n_slabs; sd.out_cap = d_meta + 3 * (size_t)n_slabs;
-    sd.result = (int64_t*)(d_meta + 4 * (size_t)n_slabs); sd.meta = (uint2*)(d_meta + r_meta); sd.first = (uint2*)(d_meta + r_first);
-    sd.max_rec = (uint32_t*)(d_meta + r_misc);
-    launch_big_slabs(sd, s);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    uint32_t max_rec = 0;
-    HIP_TRY(hipMemcpyAsync(&max_rec, sd.max_rec, 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-
+int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t) {
     if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-    const uint32_t grid = std::min<uint32_t>(2u * (uint32_t)e->n_cu, n_slabs);
-    const uint32_t cross_stride = 3u * ((max_rec + 63u) & ~63u), tab_stride = 4u * ((max_rec + 63u) & ~63u);      // D1's entries + what D1f adds (forwarded copies, split straddlers)      // records + slab extras + forwarded literal copies
-    const size_t tab_bytes = (size_t)grid * tab_stride * 16, cross_bytes = (size_t)grid * cross_stride * 16;
-    if (!e->d_bigtab.reserve(tab_bytes + cross_bytes + (size_t)grid * (tab_stride + 512u) * 4) || !e->d_out.reserve(total + 256)) return CJ_E_OOM;
-    BatchArgs a;
-    fill_args(a, slab_profile_flag(), n_slabs, d_in, sd.in_off, sd.in_len, (uint8_t*)e->d_out.p, sd.out_off, sd.out_cap, sd.result);
-    launch_lz4_decode_lds2_slabs(a, bp.sync, sd.meta, e->d_bigtab.p, (uint32_t*)(d_meta + r_misc) + 1, sd.first, iend,
-                                 (uint32_t*)(d_meta + r_done), (uint8_t*)e->d_bigtab.p + tab_bytes, tab_stride, cross_stride, grid, s, codec);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    std::vector<int64_t> res(n_slabs);
-    HIP_TRY(hipMemcpyAsync(res.data(), sd.result, (size_t)n_slabs * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(out, e->d_out.p, total, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    for (uint32_t i = 0; i < n_slabs; i++)
-        if (res[i] < 0) return corrupt;                     // the decoder's stall guard: cannot happen for a stream the parse accepted
-    return (int64_t)total;
+    t.grid = (uint32_t)std::min<size_t>(2u * (size_t)e->n_cu, n_slabs);
+    t.cross_stride = 3u * ((max_rec + 63u) & ~63u);       // D1's entries + what D1f adds (forwarded copies, split straddlers)
+    t.tab_stride = 4u * ((max_rec + 63u) & ~63u);         // records + slab extras + forwarded literal copies
+    const size_t tab_bytes = (size_t)t.grid * t.tab_stride * 16, cross_bytes = (size_t)t.grid * t.cross_stride * 16;
+    if (!e->d_bigtab.reserve(tab_bytes + cross_bytes + (size_t)t.grid * (t.tab_stride + 512u) * 4)) return CJ_E_OOM;
+    t.tabs = e->d_bigtab.p;
+    t.cross = (uint8_t*)e->d_bigtab.p + tab_bytes;
+    return 0;
 }
 
 // Several streams (LZ4 blocks without their size prefix / Snappy raw streams with starts[j] = the first element's position),
 // each a large stream of its own — the blocks of an LZ4 frame with large independent blocks (frame.hip), the large chunks of
-// a host batch (engine.hip).  The parse kernels run over the pieces of ALL blocks at once (launch_big_parse_many) and the decoder
-// over the slabs of all blocks (every block's first slab has no predecessor); the host waits twice in total.  result[j] = decoded size or
-// CJ_E_CORRUPT; returns 0, or a CJ_E_* that concerns the call as a whole (CJ_E_BAD_ARG: not for this path).
+// a host batch (engine.hip), one stream (large_decompress).  The parse kernels run over the pieces of ALL streams at once
+// (launch_big_parse_many) and the decoder over the slabs of all streams (every stream's first slab has no predecessor); the host
+// waits three times in total.  result[j] = decoded size or CJ_E_CORRUPT; returns 0, or a CJ_E_* that concerns the call as a whole
+// (CJ_E_BAD_ARG: not for this path).
 int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* const* ins, const size_t* lens, const size_t* starts, uint8_t* const* outs, const size_t* caps, int64_t* result) {
     const int64_t corrupt = codec == CJ_CODEC_SNAPPY_RAW ? CJ_E_SNAPPY_CORRUPT : CJ_E_CORRUPT;
     if (!e) e = default_engine();
     if (!e) return CJ_E_NO_DEVICE;
     if (nj == 0) return 0;
-    struct Job { size_t in_off, meta_off, out_off; BigSlabs sd; uint64_t n_seq, total; uint32_t n_sync, n_slabs; };
+    struct Job { size_t in_off, big_off, meta_off, out_off; uint64_t n_seq, total; uint32_t n_sync, n_slabs; };
     std::vector<Job> jobs(nj);
     std::vector<BigParse> bps(nj);
     std::vector<uint2> pmap;
     size_t in_total = 0, big_total = 0;
     uint32_t max_piece = kBigPieceTiny;
-    std::vector<size_t> big_off(nj);
     // the blocks of one frame lie in ONE host buffer, a few header bytes apart: one copy to the device instead of one per block
     const uint8_t* span_lo = ins[0]; const uint8_t* span_hi = ins[0] + lens[0];
     size_t sum_len = 0;
@@ -598,10 +514,8 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
         max_piece = std::max(max_piece, bp.piece);
         for (uint32_t p = 0; p < bp.np; p++) pmap.push_back(make_uint2((uint32_t)j, p));
         jobs[j].in_off = one_span ? (size_t)(ins[j] - span_lo) : in_total; in_total += (lens[j] + 64 + 255) & ~(size_t)255;
-        const size_t np = bp.np;
-        big_off[j] = big_total;
-        big_total += (((np * (bp.piece / 8)) + 255) & ~(size_t)255) + 6 * ((np * 256 + 255) & ~(size_t)255) + ((np * 8 + 255) & ~(size_t)255)
-                   + ((np * 512 + 255) & ~(size_t)255) + ((np * 16 + 255) & ~(size_t)255) + ((((size_t)bp.iend / 16 + 2) * 8 + 255) & ~(size_t)255);
+        jobs[j].big_off = big_total;
+        big_total += big_parse_layout(bp, 0);
     }
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
@@ -613,21 +527,18 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
     uint32_t* d_status = (uint32_t*)(b + o_status);                      // nj * 16 words, contiguous: one copy back
     HIP_TRY(hipMemsetAsync(d_status, 0, 64 * nj, s), CJ_E_NO_DEVICE);
     for (size_t j = 0; j < nj; j++) {
-        BigParse& bp = bps[j];
-        const size_t np = bp.np;
-        size_t off = big_off[j];
-        const auto region = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        bp.in = d_in + jobs[j].in_off;
-        bp.bits = (uint32_t*)(b + region(np * (bp.piece / 8))); bp.merge = (uint32_t*)(b + region(np * 256)); bp.exitp = (uint32_t*)(b + region(np * 256));
-        bp.next_tab = (uint32_t*)(b + region(np * 256)); bp.fe_tab = (uint32_t*)(b + region(np * 256)); bp.entry = (uint2*)(b + region(np * 8));
-        bp.lane_idx = (uint32_t*)(b + region(np * 256)); bp.lane_op = (uint64_t*)(b + region(np * 512)); bp.totals = (uint64_t*)(b + region(np * 16));
-        bp.sync = (uint2*)(b + region(((size_t)bp.iend / 16 + 2) * 8)); bp.status = d_status + 16 * j;
+        big_parse_layout(bps[j], (uintptr_t)(b + jobs[j].big_off));
+        bps[j].in = d_in + jobs[j].in_off;
+        bps[j].status = d_status + 16 * j;
         if (!one_span) HIP_TRY(hipMemcpyAsync(d_in + jobs[j].in_off, ins[j], lens[j], hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     }
     if (one_span) HIP_TRY(hipMemcpyAsync(d_in, span_lo, (size_t)(span_hi - span_lo), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(b + o_jobs, bps.data(), nj * sizeof(BigParse), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(b + o_pmap, pmap.data(), pmap.size() * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_big_parse_many((const BigParse*)(b + o_jobs), (uint32_t)nj, (const uint2*)(b + o_pmap), (uint32_t)pmap.size(), max_piece, codec, s);
+    if (nj == 1) launch_big_parse(bps[0], codec, s);                      // one stream: its descriptor by value, nothing to upload
+    else {
+        HIP_TRY(hipMemcpyAsync(b + o_jobs, bps.data(), nj * sizeof(BigParse), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+        HIP_TRY(hipMemcpyAsync(b + o_pmap, pmap.data(), pmap.size() * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+        launch_big_parse_many((const BigParse*)(b + o_jobs), (uint32_t)nj, (const uint2*)(b + o_pmap), (uint32_t)pmap.size(), max_piece, codec, s);
+    }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<uint32_t> st(16 * nj);
     HIP_TRY(hipMemcpyAsync(st.data(), d_status, 64 * nj, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
@@ -648,6 +559,11 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
         J.meta_off = n_slabs; n_slabs += J.n_slabs;                       // index of the block's first slab
         J.out_off = out_total; out_total += (J.total + 256 + 255) & ~(size_t)255;
     }
+    if (g_dbg_sync && jobs[0].n_slabs) {                                  // test hook (cj_debug_big_parse): hand job 0's sync points to the host
+        g_dbg_nseq = jobs[0].n_seq;
+        g_dbg_sync->resize((size_t)jobs[0].n_sync * 2);
+        HIP_TRY(hipMemcpy(g_dbg_sync->data(), bps[0].sync, (size_t)jobs[0].n_sync * 8, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
+    }
     // outputs that follow each other in the caller's buffer (the blocks of a frame, all full but the last): same layout on the
     // device, one copy back
     bool out_contig = true;
@@ -662,10 +578,15 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
     }
     if (n_slabs == 0) return 0;
     if (n_slabs > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    // slab rows: the batch rows | meta | first (uint2 each) | max_rec, counter | done flags
     const size_t r_misc = 7 * n_slabs, r_done = r_misc + 2, rows = r_done + (n_slabs + 1) / 2 + 1;
     if (!e->d_meta.reserve(rows * 8) || !e->d_out.reserve(out_total + 256)) return CJ_E_OOM;
     uint64_t* m = (uint64_t*)e->d_meta.p;
-    HIP_TRY(hipMemsetAsync(m + r_misc, 0, (rows - r_misc) * 8, s), CJ_E_NO_DEVICE);
+    const BatchRows d = batch_rows(m, n_slabs);
+    uint2* d_smeta = reinterpret_cast<uint2*>(d.end);
+    uint2* d_first = d_smeta + n_slabs;
+    uint32_t* d_misc = reinterpret_cast<uint32_t*>(m + r_misc);         // [0] max_rec, [1] the decoder's slab counter
+    HIP_TRY(hipMemsetAsync(d_misc, 0, (rows - r_misc) * 8, s), CJ_E_NO_DEVICE);
     const uint2* sync_base = reinterpret_cast<const uint2*>(b);
     std::vector<BigSlabs> sds(nj);
     std::vector<uint2> slab_job(n_slabs);
@@ -677,33 +598,33 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
         const size_t f = J.meta_off;
         sd.sync = bps[j].sync; sd.n_sync = J.n_sync; sd.n_seq = J.n_seq; sd.total = J.total; sd.iend = bps[j].iend; sd.in_base_off = J.in_off;
         sd.out_base_off = J.out_off; sd.sync_index_base = (uint32_t)(bps[j].sync - sync_base); sd.n_slabs = J.n_slabs;
-        sd.in_off = m + f; sd.in_len = m + n_slabs + f; sd.out_off = m + 2 * n_slabs + f; sd.out_cap = m + 3 * n_slabs + f;
-        sd.result = (int64_t*)(m + 4 * n_slabs + f); sd.meta = (uint2*)(m + 5 * n_slabs) + f; sd.first = (uint2*)(m + 6 * n_slabs) + f;
-        sd.max_rec = (uint32_t*)(m + r_misc);
+        sd.in_off = d.in_off + f; sd.in_len = d.in_len + f; sd.out_off = d.out_off + f; sd.out_cap = d.out_cap + f; sd.result = d.result + f;
+        sd.meta = d_smeta + f; sd.first = d_first + f; sd.max_rec = d_misc;
         for (uint32_t i = 0; i < J.n_slabs; i++) slab_job[f + i] = make_uint2((uint32_t)j, i);
     }
     // the descriptors and the slab -> block map travel in the parse scratch (the verdict words and the job structs are done with)
     const size_t o_sds = o_status, o_sj = (o_sds + nj * sizeof(BigSlabs) + 255) & ~(size_t)255;
-    HIP_TRY(hipMemcpyAsync(b + o_sds, sds.data(), nj * sizeof(BigSlabs), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(b + o_sj, slab_job.data(), n_slabs * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    launch_big_slabs_many((const BigSlabs*)(b + o_sds), (const uint2*)(b + o_sj), (uint32_t)n_slabs, s);
+    if (nj == 1) launch_big_slabs(sds[0], s);
+    else {
+        HIP_TRY(hipMemcpyAsync(b + o_sds, sds.data(), nj * sizeof(BigSlabs), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+        HIP_TRY(hipMemcpyAsync(b + o_sj, slab_job.data(), n_slabs * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+        launch_big_slabs_many((const BigSlabs*)(b + o_sds), (const uint2*)(b + o_sj), (uint32_t)n_slabs, s);
+    }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     uint32_t max_rec = 0;
-    HIP_TRY(hipMemcpyAsync(&max_rec, m + r_misc, 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(&max_rec, d_misc, 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
 
-    if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-    const uint32_t grid = (uint32_t)std::min<size_t>(2u * (size_t)e->n_cu, n_slabs);
-    const uint32_t cross_stride = 3u * ((max_rec + 63u) & ~63u), tab_stride = 4u * ((max_rec + 63u) & ~63u);
-    const size_t tab_bytes = (size_t)grid * tab_stride * 16, cross_bytes = (size_t)grid * cross_stride * 16;
-    if (!e->d_bigtab.reserve(tab_bytes + cross_bytes + (size_t)grid * (tab_stride + 512u) * 4)) return CJ_E_OOM;
+    SlabTabs tt;
+    const int rc = reserve_slab_tabs(e, n_slabs, max_rec, tt);
+    if (rc != 0) return rc;
     BatchArgs a;
-    fill_args(a, slab_profile_flag(), n_slabs, d_in, m, m + n_slabs, (uint8_t*)e->d_out.p, m + 2 * n_slabs, m + 3 * n_slabs, (int64_t*)(m + 4 * n_slabs));
-    launch_lz4_decode_lds2_slabs(a, sync_base, m + 5 * n_slabs, e->d_bigtab.p, (uint32_t*)(m + r_misc) + 1, m + 6 * n_slabs, 0u,
-                                 (uint32_t*)(m + r_done), (uint8_t*)e->d_bigtab.p + tab_bytes, tab_stride, cross_stride, grid, s, codec);
+    fill_args(a, slab_profile_flag(), d_in, (uint8_t*)e->d_out.p, d);
+    launch_lz4_decode_lds2_slabs(a, sync_base, d_smeta, tt.tabs, d_misc + 1, d_first, 0u, (uint32_t*)(m + r_done), tt.cross, tt.tab_stride,
+                                 tt.cross_stride, tt.grid, s, codec);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<int64_t> res(n_slabs);
-    HIP_TRY(hipMemcpyAsync(res.data(), m + 4 * n_slabs, n_slabs * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(res.data(), d.result, n_slabs * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     if (out_contig) {
         for (size_t j = 0; j < nj; j++)
             if (jobs[j].n_slabs) { HIP_TRY(hipMemcpyAsync(outs[j], e->d_out.p, out_total, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE); break; }

@@ -74,8 +74,8 @@ CJ_API int cj_device_count(void);
 
 /* =====================================================================================
  * Single-buffer entry points — exactly what a pyo3/Rust host would bind in place of the
- * libcramjam calls.  Host pointers.  Run on the default engine of device 0
- * (CJ_DEVICE env var overrides), created lazily.
+ * libcramjam calls.  Host pointers.  Run on the default engine of device 0 (of
+ * the devices HIP_VISIBLE_DEVICES shows), created lazily.
  * ===================================================================================== */
 
 /* Single-buffer entry points.  A buffer above 64 KiB (input, or announced output) is not run as one serial stream on one
