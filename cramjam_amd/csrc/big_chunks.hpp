@@ -60,7 +60,7 @@ void launch_big_parse(const BatchArgs& a, int codec, const uint32_t* list, uint3
 // in_off | in_len | out_off | out_cap | result (8 bytes x items each, in that order from `rows`), their ParseMeta, zeroed flags
 constexpr size_t kBigItemRows = 5;
 void launch_big_items(const BatchArgs& a, const uint32_t* list, uint32_t base, const void* bigmeta, const void* recs, uint32_t cap, uint64_t* rows, void* item_meta, uint32_t* done, hipStream_t s);
-void launch_lz4_decode_big_slabs(const BatchArgs& items, const void* meta, const void* recs, const void* bigmeta, uint32_t cap, void* tabs, uint32_t* counter,
-                                 uint32_t* done, void* cross, uint32_t tab_stride, uint32_t cross_stride, uint32_t grid, hipStream_t s, int codec);
+void launch_lz4_decode_big_slabs(const BatchArgs& items, const void* meta, const void* recs, const void* bigmeta, uint32_t cap, uint32_t* counter,
+                                 uint32_t* done, const SlabTabs& t, hipStream_t s, int codec);
 
 }  // namespace cj

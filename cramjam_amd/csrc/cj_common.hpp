@@ -77,9 +77,20 @@ int large_decompress_listed(::cj_engine* e, int codec, uint32_t flags, size_t n_
                             uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 int64_t large_decompress(int codec, uint32_t flags, const uint8_t* in, size_t n, uint8_t* out, size_t cap);
 bool large_few_elements(int codec, uint32_t flags, const uint8_t* in, size_t n, size_t cap);   // a small stream of a handful of long runs: the one-wavefront kernel is quicker
-void launch_lz4_decode_lds2_slabs(const BatchArgs& a, const void* sync, const void* meta, void* tabs, uint32_t* counter,
-                                  const void* first, uint32_t stream_len, uint32_t* done, void* cross, uint32_t tab_stride,
-                                  uint32_t cross_stride, uint32_t grid, hipStream_t s, int codec, bool rel = false);
+// The slab decoder's per-workgroup tables, one area after another from `tabs`: grid record tables of tab_stride 16-byte records, grid
+// cross lists of cross_stride 16-byte entries, grid deferred lists of defer_stride() words (for each of the eight waves its share of the
+// records + a batch of 64).  Every reservation and launch of the slab mode takes its sizes and pointers from here.
+struct SlabTabs {
+    uint32_t grid, tab_stride, cross_stride;
+    void* tabs = nullptr;
+    uint32_t defer_stride() const { return tab_stride + 8u * 64u; }
+    size_t cross_off() const { return (size_t)grid * tab_stride * 16; }
+    size_t defer_off() const { return cross_off() + (size_t)grid * cross_stride * 16; }
+    size_t bytes() const { return defer_off() + (size_t)grid * defer_stride() * 4; }
+};
+// one large stream / the blocks of a linked frame (large.hip, frame.hip): t.grid workgroups; done: one zeroed word per slab
+void launch_lz4_decode_lds2_slabs(const BatchArgs& a, const void* sync, const void* meta, uint32_t* counter, const void* first,
+                                  uint32_t stream_len, uint32_t* done, const SlabTabs& t, hipStream_t s, int codec, bool rel = false);
 void launch_snappy_decode_routed(const BatchArgs& a, const void* meta, hipStream_t s);       // wave kernel on chunks the parse kernel routed to it
 hipError_t launch_snappy_encode(const BatchArgs& a, hipStream_t s);
 

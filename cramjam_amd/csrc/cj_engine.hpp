@@ -111,4 +111,19 @@ int launch(cj_engine* e, cj_codec codec, cj_op op, const BatchArgs& a, hipStream
 void fill_args(BatchArgs& a, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off,
                const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
                int64_t* result);
+
+// The u64 rows of a batch of n chunks, one after another from a base pointer (a host copy such as e->h_meta, or the device one in e->d_meta)
+struct BatchRows {
+    uint64_t* in_off; uint64_t* in_len; uint64_t* out_off; uint64_t* out_cap; int64_t* result;
+    uint64_t* end;               // the first row after them
+    size_t n;
+    // chunks [a0, a0 + k) of the same rows (end stays the whole batch's)
+    BatchRows sub(size_t a0, size_t k) const { return {in_off + a0, in_len + a0, out_off + a0, out_cap + a0, result + a0, end, k}; }
+};
+inline BatchRows batch_rows(uint64_t* base, size_t n) {
+    return {base, base + n, base + 2 * n, base + 3 * n, reinterpret_cast<int64_t*>(base + 4 * n), base + 5 * n, n};
+}
+inline void fill_args(BatchArgs& a, uint32_t flags, const uint8_t* in_base, uint8_t* out_base, const BatchRows& r) {
+    fill_args(a, flags, r.n, in_base, r.in_off, r.in_len, out_base, r.out_off, r.out_cap, r.result);
+}
 }  // namespace cj

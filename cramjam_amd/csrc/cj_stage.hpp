@@ -1,5 +1,6 @@
-// cj_stage.hpp — the staging steps the framed (frame.hip) and large-buffer (large.hip) host paths share: named batch rows, the piece
-// compressor, the segment assembler and the slab decoder's tables.  The format rules stay with their callers.  Not part of the C-ABI.
+// cj_stage.hpp — the staging steps the framed (frame.hip) and large-buffer (large.hip) host paths share: the piece compressor, the
+// segment assembler and the reservation of the slab decoder's tables.  The batch rows (BatchRows) are the engine's, in cj_engine.hpp;
+// the slab tables' layout (SlabTabs) is the launchers', in cj_common.hpp.  The format rules stay with their callers.  Not part of the C-ABI.
 #pragma once
 #include "cj_engine.hpp"
 
@@ -10,19 +11,6 @@ namespace cj {
 void launch_crc32c_pieces(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint32_t* out, uint32_t n, hipStream_t s);
 void launch_copy_segments(const uint64_t* src, uint8_t* dst_base, const uint64_t* dst_off, const uint64_t* len,
                           const uint64_t* hdr, uint32_t hdr_len, uint32_t n, hipStream_t s);      // frame_kernels.hip
-
-// The u64 rows of a batch of n chunks, one after another from a base pointer (the host copy in e->h_meta or the device one in e->d_meta)
-struct BatchRows {
-    uint64_t* in_off; uint64_t* in_len; uint64_t* out_off; uint64_t* out_cap; int64_t* result;
-    uint64_t* end;               // the first row after them
-    size_t n;
-};
-inline BatchRows batch_rows(uint64_t* base, size_t n) {
-    return {base, base + n, base + 2 * n, base + 3 * n, reinterpret_cast<int64_t*>(base + 4 * n), base + 5 * n, n};
-}
-inline void fill_args(BatchArgs& a, uint32_t flags, const uint8_t* in_base, uint8_t* out_base, const BatchRows& r) {
-    fill_args(a, flags, r.n, in_base, r.in_off, r.in_len, out_base, r.out_off, r.out_cap, r.result);
-}
 
 // Compress in[0, n), cut into pieces of `piece` bytes, as ONE batch into e->d_out (`stride` bytes apart), the input staged at e->d_in + H
 // behind the last H bytes before it (hist: linked LZ4 blocks, kFlagLinkedEnc — piece 0 may refer to those H bytes, every other piece to
@@ -77,7 +65,6 @@ inline int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lea
 }
 
 // The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
-struct SlabTabs { uint32_t grid, tab_stride, cross_stride; void* tabs; void* cross; };
 int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);
 
 }  // namespace cj

@@ -52,7 +52,7 @@ int lds_scratch(cj_engine* e, const cj::BatchArgs& a, hipStream_t s, bool with_s
 //                      pass over the input (100 k chunks: 18 ms fused, 10.6 ms with the parse kernel)
 //   then               the wavefront-per-chunk kernel on what the parse left over (errors, chunks above 64 KiB, few long runs)
 //   flags              CJ_FLAG_FORCE_WAVE_PER_CHUNK / _LANE_PER_CHUNK: one mapping for every chunk (tests, comparisons)
-constexpr size_t kBigCap = 8192;
+constexpr size_t kBigCap = 8192;          // big chunks (CJ_FLAG_BIG_CHUNKS) decoded per group: each holds a record area of 1 MiB while its group is in flight
 constexpr int kBigObs = 8;                // counts of big chunks the engine remembers (cj_engine::big_obs)
 
 // CJ_FLAG_BIG_CHUNKS: which chunks lie in (64 KiB, 256 KiB] is known on the device only (big_list_kernel), but the record areas
@@ -66,9 +66,12 @@ int plan_big(cj_engine* e, cj_codec codec, const cj::BatchArgs& a, hipStream_t s
     const size_t big_list_bytes = ((4 + (size_t)a.n_chunks) * 4 + 255) & ~(size_t)255;
     if (!e->d_biglist.reserve(big_list_bytes)) { (void)hipGetLastError(); return 0; }      // no room for the list: the chunks stay with the wavefront kernel
     uint32_t* big_list = (uint32_t*)e->d_biglist.p;
-    if (!e->h_count) {
-        HIP_TRY(hipHostMalloc((void**)&e->h_count, 64, hipHostMallocDefault), CJ_E_OOM);
-        for (int i = 0; i < kBigObs; i++) HIP_TRY(hipEventCreateWithFlags(&e->big_ev[i], hipEventDisableTiming), CJ_E_NO_DEVICE);
+    if (!e->h_count) {                                        // (h_count is set last: after a failure here the next call starts over)
+        uint32_t* h = nullptr;
+        HIP_TRY(hipHostMalloc((void**)&h, 64, hipHostMallocDefault), CJ_E_OOM);
+        for (hipEvent_t& ev : e->big_ev)
+            if (!ev && !hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreateWithFlags")) { (void)hipHostFree(h); return CJ_E_NO_DEVICE; }
+        e->h_count = h;
     }
     cj::launch_big_list(a, codec, big_list, s);
     // counts that have arrived since the last call
@@ -93,7 +96,24 @@ int plan_big(cj_engine* e, cj_codec codec, const cj::BatchArgs& a, hipStream_t s
     *n_plan = (uint32_t)std::min<size_t>(plan, a.n_chunks);
     *list_out = big_list;
     return 0;
-}          // big chunks (CJ_FLAG_BIG_CHUNKS) decoded per group: each holds a record area of 1 MiB while its group is in flight
+}
+
+// d_bigmisc for a group of cap listed chunks and their kBigSlabs * cap slab work items: BigMeta x cap (256-byte aligned) | the items'
+// batch rows | their ParseMeta | their done flags | the slab counter | the walk scratch.  base 0: offsets only; returns the size.
+struct BigGroup { void* meta; cj::BatchRows rows; void* imeta; uint32_t* done; uint32_t* ctr; void* walk; };
+size_t big_group_layout(BigGroup& g, uintptr_t base, uint32_t cap) {
+    static_assert(cj::kBigItemRows == 5, "the items' descriptor rows are a BatchRows");
+    const size_t items = (size_t)cj::kBigSlabs * cap;
+    size_t off = 0;
+    const auto region = [&](size_t bytes) { const uintptr_t p = base + off; off += bytes; return p; };
+    g.meta = (void*)region((cj::big_meta_bytes(cap) + 255) & ~(size_t)255);
+    g.rows = cj::batch_rows((uint64_t*)region(cj::kBigItemRows * 8 * items), items);
+    g.imeta = (void*)region(8 * items);
+    g.done = (uint32_t*)region(4 * items);
+    g.ctr = (uint32_t*)region(256);
+    g.walk = (void*)region(cj::big_walk_scratch_bytes(cap));
+    return off;
+}
 
 int launch_decode(cj_engine* e, cj_codec codec, const cj::BatchArgs& a_in, hipStream_t s) {
     const bool lz4 = codec == CJ_CODEC_LZ4_BLOCK;
@@ -142,30 +162,23 @@ int launch_decode(cj_engine* e, cj_codec codec, const cj::BatchArgs& a_in, hipSt
         // (1 MiB each); what that stage does not take stays flagged for the wavefront kernel
         const uint32_t cap = (uint32_t)std::min<size_t>(n_big, kBigCap);
         const uint32_t items = cj::kBigSlabs * cap;
-        // (per workgroup: a slab's records + at most one extra record each — the literals of a match that is cut at the slab's start — and at most one
-        //  cross copy each; no forwarding in this mode: nothing stages the input)
-        const uint32_t tab_stride = 2u * (cj::kBigSlabRecs + 64u), cross_stride = cj::kBigSlabRecs + 64u;
-        // d_bigmisc: BigMeta x cap | item rows (5 x 8 bytes x items) | item meta | done flags | counter | walk scratch
-        const size_t o_meta = 0, o_rows = (o_meta + cj::big_meta_bytes(cap) + 255) & ~(size_t)255,
-                     o_imeta = o_rows + cj::kBigItemRows * 8 * (size_t)items, o_done = o_imeta + 8 * (size_t)items, o_ctr = o_done + 4 * (size_t)items,
-                     o_walk = o_ctr + 256, total = o_walk + cj::big_walk_scratch_bytes(cap);
+        // the slab decoder's persistent workgroups and their tables, 0.9 MiB each (per workgroup: a slab's records + at most one extra record each
+        // — the literals of a match that is cut at the slab's start — and at most one cross copy each; no forwarding in this mode: nothing stages the input)
+        cj::SlabTabs tt = {std::min(cj::kBigSlabWgsPerCu * (uint32_t)e->n_cu, items), 2u * (cj::kBigSlabRecs + 64u), cj::kBigSlabRecs + 64u};
+        BigGroup g;
+        const size_t misc_bytes = big_group_layout(g, 0, cap);
         // no room for the record areas: the chunks stay with the wavefront kernel (slower, never wrong)
-        const uint32_t sgrid = std::min(cj::kBigSlabWgsPerCu * (uint32_t)e->n_cu, items);          // the slab decoder's persistent workgroups (their tables are 0.9 MiB each)
-        const bool room = e->d_bigrecs.reserve_exact(cj::big_recs_bytes(cap)) && e->d_bigmisc.reserve(total)
-            && e->d_bigslabtab.reserve((size_t)sgrid * tab_stride * 16 + (size_t)sgrid * cross_stride * 16 + (size_t)sgrid * (tab_stride + 512u) * 4);
+        const bool room = e->d_bigrecs.reserve_exact(cj::big_recs_bytes(cap)) && e->d_bigmisc.reserve(misc_bytes) && e->d_bigslabtab.reserve(tt.bytes());
         if (!room) (void)hipGetLastError();
-        uint8_t* m = (uint8_t*)e->d_bigmisc.p;
+        big_group_layout(g, (uintptr_t)e->d_bigmisc.p, cap);
+        tt.tabs = e->d_bigslabtab.p;
         for (uint32_t base = 0; room && base < n_big; base += cap) {
-            HIP_TRY(hipMemsetAsync(m + o_ctr, 0, 256, s), CJ_E_NO_DEVICE);
-            cj::launch_big_parse(a, codec, big_list, base, cap, e->d_bigrecs.p, m + o_meta, e->d_pmeta.p, m + o_walk, s);
-            uint64_t* rows = (uint64_t*)(m + o_rows);
-            cj::launch_big_items(a, big_list, base, m + o_meta, e->d_bigrecs.p, cap, rows, m + o_imeta, (uint32_t*)(m + o_done), s);
-            cj::BatchArgs it = a;
-            it.in_off = rows; it.in_len = rows + items; it.out_off = rows + 2 * (size_t)items; it.out_cap = rows + 3 * (size_t)items;
-            it.result = (int64_t*)(rows + 4 * (size_t)items); it.n_chunks = items; it.flags = a.flags & CJ_FLAG_DEBUG_PROFILE;
-            uint8_t* t = (uint8_t*)e->d_bigslabtab.p;
-            cj::launch_lz4_decode_big_slabs(it, m + o_imeta, e->d_bigrecs.p, m + o_meta, cap, t, (uint32_t*)(m + o_ctr), (uint32_t*)(m + o_done),
-                                            t + (size_t)sgrid * tab_stride * 16, tab_stride, cross_stride, sgrid, s, codec);
+            HIP_TRY(hipMemsetAsync(g.ctr, 0, 256, s), CJ_E_NO_DEVICE);
+            cj::launch_big_parse(a, codec, big_list, base, cap, e->d_bigrecs.p, g.meta, e->d_pmeta.p, g.walk, s);
+            cj::launch_big_items(a, big_list, base, g.meta, e->d_bigrecs.p, cap, g.rows.in_off, g.imeta, g.done, s);
+            cj::BatchArgs it;
+            cj::fill_args(it, a.flags & CJ_FLAG_DEBUG_PROFILE, a.in_base, a.out_base, g.rows);
+            cj::launch_lz4_decode_big_slabs(it, g.imeta, e->d_bigrecs.p, g.meta, cap, g.ctr, g.done, tt, s, codec);
         }
     }
     if (lz4) cj::launch_lz4_decode_routed(a, e->d_pmeta.p, s);                // few long runs / oversize chunks / errors
@@ -253,13 +266,55 @@ int64_t single(cj_codec codec, cj_op op, uint32_t flags, const uint8_t* in, size
     return rc != 0 ? (int64_t)rc : res;
 }
 
+// The rows of a host batch in e->h_meta: inputs and outputs one after another, 16 bytes aligned, their sizes added to in_total / out_total.
+// LZ4 compress: the kernel gets a full LZ4_compressBound of room on the device; the caller's capacity applies when copying back (within_cap).
+cj::BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const size_t* in_lens, const size_t* out_caps,
+                      uint64_t& in_total, uint64_t& out_total) {
+    e->h_meta.assign(5 * n, 0);
+    const cj::BatchRows h = cj::batch_rows(e->h_meta.data(), n);
+    for (size_t i = 0; i < n; i++) {
+        h.in_off[i] = in_total;
+        h.in_len[i] = in_lens[i];
+        in_total += (in_lens[i] + 15u) & ~(uint64_t)15u;
+        uint64_t dcap = out_caps[i];
+        if (codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS)
+            dcap = std::max<uint64_t>(dcap, cj_lz4_block_compress_bound(in_lens[i], (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0));
+        h.out_off[i] = out_total;
+        h.out_cap[i] = dcap;
+        out_total += (dcap + 15u) & ~(uint64_t)15u;
+    }
+    return h;
+}
+
+// a result that does not fit the caller's capacity (LZ4 compress, which had a full bound on the device) is "Compression failed"
+int64_t within_cap(int64_t r, size_t cap) { return r > 0 && (uint64_t)r > cap ? (int64_t)CJ_E_COMPRESS_FAILED : r; }
+
+// the inputs of chunks [a0, b0) (`bytes` of staging) into their places in h_in
+void pack(cj_engine* e, const cj::BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const uint8_t* const* in_ptrs, const size_t* in_lens) {
+    parallel_chunks(b0 - a0, bytes, [&](size_t a, size_t b) {
+        for (size_t i = a0 + a; i < a0 + b; i++)
+            if (in_lens[i]) std::memcpy(e->h_in.p + h.in_off[i], in_ptrs[i], in_lens[i]);
+    });
+}
+
+// the results res of chunks [a0, b0) into result, their outputs from h_out (`bytes` of staging) to the caller
+void scatter(cj_engine* e, const cj::BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const int64_t* res, uint8_t* const* out_ptrs,
+             const size_t* out_caps, int64_t* result) {
+    parallel_chunks(b0 - a0, bytes, [&](size_t a, size_t b) {
+        for (size_t i = a0 + a; i < a0 + b; i++) {
+            result[i] = within_cap(res[i], out_caps[i]);
+            if (result[i] > 0) std::memcpy(out_ptrs[i], e->h_out.p + h.out_off[i], (size_t)result[i]);
+        }
+    });
+}
+
 // A LARGE host batch, in slices: while slice k is uploaded and decoded on the engine's stream and slice k - 1 travels back
 // on a second one, the host packs slice k + 1 into the pinned staging and scatters the slices that have arrived — the one-shot
 // path below does these five things one after the other (pack, H2D, kernels, D2H, scatter: 18.8 GB/s of output for 16 384 x 64 KiB).
-// m = the engine's meta rows (in_off | in_len | out_off | out_cap | result), already laid out by the caller; e->mu is held.
-int batch_host_sliced(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
+// h = the batch's rows, laid out by the caller; e->mu is held.
+int batch_host_sliced(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, const cj::BatchRows& h, const uint8_t* const* in_ptrs, const size_t* in_lens,
                       uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, uint64_t in_total, uint64_t out_total) {
-    const std::vector<uint64_t>& m = e->h_meta;
+    const size_t n = h.n;
     if (!e->h_in.reserve(in_total) || !e->h_out.reserve(out_total) || !e->h_res.reserve(n * 8)) return CJ_E_OOM;
     if (!e->stream_back) HIP_TRY(hipStreamCreateWithFlags(&e->stream_back, hipStreamNonBlocking), CJ_E_NO_DEVICE);
     size_t K = (size_t)((in_total + out_total) >> 26);               // ~64 MiB of traffic per slice
@@ -271,56 +326,43 @@ int batch_host_sliced(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, si
     }
     uint8_t* d_in = (uint8_t*)e->d_in.p;
     uint8_t* d_out = (uint8_t*)e->d_out.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
+    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
     int64_t* h_res = (int64_t*)e->h_res.p;
-    HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);     // (the rows up to result)
     std::vector<size_t> c(K + 1, n);                                 // slice k = chunks [c[k], c[k + 1]): equal shares of the output space (compress: of the bounds)
     c[0] = 0;
     for (size_t k = 1; k < K; k++) {
         const uint64_t want = out_total / K * k;
         size_t lo = c[k - 1], hi = n;
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (m[2 * n + mid] < want) lo = mid + 1; else hi = mid; }
+        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (h.out_off[mid] < want) lo = mid + 1; else hi = mid; }
         c[k] = lo;
     }
-    const auto in_at = [&](size_t i) { return i < n ? m[i] : in_total; };
-    const auto out_at = [&](size_t i) { return i < n ? m[2 * n + i] : out_total; };
-    const auto scatter = [&](size_t k) {
-        const size_t a0 = c[k], b0 = c[k + 1];
-        parallel_chunks(b0 - a0, out_at(b0) - out_at(a0), [&](size_t a, size_t b) {
-            for (size_t i = a0 + a; i < a0 + b; i++) {
-                result[i] = h_res[i];
-                if (result[i] <= 0) continue;
-                if ((uint64_t)result[i] > out_caps[i]) { result[i] = CJ_E_COMPRESS_FAILED; continue; }
-                std::memcpy(out_ptrs[i], e->h_out.p + m[2 * n + i], (size_t)result[i]);
-            }
-        });
-    };
+    const auto in_at = [&](size_t i) { return i < n ? h.in_off[i] : in_total; };
+    const auto out_at = [&](size_t i) { return i < n ? h.out_off[i] : out_total; };
+    const auto scatter_slice = [&](size_t k) { scatter(e, h, c[k], c[k + 1], out_at(c[k + 1]) - out_at(c[k]), h_res, out_ptrs, out_caps, result); };
     const auto bail = [&](int rc) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream_back); return rc; };
     size_t scattered = 0;
     for (size_t k = 0; k < K; k++) {
         const size_t a0 = c[k], b0 = c[k + 1];
         if (b0 > a0) {
-            parallel_chunks(b0 - a0, in_at(b0) - in_at(a0), [&](size_t a, size_t b) {
-                for (size_t i = a0 + a; i < a0 + b; i++)
-                    if (in_lens[i]) std::memcpy(e->h_in.p + m[i], in_ptrs[i], in_lens[i]);
-            });
+            pack(e, h, a0, b0, in_at(b0) - in_at(a0), in_ptrs, in_lens);
             if (in_at(b0) > in_at(a0) && !hip_ok(hipMemcpyAsync(d_in + in_at(a0), e->h_in.p + in_at(a0), in_at(b0) - in_at(a0), hipMemcpyHostToDevice, e->stream), "hipMemcpyAsync")) return bail(CJ_E_NO_DEVICE);
             cj::BatchArgs a;
-            fill_args(a, flags, b0 - a0, d_in, d_meta + a0, d_meta + n + a0, d_out, d_meta + 2 * n + a0, d_meta + 3 * n + a0, (int64_t*)(d_meta + 4 * n + a0));
+            fill_args(a, flags, d_in, d_out, d.sub(a0, b0 - a0));
             const int rc = cj::launch(e, codec, op, a, e->stream);
             if (rc != 0) return bail(rc);
         }
         if (!hip_ok(hipEventRecord(e->slice_ev[2 * k], e->stream), "hipEventRecord") || !hip_ok(hipStreamWaitEvent(e->stream_back, e->slice_ev[2 * k], 0), "hipStreamWaitEvent")) return bail(CJ_E_NO_DEVICE);
         if (b0 > a0) {
-            if (!hip_ok(hipMemcpyAsync(h_res + a0, d_meta + 4 * n + a0, (b0 - a0) * 8, hipMemcpyDeviceToHost, e->stream_back), "hipMemcpyAsync")) return bail(CJ_E_NO_DEVICE);
+            if (!hip_ok(hipMemcpyAsync(h_res + a0, d.result + a0, (b0 - a0) * 8, hipMemcpyDeviceToHost, e->stream_back), "hipMemcpyAsync")) return bail(CJ_E_NO_DEVICE);
             if (out_at(b0) > out_at(a0) && !hip_ok(hipMemcpyAsync(e->h_out.p + out_at(a0), d_out + out_at(a0), out_at(b0) - out_at(a0), hipMemcpyDeviceToHost, e->stream_back), "hipMemcpyAsync")) return bail(CJ_E_NO_DEVICE);
         }
         if (!hip_ok(hipEventRecord(e->slice_ev[2 * k + 1], e->stream_back), "hipEventRecord")) return bail(CJ_E_NO_DEVICE);
-        while (scattered < k && hipEventQuery(e->slice_ev[2 * scattered + 1]) == hipSuccess) scatter(scattered++);
+        while (scattered < k && hipEventQuery(e->slice_ev[2 * scattered + 1]) == hipSuccess) scatter_slice(scattered++);
     }
     for (; scattered < K; scattered++) {
         if (!hip_ok(hipEventSynchronize(e->slice_ev[2 * scattered + 1]), "hipEventSynchronize")) return bail(CJ_E_NO_DEVICE);
-        scatter(scattered);
+        scatter_slice(scattered);
     }
     HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
     return 0;
@@ -424,7 +466,7 @@ int cj_engine_create(int device, cj_engine** out) {
 void cj_engine_destroy(cj_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    e->d_in.release(); e->d_out.release(); e->d_meta.release(); e->d_sync.release(); e->d_bigrecs.release(); e->d_bigmisc.release(); e->d_biglist.release(); if (e->h_count) { (void)hipHostFree(e->h_count); for (auto& ev : e->big_ev) if (ev) (void)hipEventDestroy(ev); } e->d_bigslabtab.release(); e->d_pmeta.release(); e->d_lanelist.release(); e->d_frame.release(); e->d_tab.release(); e->d_big.release(); e->d_bigtab.release();
+    e->d_in.release(); e->d_out.release(); e->d_meta.release(); e->d_sync.release(); e->d_bigrecs.release(); e->d_bigmisc.release(); e->d_biglist.release(); if (e->h_count) (void)hipHostFree(e->h_count); for (auto& ev : e->big_ev) if (ev) (void)hipEventDestroy(ev); e->d_bigslabtab.release(); e->d_pmeta.release(); e->d_lanelist.release(); e->d_frame.release(); e->d_tab.release(); e->d_big.release(); e->d_bigtab.release();
     e->h_in.release(); e->h_out.release(); e->h_res.release();
     for (hipEvent_t ev : e->slice_ev) (void)hipEventDestroy(ev);
     if (e->stream_back) (void)hipStreamDestroy(e->stream_back);
@@ -535,73 +577,45 @@ int cj_batch_host(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t
     std::lock_guard<std::mutex> lock(e->mu);
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
 
-    // meta layout (u64 each, n entries per row): in_off | in_len | out_off | out_cap | result
-    std::vector<uint64_t>& m = e->h_meta;
-    m.assign(5 * n, 0);
     uint64_t in_total = 0, out_total = 0;
-    for (size_t i = 0; i < n; i++) {
-        m[i] = in_total;
-        m[n + i] = in_lens[i];
-        in_total += (in_lens[i] + 15u) & ~(uint64_t)15u;
-        // LZ4 compress: the kernel wants a full LZ4_compressBound of room; give it that on the device and
-        // apply the caller's capacity when copying back (fits -> ok, else "Compression failed").
-        uint64_t dcap = out_caps[i];
-        if (codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS) {
-            uint64_t b = cj_lz4_block_compress_bound(in_lens[i], (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0);
-            if (b > dcap) dcap = b;
-        }
-        m[2 * n + i] = out_total;
-        m[3 * n + i] = dcap;
-        out_total += (dcap + 15u) & ~(uint64_t)15u;
-    }
+    const cj::BatchRows h = lay_out(e, codec, op, flags, n, in_lens, out_caps, in_total, out_total);
     if (!e->d_in.reserve(in_total + 16) || !e->d_out.reserve(out_total + 16) || !e->d_meta.reserve(5 * n * 8)) return CJ_E_OOM;
 
     // (a large batch: sliced, so that packing, the two directions of the link, the kernels and the scattering overlap)
     if (n >= 512 && in_total + out_total >= (128ull << 20))
-        return batch_host_sliced(e, codec, op, flags, n, in_ptrs, in_lens, out_ptrs, out_caps, result, in_total, out_total);
+        return batch_host_sliced(e, codec, op, flags, h, in_ptrs, in_lens, out_ptrs, out_caps, result, in_total, out_total);
 
     uint8_t* d_in = (uint8_t*)e->d_in.p;
     uint8_t* d_out = (uint8_t*)e->d_out.p;
-    uint64_t* d_meta = (uint64_t*)e->d_meta.p;
+    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
     if (n == 1) {
         if (in_lens[0]) HIP_TRY(hipMemcpyAsync(d_in, in_ptrs[0], in_lens[0], hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     } else {
         if (!e->h_in.reserve(in_total)) return CJ_E_OOM;
-        parallel_chunks(n, in_total, [&](size_t a, size_t b) {
-            for (size_t i = a; i < b; i++)
-                if (in_lens[i]) std::memcpy(e->h_in.p + m[i], in_ptrs[i], in_lens[i]);
-        });
+        pack(e, h, 0, n, in_total, in_ptrs, in_lens);
         if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     }
-    HIP_TRY(hipMemcpyAsync(d_meta, m.data(), 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);     // (the rows up to result)
 
     cj::BatchArgs a;
-    fill_args(a, flags, n, d_in, d_meta, d_meta + n, d_out, d_meta + 2 * n, d_meta + 3 * n, (int64_t*)(d_meta + 4 * n));
+    fill_args(a, flags, d_in, d_out, d);
     int rc = launch(e, codec, op, a, e->stream);
     if (rc != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, d_meta + 4 * n, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
 
     if (n == 1) {
-        if (result[0] > 0) {
-            if ((uint64_t)result[0] > out_caps[0]) result[0] = CJ_E_COMPRESS_FAILED;
-            else HIP_TRY(hipMemcpy(out_ptrs[0], d_out, (size_t)result[0], hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-        }
+        result[0] = within_cap(result[0], out_caps[0]);
+        if (result[0] > 0) HIP_TRY(hipMemcpy(out_ptrs[0], d_out, (size_t)result[0], hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
         return 0;
     }
     // copy back only the span that was produced
     uint64_t span = 0;
     for (size_t i = 0; i < n; i++)
-        if (result[i] > 0 && m[2 * n + i] + (uint64_t)result[i] > span) span = m[2 * n + i] + (uint64_t)result[i];
+        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
     if (!e->h_out.reserve(span)) return CJ_E_OOM;
     if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-    parallel_chunks(n, span, [&](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) {
-            if (result[i] <= 0) continue;
-            if ((uint64_t)result[i] > out_caps[i]) { result[i] = CJ_E_COMPRESS_FAILED; continue; }
-            std::memcpy(out_ptrs[i], e->h_out.p + m[2 * n + i], (size_t)result[i]);
-        }
-    });
+    scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
     return 0;
 }
 

@@ -379,8 +379,8 @@ int lz4_frame_linked_lds(cj_engine* e, const Lz4Frame& f, const uint8_t* d_in, s
         cj::SlabTabs tt;
         const int rc = cj::reserve_slab_tabs(e, nb, cj::kSyncStride * cj::kSyncEvery, tt);
         if (rc != 0) return rc;
-        cj::launch_lz4_decode_lds2_slabs(a, e->d_sync.p, e->d_pmeta.p, tt.tabs, (uint32_t*)(d_meta + r_cnt), d_meta + r_first, 0u,
-                                         (uint32_t*)(d_meta + r_done), tt.cross, tt.tab_stride, tt.cross_stride, tt.grid, s, CJ_CODEC_LZ4_BLOCK, true);
+        cj::launch_lz4_decode_lds2_slabs(a, e->d_sync.p, e->d_pmeta.p, (uint32_t*)(d_meta + r_cnt), d_meta + r_first, 0u,
+                                         (uint32_t*)(d_meta + r_done), tt, s, CJ_CODEC_LZ4_BLOCK, true);
     }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(res.data(), d.result, nb * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);     // the decoder's stall guard reports here

@@ -473,10 +473,8 @@ int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& 
     t.grid = (uint32_t)std::min<size_t>(2u * (size_t)e->n_cu, n_slabs);
     t.cross_stride = 3u * ((max_rec + 63u) & ~63u);       // D1's entries + what D1f adds (forwarded copies, split straddlers)
     t.tab_stride = 4u * ((max_rec + 63u) & ~63u);         // records + slab extras + forwarded literal copies
-    const size_t tab_bytes = (size_t)t.grid * t.tab_stride * 16, cross_bytes = (size_t)t.grid * t.cross_stride * 16;
-    if (!e->d_bigtab.reserve(tab_bytes + cross_bytes + (size_t)t.grid * (t.tab_stride + 512u) * 4)) return CJ_E_OOM;
+    if (!e->d_bigtab.reserve(t.bytes())) return CJ_E_OOM;
     t.tabs = e->d_bigtab.p;
-    t.cross = (uint8_t*)e->d_bigtab.p + tab_bytes;
     return 0;
 }
 
@@ -620,8 +618,7 @@ int large_decompress_many(cj_engine* e, int codec, size_t nj, const uint8_t* con
     if (rc != 0) return rc;
     BatchArgs a;
     fill_args(a, slab_profile_flag(), d_in, (uint8_t*)e->d_out.p, d);
-    launch_lz4_decode_lds2_slabs(a, sync_base, d_smeta, tt.tabs, d_misc + 1, d_first, 0u, (uint32_t*)(m + r_done), tt.cross, tt.tab_stride,
-                                 tt.cross_stride, tt.grid, s, codec);
+    launch_lz4_decode_lds2_slabs(a, sync_base, d_smeta, d_misc + 1, d_first, 0u, (uint32_t*)(m + r_done), tt, s, codec);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     std::vector<int64_t> res(n_slabs);
     HIP_TRY(hipMemcpyAsync(res.data(), d.result, n_slabs * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);

@@ -1424,23 +1424,23 @@ void launch_lz4_decode_fused(const BatchArgs& a, void* meta, void* tabs, uint32_
     else { if (sn) launch_fused_window<CJ_CODEC_SNAPPY_RAW, 16384u, 128u>(a, meta, tabs, counter, grid, s); else launch_fused_window<CJ_CODEC_LZ4_BLOCK, 16384u, 128u>(a, meta, tabs, counter, grid, s); }
 }
 
+// the slab mode's arguments on the tables t (cj_common.hpp)
+static SlabArgs slab_args(const SlabTabs& t, uint32_t* done, uint32_t rel, uint32_t prev) {
+    uint8_t* b = (uint8_t*)t.tabs;
+    return {done, (uint4*)(b + t.cross_off()), t.tab_stride, t.cross_stride, rel, (uint32_t*)(b + t.defer_off()), t.defer_stride(), prev};
+}
+
 // items: the slab work items' descriptors (a.n_chunks = kBigSlabs * cap of them), meta: their ParseMeta (nseq = records of the slab, 0 = nothing to do)
-void launch_lz4_decode_big_slabs(const BatchArgs& items, const void* meta, const void* recs, const void* bigmeta, uint32_t cap, void* tabs, uint32_t* counter,
-                                 uint32_t* done, void* cross, uint32_t tab_stride, uint32_t cross_stride, uint32_t grid, hipStream_t s, int codec) {
+void launch_lz4_decode_big_slabs(const BatchArgs& items, const void* meta, const void* recs, const void* bigmeta, uint32_t cap, uint32_t* counter,
+                                 uint32_t* done, const SlabTabs& t, hipStream_t s, int codec) {
     if (items.n_chunks == 0) return;
-    const uint32_t defer_stride = tab_stride + 8u * 64u;
-    const SlabArgs sl = {done, (uint4*)cross, tab_stride, cross_stride, 0u,
-                         reinterpret_cast<uint32_t*>((uint4*)cross + (size_t)grid * cross_stride), defer_stride, cap};
+    const SlabArgs sl = slab_args(t, done, 0u, cap);
     const FeedArgs fd = {(const uint4*)recs, (const BigMeta*)bigmeta, cap};
     constexpr uint32_t bytes = lds2_bytes(kBigSlabBytes) + 3u * kBigLanes * 4u;          // + the regions' table (kRecFeed)
     static_assert(kBigSlabWgsPerCu * bytes <= 163840u, "workgroups per CU");
-    if (codec == CJ_CODEC_SNAPPY_RAW) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz4_decode_bigslabs_kernel<CJ_CODEC_SNAPPY_RAW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        hipLaunchKernelGGL((lz4_decode_bigslabs_kernel<CJ_CODEC_SNAPPY_RAW>), dim3(grid), dim3(kBigSlabThreads), bytes, s, items, (const ParseMeta*)meta, (uint4*)tabs, counter, sl, fd);
-        return;
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz4_decode_bigslabs_kernel<CJ_CODEC_LZ4_BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    hipLaunchKernelGGL((lz4_decode_bigslabs_kernel<CJ_CODEC_LZ4_BLOCK>), dim3(grid), dim3(kBigSlabThreads), bytes, s, items, (const ParseMeta*)meta, (uint4*)tabs, counter, sl, fd);
+    const auto k = codec == CJ_CODEC_SNAPPY_RAW ? lz4_decode_bigslabs_kernel<CJ_CODEC_SNAPPY_RAW> : lz4_decode_bigslabs_kernel<CJ_CODEC_LZ4_BLOCK>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    hipLaunchKernelGGL(k, dim3(t.grid), dim3(kBigSlabThreads), bytes, s, items, (const ParseMeta*)meta, (uint4*)t.tabs, counter, sl, fd);
 }
 
 size_t lz4_lds2_tab_bytes(uint32_t grid, uint32_t win) { return (size_t)grid * lds2_tab_records(win) * sizeof(uint4); }
@@ -1478,27 +1478,15 @@ void launch_lz4_decode_lds2_linked(const BatchArgs& a, const void* sync, const v
                        (const uint2*)sync, (const ParseMeta*)meta, (uint4*)tabs, counter, (const uint2*)frames, n_frames);
 }
 
-// large.hip: the slabs of one large stream.  tabs: grid * tab_stride records; cross: grid * cross_stride entries; done: one
-// zeroed word per slab
-void launch_lz4_decode_lds2_slabs(const BatchArgs& a, const void* sync, const void* meta, void* tabs, uint32_t* counter,
-                                  const void* first, uint32_t stream_len, uint32_t* done, void* cross, uint32_t tab_stride,
-                                  uint32_t cross_stride, uint32_t grid, hipStream_t s, int codec, bool rel) {
+// large.hip / frame.hip: the slabs of large streams, the blocks of a linked frame (rel)
+void launch_lz4_decode_lds2_slabs(const BatchArgs& a, const void* sync, const void* meta, uint32_t* counter, const void* first,
+                                  uint32_t stream_len, uint32_t* done, const SlabTabs& t, hipStream_t s, int codec, bool rel) {
     if (a.n_chunks == 0) return;
-    // the deferred lists (one per wave: at most its share of the records + a batch) follow the cross lists
-    const uint32_t defer_stride = tab_stride + 8u * 64u;
-    const SlabArgs sl = {done, (uint4*)cross, tab_stride, cross_stride, rel ? 1u : 0u,
-                         reinterpret_cast<uint32_t*>((uint4*)cross + (size_t)grid * cross_stride), defer_stride};
-    if (codec == CJ_CODEC_SNAPPY_RAW) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz4_decode_slabs_kernel<CJ_CODEC_SNAPPY_RAW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kL2Bytes);
-        hipLaunchKernelGGL((lz4_decode_slabs_kernel<CJ_CODEC_SNAPPY_RAW>), dim3(grid), dim3(kL2Threads), kL2Bytes, s, a,
-                           (const uint2*)sync, (const ParseMeta*)meta, (uint4*)tabs, counter, (const uint2*)first, stream_len, sl);
-        return;
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz4_decode_slabs_kernel<CJ_CODEC_LZ4_BLOCK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kL2Bytes);
-    hipLaunchKernelGGL((lz4_decode_slabs_kernel<CJ_CODEC_LZ4_BLOCK>), dim3(grid), dim3(kL2Threads), kL2Bytes, s, a,
-                       (const uint2*)sync, (const ParseMeta*)meta, (uint4*)tabs, counter, (const uint2*)first, stream_len, sl);
+    const SlabArgs sl = slab_args(t, done, rel ? 1u : 0u, 1u);
+    const auto k = codec == CJ_CODEC_SNAPPY_RAW ? lz4_decode_slabs_kernel<CJ_CODEC_SNAPPY_RAW> : lz4_decode_slabs_kernel<CJ_CODEC_LZ4_BLOCK>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kL2Bytes);
+    hipLaunchKernelGGL(k, dim3(t.grid), dim3(kL2Threads), kL2Bytes, s, a,
+                       (const uint2*)sync, (const ParseMeta*)meta, (uint4*)t.tabs, counter, (const uint2*)first, stream_len, sl);
 }
 
 
