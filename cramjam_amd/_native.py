@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CJ_HIP_LIB") or os.path.join(_HERE, "libcramjam_hip.so")   # CJ_HIP_LIB: a tuning variant (tools/build_variant.sh)
 
 CODEC_LZ4_BLOCK, CODEC_SNAPPY_RAW = 0, 1
+FORMAT_LZ4_FRAME, FORMAT_SNAPPY_FRAMED = 0, 1      # cj_frame_batch_*
 OP_DECOMPRESS, OP_COMPRESS = 0, 1
 FLAG_LZ4_SIZE_PREFIX = 1
 FLAG_FORCE_WAVE_PER_CHUNK = 0x100
@@ -53,6 +54,8 @@ SYMBOLS = {
     "cj_engine_sync": (_int, [_vp]),
     "cj_stream_sync": (_int, [_vp, _vp]),
     "cj_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_frame_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_frame_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_device_alloc": (_vp, [_vp, _sz]),
     "cj_device_free": (None, [_vp, _vp]),
@@ -71,6 +74,7 @@ BENCH_SYMBOLS = {
     "cj_debug_big_parse": (C.c_int64, [_int, _u32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "cj_bench_compare": (_int, [_vp, _vp, _vp, C.c_uint64, _u32, C.c_uint64, _u32, _vp, _vp]),
     "cj_debug_big_scratch_bytes": (C.c_uint64, [_vp]),
+    "cj_debug_xxh32_device": (_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
 }
 
 _lib = None
@@ -110,10 +114,10 @@ def _with_hip_error(ex):
     return msg if msg.endswith(")") else "%s (%s)" % (msg, lib().cj_last_hip_error().decode())
 
 
-def _batch_host_addr():
-    """address of cj_batch_host in the library the engines of this process come from (CJ_HIP_LIB may name a tuning variant; the
-    CPython module links the product library)"""
-    return C.cast(lib().cj_batch_host, C.c_void_p).value
+def _batch_host_addr(name="cj_batch_host"):
+    """address of cj_batch_host (or of cj_frame_batch_host, which has the same signature) in the library the engines of this process
+    come from (CJ_HIP_LIB may name a tuning variant; the CPython module links the product library)"""
+    return C.cast(getattr(lib(), name), C.c_void_p).value
 
 
 class Engine:
@@ -170,21 +174,26 @@ class Engine:
             raise EngineError("timed batch failed: %s" % lib().cj_last_hip_error().decode())
         return ms
 
-    def batch_host(self, codec, op, flags, inputs, out_caps):
+    def frame_batch_device(self, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, stream=None):
+        check(lib().cj_frame_batch_device(self.h, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off,
+                                          out_cap, result, stream))
+
+    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host"):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
-        Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes."""
+        Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
+        fn: "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
         from . import _cramjam                      # the CPython host layer: the engine scatters straight into the bytes objects
         try:
-            return _cramjam.batch_host(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, _batch_host_addr())
+            return _cramjam.batch_host(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, _batch_host_addr(fn))
         except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
             raise EngineError(_with_hip_error(ex)) from None
 
-    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None):
+    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host"):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
         from . import _cramjam
         try:
-            return _cramjam.batch_host_into(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr())
+            return _cramjam.batch_host_into(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr(fn))
         except RuntimeError as ex:
             raise EngineError(_with_hip_error(ex)) from None
 

@@ -13,7 +13,10 @@ def _engine(device):
     return _engines[device]
 
 
-def _run_into(codec, op, flags, inputs, out_caps, devices, out):
+_BLOCKS, _FRAMES = "cj_batch_host", "cj_frame_batch_host"      # the native call: raw blocks, or framed streams (codec is a FORMAT_*)
+
+
+def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS):
     """results + memoryviews into `out` (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output byte"""
     devices = list(devices) if devices is not None else [0]
     n = len(inputs)
@@ -22,13 +25,13 @@ def _run_into(codec, op, flags, inputs, out_caps, devices, out):
         offsets.append(run); run += int(c)
     mv = memoryview(out).cast("B")
     if len(devices) == 1:
-        res = _engine(devices[0]).batch_host_into(codec, op, flags, inputs, out_caps, out, offsets)
+        res = _engine(devices[0]).batch_host_into(codec, op, flags, inputs, out_caps, out, offsets, fn)
     else:
         shards = [list(range(g, n, len(devices))) for g in range(len(devices))]
 
         def work(g):
             idx = shards[g]
-            return _engine(devices[g]).batch_host_into(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], out, [offsets[i] for i in idx])
+            return _engine(devices[g]).batch_host_into(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], out, [offsets[i] for i in idx], fn)
         with ThreadPoolExecutor(len(devices)) as ex:
             parts = list(ex.map(work, range(len(devices))))
         res = [None] * n
@@ -38,18 +41,18 @@ def _run_into(codec, op, flags, inputs, out_caps, devices, out):
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
 
 
-def _run(codec, op, flags, inputs, out_caps, devices, out=None):
+def _run(codec, op, flags, inputs, out_caps, devices, out=None, fn=_BLOCKS):
     if out is not None:
-        return _run_into(codec, op, flags, inputs, out_caps, devices, out)
+        return _run_into(codec, op, flags, inputs, out_caps, devices, out, fn)
     devices = list(devices) if devices is not None else [0]
     n = len(inputs)
     if len(devices) == 1:
-        return _engine(devices[0]).batch_host(codec, op, flags, inputs, out_caps)
+        return _engine(devices[0]).batch_host(codec, op, flags, inputs, out_caps, fn)
     shards = [list(range(g, n, len(devices))) for g in range(len(devices))]   # chunk i -> gpu i mod G
 
     def work(g):
         idx = shards[g]
-        return _engine(devices[g]).batch_host(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx])
+        return _engine(devices[g]).batch_host(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], fn)
     with ThreadPoolExecutor(len(devices)) as ex:
         parts = list(ex.map(work, range(len(devices))))
     res, outs = [None] * n, [None] * n
@@ -87,6 +90,46 @@ def snappy_compress_raw_many(chunks, devices=None, out=None):
     L = N.lib()
     caps = [L.cj_snappy_raw_max_compress_len(len(c)) for c in chunks]
     return _run(N.CODEC_SNAPPY_RAW, N.OP_COMPRESS, 0, chunks, caps, devices, out)
+
+
+# ---- batches of framed streams: one LZ4 frame / Snappy framed stream per entry (cj_frame_batch_host) ----------------------------
+# result[i] and the bytes are what cramjam_amd.lz4.decompress / .compress and cramjam_amd.snappy.decompress / .compress give for that
+# stream alone (the C exports' error codes instead of exceptions); output_lens: per-stream capacities (default: the bound of each stream).
+def _addr_len(b):
+    import numpy as np
+    a = np.frombuffer(b, dtype=np.uint8)
+    return _C.c_void_p(a.ctypes.data if a.size else None), a.size
+
+
+def lz4_decompress_frames(frames, output_lens=None, devices=None, out=None):
+    """decode many LZ4 frames; returns (results, outputs) as lz4_decompress_blocks"""
+    if output_lens is None:
+        L = N.lib()
+        output_lens = [max(L.cj_lz4_frame_decompress_bound(*_addr_len(f)), 0) for f in frames]
+    return _run(N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, frames, output_lens, devices, out, _FRAMES)
+
+
+def lz4_compress_frames(buffers, devices=None, out=None):
+    """one LZ4 frame per buffer (64 KiB independent blocks, content checksum); out: as in lz4_decompress_blocks, it has to hold
+    sum(cj_lz4_frame_compress_bound(len(buffer))) bytes"""
+    L = N.lib()
+    return _run(N.FORMAT_LZ4_FRAME, N.OP_COMPRESS, 0, buffers, [L.cj_lz4_frame_compress_bound(len(memoryview(b).cast("B"))) for b in buffers],
+                devices, out, _FRAMES)
+
+
+def snappy_decompress_framed_many(streams, output_lens=None, devices=None, out=None):
+    """decode many Snappy framed streams"""
+    if output_lens is None:
+        L = N.lib()
+        output_lens = [max(L.cj_snappy_frame_decompress_len(*_addr_len(f)), 0) for f in streams]
+    return _run(N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, streams, output_lens, devices, out, _FRAMES)
+
+
+def snappy_compress_framed_many(buffers, devices=None, out=None):
+    """one Snappy framed stream per buffer"""
+    L = N.lib()
+    return _run(N.FORMAT_SNAPPY_FRAMED, N.OP_COMPRESS, 0, buffers, [L.cj_snappy_frame_max_compress_len(len(memoryview(b).cast("B"))) for b in buffers],
+                devices, out, _FRAMES)
 
 
 # ---- device-resident batches: no host copy, no ctypes at the call site ---------------------------------------------------------
@@ -185,7 +228,7 @@ def _is_device_obj(x):
     return hasattr(x, "__cuda_array_interface__") or (hasattr(x, "__dlpack__") and not hasattr(x, "__array_interface__") and not isinstance(x, (list, tuple)))
 
 
-def _device_batch(codec, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync):
+def _device_batch(codec, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, frames=False):
     import numpy as np
     if stream is not None and int(stream) == 0:
         raise ValueError("cramjam_amd.batch: the NULL stream (torch's default stream has handle 0) cannot be named through the C-ABI, where NULL means "
@@ -232,7 +275,8 @@ def _device_batch(codec, op, flags, inp, in_off, in_len, out, out_off, out_cap, 
             if vr.itemsize != 8 or vr.count != n:
                 raise ValueError("cramjam_amd.batch: result must hold %d 64-bit integers" % n)
             p_res = vr.ptr
-        eng.batch_device(codec, op, flags, n, vin.ptr, p_in_off, p_in_len, vout.ptr, p_out_off, p_out_cap, p_res, stream)
+        submit = eng.frame_batch_device if frames else eng.batch_device
+        submit(codec, op, flags, n, vin.ptr, p_in_off, p_in_len, vout.ptr, p_out_off, p_out_cap, p_res, stream)
         if sync:
             if stream is not None:
                 N.check(N.lib().cj_stream_sync(eng.h, stream))
@@ -278,3 +322,25 @@ def snappy_decompress_raw_many_device(inp, in_off, in_len, out, out_off, out_cap
 def snappy_compress_raw_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Compress a device-resident batch into Snappy raw blocks (src/snappy.rs:70-78); out_cap[i] >= cramjam.snappy.compress_raw_max_len(in_len[i])."""
     return _device_batch(N.CODEC_SNAPPY_RAW, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+# ---- device-resident batches of framed streams (cj_frame_batch_device): the same arguments; stream i is inp[in_off[i] : + in_len[i]] and
+# its output goes to out[out_off[i] : + out_cap[i]].  The call waits for the stream once (it reads back the block counts / in_len).
+def lz4_decompress_frames_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of LZ4 frames (result[i] as cramjam_amd.lz4.decompress of frame i with that capacity)."""
+    return _device_batch(N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+
+
+def lz4_compress_frames_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """One LZ4 frame per device-resident buffer; out_cap[i] >= cj_lz4_frame_compress_bound(in_len[i])."""
+    return _device_batch(N.FORMAT_LZ4_FRAME, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+
+
+def snappy_decompress_framed_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of Snappy framed streams."""
+    return _device_batch(N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+
+
+def snappy_compress_framed_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """One Snappy framed stream per device-resident buffer; out_cap[i] >= cj_snappy_frame_max_compress_len(in_len[i])."""
+    return _device_batch(N.FORMAT_SNAPPY_FRAMED, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)

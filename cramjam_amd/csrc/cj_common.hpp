@@ -91,6 +91,13 @@ struct SlabTabs {
 // one large stream / the blocks of a linked frame (large.hip, frame.hip): t.grid workgroups; done: one zeroed word per slab
 void launch_lz4_decode_lds2_slabs(const BatchArgs& a, const void* sync, const void* meta, uint32_t* counter, const void* first,
                                   uint32_t stream_len, uint32_t* done, const SlabTabs& t, hipStream_t s, int codec, bool rel = false);
+// linked-block LZ4 frames (lz4_decode.hip): one wavefront per job walks blocks [blk0, blk0 + nblk) of the block tables into
+// out_base + out_off[.. out_cap); the single-frame form (frame.hip) is the one-job case
+struct ChainJob { uint64_t blk0, out_off, out_cap; uint32_t nblk, block_max; };
+void launch_lz4_frame_chain(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint32_t nblk, uint8_t* out,
+                            uint64_t out_cap, uint32_t block_max, int64_t* result, hipStream_t s);
+void launch_lz4_frame_chains(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint8_t* out_base, int64_t* result,
+                             const ChainJob* jobs, uint32_t n_jobs, hipStream_t s);
 void launch_snappy_decode_routed(const BatchArgs& a, const void* meta, hipStream_t s);       // wave kernel on chunks the parse kernel routed to it
 hipError_t launch_snappy_encode(const BatchArgs& a, hipStream_t s);
 

@@ -102,6 +102,10 @@ struct cj_engine {
     int big_next = 0;
     cj::DevBuf d_big, d_bigtab;    // large.hip: parse scratch / record tables of one large stream (under `mu`)
     int n_cu = 0;
+    std::mutex fb_mu;              // frame_batch.hip: batches of framed streams — frame table, block rows and decode slots, its staging
+    cj::DevBuf d_fb;
+    cj::PinnedBuf h_fb;
+    hipEvent_t fb_free = nullptr;  // ... recorded after the last kernel that uses them
 };
 
 namespace cj {

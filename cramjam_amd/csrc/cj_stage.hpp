@@ -12,6 +12,48 @@ void launch_crc32c_pieces(const uint8_t* base, const uint64_t* off, const uint64
 void launch_copy_segments(const uint64_t* src, uint8_t* dst_base, const uint64_t* dst_off, const uint64_t* len,
                           const uint64_t* hdr, uint32_t hdr_len, uint32_t n, hipStream_t s);      // frame_kernels.hip
 
+// ---- batches of framed streams (frame_batch.hip host side, frame_kernels.hip device side) -------------------------------------
+// One row per stream.  blk0 / slot0 come from the host's scan of the first pass; the walk's second pass fills the rest.
+struct FbFrame {
+    uint64_t blk0, slot0;          // first block row; offset of the stream's decoded blocks in the scratch (decompress)
+    uint64_t content_size, total;  // LZ4 content size; decoded bytes the walk listed
+    int64_t err, late;             // header-level error; LZ4 late error / Snappy error after the listed pieces
+    uint32_t nblk, block_max;      // blocks (pieces) of the stream: pass 1's count
+    uint32_t content_sum, bits;    // kFb* bits
+};
+constexpr uint32_t kFbIndep = 1, kFbBsum = 2, kFbCsize = 4, kFbCsum = 8, kFbSkip = 16, kFbComplete = 32;
+// The per-block rows: the engine's batch (in_base = the streams, out_base = the scratch) and what the format adds
+struct FbRows {
+    BatchRows b;
+    uint64_t *cp_src, *cp_dst, *cp_len;     // Snappy stored pieces: copy_segments rows into the scratch (len 0 elsewhere)
+    uint64_t *ck_off, *ck_len;              // checksummed bytes: LZ4 block payload in the streams / Snappy piece in the scratch
+    uint32_t *word, *expect, *got;          // LZ4 block word / Snappy decoded length | bit 31 stored; checksum in the stream; computed
+};
+constexpr size_t kFbRowWords = 13;          // u64 rows per block
+inline FbRows fb_rows(uint64_t* base, size_t nb) {
+    FbRows r;
+    r.b = batch_rows(base, nb);
+    uint64_t* p = r.b.end;
+    r.cp_src = p; r.cp_dst = p + nb; r.cp_len = p + 2 * nb; r.ck_off = p + 3 * nb; r.ck_len = p + 4 * nb;
+    r.word = reinterpret_cast<uint32_t*>(p + 5 * nb);
+    r.expect = reinterpret_cast<uint32_t*>(p + 6 * nb);
+    r.got = reinterpret_cast<uint32_t*>(p + 7 * nb);
+    return r;
+}
+// pass 1 (cnt != nullptr: cnt[2i] = blocks, cnt[2i + 1] = scratch bytes) or pass 2 (the rows, the chain jobs of LZ4 frames with linked blocks)
+void launch_fb_walk(int fmt, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint64_t* cnt,
+                    FbFrame* fr, FbRows r, ChainJob* jobs, hipStream_t s);
+// out[i] = XXH32(base + off[i] .. + len[i]), seed 0; one wavefront per stream
+void launch_xxh32_streams(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint32_t* out, size_t n, hipStream_t s);
+// decompress: the stream-order verdict of each stream, its bytes compacted into out_base + out_off[i] (LZ4: then the content checksum)
+void launch_fb_finish(int fmt, size_t n, const FbFrame* fr, FbRows r, const uint8_t* in_base, const uint8_t* scratch, uint8_t* out_base,
+                      const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s);
+// compress: the rows of the 64 KiB pieces (fr[i].blk0 = first piece) into the scratch, `stride` bytes apart
+void launch_fb_pieces(size_t n, const FbFrame* fr, const uint64_t* in_off, const uint64_t* in_len, BatchRows b, uint64_t stride, hipStream_t s);
+// compress: header, block words / chunk headers, payloads (stored or from the scratch), EndMark and checksum; sums = LZ4 content XXH32
+void launch_fb_assemble(int fmt, size_t n, const FbFrame* fr, FbRows r, const uint32_t* sums, const uint8_t* in_base, const uint64_t* in_len, const uint8_t* scratch, uint64_t stride, uint8_t* out_base, const uint64_t* out_off,
+                        const uint64_t* out_cap, int64_t* result, hipStream_t s);
+
 // Compress in[0, n), cut into pieces of `piece` bytes, as ONE batch into e->d_out (`stride` bytes apart), the input staged at e->d_in + H
 // behind the last H bytes before it (hist: linked LZ4 blocks, kFlagLinkedEnc — piece 0 may refer to those H bytes, every other piece to
 // the piece before it).  Queues the results' copy into res and, with `first`, the stitch plan kernel (first[i] = literal length of piece
@@ -63,6 +105,17 @@ int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lead_len, 
 inline int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lead_len, std::initializer_list<const Segments*> lists, uint8_t* out) {
     return assemble(e, size, lead, lead_len, lists, 0, [](uint8_t*) { return 0; }, out);
 }
+
+// A host batch (engine.hip): lay_out puts the rows of n buffers in e->h_meta — inputs and outputs one after another, 16 bytes aligned,
+// their sizes added to in_total / out_total (widen: LZ4 block compress gets a full LZ4_compressBound of room on the device); pack
+// copies the inputs of [a0, b0) into e->h_in, scatter the results res of [a0, b0) into result (within_cap) and their outputs from
+// e->h_out to the caller
+BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const size_t* in_lens, const size_t* out_caps,
+                  uint64_t& in_total, uint64_t& out_total, bool widen = true);
+int64_t within_cap(int64_t r, size_t cap);
+void pack(cj_engine* e, const BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const uint8_t* const* in_ptrs, const size_t* in_lens);
+void scatter(cj_engine* e, const BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const int64_t* res, uint8_t* const* out_ptrs,
+             const size_t* out_caps, int64_t* result);
 
 // The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
 int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);

@@ -2,8 +2,9 @@
 // submission, host staging and the single-buffer drop-in entry points.  Host-side C++ over the HIP
 // runtime; all codec arithmetic is in the four *_decode/_encode.hip kernels.  There is no CPU codec
 // in this library: if no device is usable the entry points return CJ_E_NO_DEVICE.
-#include "cj_engine.hpp"
+#include "cj_stage.hpp"
 #include "big_chunks.hpp"
+#include "frame_grammar.hpp"
 
 using cj::hip_ok;
 using cj::parallel_chunks;
@@ -266,10 +267,14 @@ int64_t single(cj_codec codec, cj_op op, uint32_t flags, const uint8_t* in, size
     return rc != 0 ? (int64_t)rc : res;
 }
 
+}  // namespace
+
+namespace cj {
+
 // The rows of a host batch in e->h_meta: inputs and outputs one after another, 16 bytes aligned, their sizes added to in_total / out_total.
 // LZ4 compress: the kernel gets a full LZ4_compressBound of room on the device; the caller's capacity applies when copying back (within_cap).
 cj::BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const size_t* in_lens, const size_t* out_caps,
-                      uint64_t& in_total, uint64_t& out_total) {
+                      uint64_t& in_total, uint64_t& out_total, bool widen) {
     e->h_meta.assign(5 * n, 0);
     const cj::BatchRows h = cj::batch_rows(e->h_meta.data(), n);
     for (size_t i = 0; i < n; i++) {
@@ -277,7 +282,7 @@ cj::BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, si
         h.in_len[i] = in_lens[i];
         in_total += (in_lens[i] + 15u) & ~(uint64_t)15u;
         uint64_t dcap = out_caps[i];
-        if (codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS)
+        if (widen && codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS)
             dcap = std::max<uint64_t>(dcap, cj_lz4_block_compress_bound(in_lens[i], (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0));
         h.out_off[i] = out_total;
         h.out_cap[i] = dcap;
@@ -307,6 +312,15 @@ void scatter(cj_engine* e, const cj::BatchRows& h, size_t a0, size_t b0, uint64_
         }
     });
 }
+
+}  // namespace cj
+
+using cj::lay_out;
+using cj::within_cap;
+using cj::pack;
+using cj::scatter;
+
+namespace {
 
 // A LARGE host batch, in slices: while slice k is uploaded and decoded on the engine's stream and slice k - 1 travels back
 // on a second one, the host packs slice k + 1 into the pinned staging and scatters the slices that have arrived — the one-shot
@@ -432,22 +446,7 @@ size_t cj_snappy_raw_max_compress_len(size_t len) {
     return m > 0xFFFFFFFFull ? 0 : (size_t)m;
 }
 
-int64_t cj_snappy_raw_decompress_len(const uint8_t* in, size_t n) {
-    if (n == 0) return 0;
-    uint64_t v = 0;
-    unsigned shift = 0;
-    for (size_t i = 0; i < n && i < 10; i++) {
-        uint8_t b = in[i];
-        if (b < 0x80) {
-            if (i == 9 && b > 1) return CJ_E_SNAPPY_HEADER;
-            v |= (uint64_t)b << shift;
-            return v > 0xFFFFFFFFull ? (int64_t)CJ_E_SNAPPY_TOO_BIG : (int64_t)v;
-        }
-        v |= (uint64_t)(b & 0x7f) << shift;
-        shift += 7;
-    }
-    return CJ_E_SNAPPY_HEADER;
-}
+int64_t cj_snappy_raw_decompress_len(const uint8_t* in, size_t n) { return cj::snappy_varint_len(in, n); }
 
 int cj_engine_create(int device, cj_engine** out) {
     if (!out) return CJ_E_BAD_ARG;
@@ -471,7 +470,8 @@ void cj_engine_destroy(cj_engine* e) {
     for (hipEvent_t ev : e->slice_ev) (void)hipEventDestroy(ev);
     if (e->stream_back) (void)hipStreamDestroy(e->stream_back);
     if (e->scratch_free) (void)hipEventDestroy(e->scratch_free);
-   
+    e->d_fb.release(); e->h_fb.release();
+    if (e->fb_free) (void)hipEventDestroy(e->fb_free);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }

@@ -9,13 +9,9 @@
 #include "cj_stage.hpp"
 #include "xxh32_host.hpp"
 #include "lz4_lane_walk.hpp"
+#include "frame_grammar.hpp"
 
 #include <atomic>
-
-namespace cj {
-void launch_lz4_frame_chain(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint32_t nblk, uint8_t* out,
-                            uint64_t out_cap, uint32_t block_max, int64_t* result, hipStream_t s);
-}
 
 namespace {
 // (tuning builds only: every linked-block frame through the chain kernel; the shipped library reads no environment)
@@ -28,73 +24,11 @@ inline bool lz4f_chain_only() {
 #endif
 }
 
-constexpr size_t kPiece = 65536;          // snap MAX_BLOCK_SIZE
-constexpr size_t kMaxChunk = 76490;       // snap MAX_COMPRESS_BLOCK_SIZE = max_compress_len(65536)
-constexpr size_t kTmpStride = 76496;      // kMaxChunk rounded up to 16
+constexpr size_t kPiece = cj::kSnapPiece;
+constexpr size_t kTmpStride = 76496;      // cj::kSnapMaxChunk rounded up to 16
 const uint8_t kIdent[10] = { 0xff, 0x06, 0x00, 0x00, 's', 'N', 'a', 'P', 'p', 'Y' };
 
-struct Piece {
-    uint64_t src_off;     // payload offset in the framed stream
-    uint64_t dst_off;     // offset of the decoded piece in the output
-    uint32_t src_len, dst_len, crc;
-    bool stored;
-};
-
-// Walk the chunk grammar (snap read::FrameDecoder::read).  Data chunks are appended to `pieces` (may be null);
-// returns 0 or the first header-level error, in which case the pieces before it are still listed: snap would
-// have decoded those first, so their errors take precedence.
-int64_t snappy_frame_walk(const uint8_t* in, size_t n, std::vector<Piece>* pieces, uint64_t* total) {
-    size_t pos = 0;
-    uint64_t op = 0;
-    bool ident = false;
-    int64_t err = 0;
-    while (pos < n) {
-        if (n - pos < 4) { err = CJ_E_FRAME_EOF; break; }
-        const uint8_t ty = in[pos];
-        if (!ident) {
-            if (ty != 0xff) { err = CJ_E_SNAPPY_STREAM_HEADER; break; }
-            ident = true;
-        }
-        const size_t len = (size_t)in[pos + 1] | ((size_t)in[pos + 2] << 8) | ((size_t)in[pos + 3] << 16);
-        if (len > kMaxChunk) { err = CJ_E_SNAPPY_CHUNK_LEN; break; }
-        pos += 4;
-        if (ty >= 0x02 && ty <= 0x7f) { err = CJ_E_SNAPPY_CHUNK_TYPE; break; }
-        if (ty >= 0x80 && ty <= 0xfe) {                 // reserved skippable, padding
-            if (n - pos < len) { err = CJ_E_FRAME_EOF; break; }
-            pos += len;
-            continue;
-        }
-        if (ty == 0xff) {
-            if (len != 6) { err = CJ_E_SNAPPY_CHUNK_LEN; break; }
-            if (n - pos < 6) { err = CJ_E_FRAME_EOF; break; }
-            if (std::memcmp(in + pos, kIdent + 4, 6) != 0) { err = CJ_E_SNAPPY_STREAM_HEADER; break; }
-            pos += 6;
-            continue;
-        }
-        if (len < 4) { err = CJ_E_SNAPPY_CHUNK_LEN; break; }
-        if (n - pos < 4) { err = CJ_E_FRAME_EOF; break; }
-        Piece p;
-        p.crc = (uint32_t)in[pos] | ((uint32_t)in[pos + 1] << 8) | ((uint32_t)in[pos + 2] << 16) | ((uint32_t)in[pos + 3] << 24);
-        pos += 4;
-        const size_t sn = len - 4;
-        p.stored = ty == 0x01;
-        if (p.stored && sn > kPiece) { err = CJ_E_SNAPPY_CHUNK_LEN; break; }
-        if (n - pos < sn) { err = CJ_E_FRAME_EOF; break; }
-        uint64_t dn = sn;
-        if (!p.stored) {
-            const int64_t d = cj_snappy_raw_decompress_len(in + pos, sn);   // empty block -> 0; the decoder then reports Empty
-            if (d < 0) { err = d; break; }
-            if ((uint64_t)d > kPiece) { err = CJ_E_SNAPPY_CHUNK_LEN; break; }
-            dn = (uint64_t)d;
-        }
-        p.src_off = pos; p.src_len = (uint32_t)sn; p.dst_off = op; p.dst_len = (uint32_t)dn;
-        if (pieces) pieces->push_back(p);
-        pos += sn;
-        op += dn;
-    }
-    if (total) *total = op;
-    return err;
-}
+using Piece = cj::SnapPiece;
 
 }  // namespace
 
@@ -108,7 +42,7 @@ size_t cj_snappy_frame_max_compress_len(size_t n) {
 int64_t cj_snappy_frame_decompress_len(const uint8_t* in, size_t n) {
     if (n && !in) return CJ_E_BAD_ARG;
     uint64_t total = 0;
-    const int64_t err = snappy_frame_walk(in, n, nullptr, &total);
+    const int64_t err = cj::snappy_frame_walk(in, n, [](const Piece&) {}, &total);
     return err ? err : (int64_t)total;
 }
 
@@ -118,7 +52,7 @@ int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, si
     if (!e) return CJ_E_NO_DEVICE;
     std::vector<Piece> pieces;
     uint64_t total = 0;
-    const int64_t gerr = snappy_frame_walk(in, n, &pieces, &total);
+    const int64_t gerr = cj::snappy_frame_walk(in, n, [&](const Piece& p) { pieces.push_back(p); }, &total);
     const size_t np = pieces.size();
     if (np == 0) return gerr;
     if (np > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
@@ -252,57 +186,18 @@ constexpr size_t kLz4fBlock = 65536;                      // the reference encod
 constexpr size_t kLz4fTmpStride = 65824;                  // LZ4_compressBound(65536) = 65809, rounded up to 16
 
 struct Lz4Block { uint64_t src_off; uint32_t word; };     // word = size | bit 31 (stored)
-struct Lz4Frame {
-    bool indep = true, bsum = false, csize = false, csum = false;
-    uint32_t block_max = 0;
-    uint64_t content_size = 0;
-    uint32_t content_sum = 0;
+struct Lz4Frame : cj::Lz4Header {
     std::vector<Lz4Block> blocks;
-    bool skippable = false;
-    bool complete = false;        // the EndMark was reached
-    int64_t late_err = 0;         // error met while walking the blocks (the blocks listed before it are intact)
 };
 
-// header + block walk (LZ4F_decompress's own checks; truncation = the lz4 crate's "Finish runned before read end ...")
+// the shared walk (frame_grammar.hpp), the blocks listed; with verify_block_sums the walk stops at the first bad block checksum
 int64_t lz4_frame_walk(const uint8_t* in, size_t n, Lz4Frame& f, bool verify_block_sums) {
-    if (n >= 8 && (xrd32(in) & 0xFFFFFFF0u) == 0x184D2A50u) {
-        f.skippable = true;
-        return n - 8 < xrd32(in + 4) ? (int64_t)CJ_E_LZ4F_INCOMPLETE : 0;
-    }
-    if (n < 7) return CJ_E_LZ4F_INCOMPLETE;
-    if (xrd32(in) != 0x184D2204u) return CJ_E_LZ4F_FRAME_TYPE;
-    const uint8_t flg = in[4], bd = in[5];
-    if ((flg >> 6) != 1 || (flg & 0x02)) return CJ_E_LZ4F_HEADER;
-    if ((bd & 0x8F) != 0) return CJ_E_LZ4F_HEADER;
-    f.indep = (flg >> 5) & 1; f.bsum = (flg >> 4) & 1; f.csize = (flg >> 3) & 1; f.csum = (flg >> 2) & 1;
-    const bool dictid = flg & 1;
-    const uint32_t code = (bd >> 4) & 7;
-    if (code < 4) return CJ_E_LZ4F_BLOCK_SIZE;
-    f.block_max = 1u << (8 + 2 * code);
-    const size_t hl = 6 + (f.csize ? 8 : 0) + (dictid ? 4 : 0);
-    if (n < hl + 1) return CJ_E_LZ4F_INCOMPLETE;
-    if (f.csize) f.content_size = (uint64_t)xrd32(in + 6) | ((uint64_t)xrd32(in + 10) << 32);
-    if (in[hl] != (uint8_t)(xxh32(in + 4, hl - 4, 0) >> 8)) return CJ_E_LZ4F_HEADER;
-    // block walk: an error here is a LATE error — the streaming decoder has already written the blocks before it
-    size_t pos = hl + 1;
-    for (;;) {
-        if (n - pos < 4) { f.late_err = CJ_E_LZ4F_INCOMPLETE; return 0; }
-        const uint32_t w = xrd32(in + pos);
-        pos += 4;
-        if (w == 0) break;
+    return cj::lz4_frame_walk(in, n, f, [&](uint64_t pos, uint32_t w) {
         const size_t sz = w & 0x7FFFFFFFu;
-        if (sz > f.block_max) { f.late_err = CJ_E_LZ4F_BLOCK_SIZE; return 0; }
-        if (n - pos < sz + (f.bsum ? 4u : 0u)) { f.late_err = CJ_E_LZ4F_INCOMPLETE; return 0; }
-        if (f.bsum && verify_block_sums && xrd32(in + pos + sz) != xxh32(in + pos, sz, 0)) { f.late_err = CJ_E_LZ4F_BLOCK_CHECKSUM; return 0; }
+        if (f.bsum && verify_block_sums && xrd32(in + pos + sz) != xxh32(in + pos, sz, 0)) return false;
         f.blocks.push_back({pos, w});
-        pos += sz + (f.bsum ? 4 : 0);
-    }
-    f.complete = true;
-    if (f.csum) {
-        if (n - pos < 4) { f.late_err = CJ_E_LZ4F_INCOMPLETE; return 0; }
-        f.content_sum = xrd32(in + pos);
-    }
-    return 0;
+        return true;
+    });
 }
 
 }  // namespace

@@ -1,0 +1,162 @@
+// frame_batch.hip — many independent framed streams per call (cj_frame_batch_device / cj_frame_batch_host): LZ4 frames and
+// Snappy framed streams, both directions.  Everything specific to the format runs on the device, because a device batch has no
+// host copy of its streams: the grammar walk (one lane per stream, two passes around one read-back of the block counts), XXH32
+// and CRC-32C, the stream-order verdict and the assembly (frame_kernels.hip).  The blocks go through the batch engine as one
+// batch; linked LZ4 blocks through the chain kernel, one wavefront per frame.  The verdicts are those of the single-stream
+// exports in frame.hip.
+#include "cj_stage.hpp"
+
+namespace {
+
+constexpr uint64_t kLz4Stride = 65824;       // LZ4_compressBound(65536) = 65809, rounded up to 16
+constexpr uint64_t kSnapStride = 76496;      // max_compress_len(65536) = 76490, rounded up to 16
+constexpr uint64_t kPiece = 65536;
+
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+// the frame batch's scratch (e->d_fb, e->h_fb) is reused by the next call: it waits for this one on the device; growing it waits on the host
+int fb_reserve(cj_engine* e, size_t dev_bytes, size_t host_bytes) {
+    if ((dev_bytes > e->d_fb.cap || host_bytes > e->h_fb.cap) && e->fb_free) HIP_TRY(hipEventSynchronize(e->fb_free), CJ_E_NO_DEVICE);
+    if (!e->d_fb.reserve(dev_bytes) || !e->h_fb.reserve(host_bytes)) return CJ_E_OOM;
+    return 0;
+}
+
+int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
+    // (the lock is held across the one wait below: frame batches on one engine run one after another, and a call waits for everything
+    //  its caller queued on `s` before it, so a second caller's batch also waits behind that.  Engines are cheap: one per thread or stream
+    //  avoids it.)
+    std::lock_guard<std::mutex> lock(e->fb_mu);
+    if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
+    else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);          // the previous user of the scratch
+    const size_t tab = up16(n * sizeof(cj::FbFrame));
+    int rc = fb_reserve(e, std::max(16 * n, tab), tab + 16 * n);
+    if (rc != 0) return rc;
+    uint64_t* cnt = (uint64_t*)e->h_fb.p;                                         // read back: [2i] blocks, [2i + 1] scratch bytes / in_len
+    cj::FbFrame* h_fr = reinterpret_cast<cj::FbFrame*>(e->h_fb.p + 16 * n);
+    const bool dec = op == CJ_OP_DECOMPRESS;
+    // the one wait: the host sizes the block rows and the scratch from the streams' block counts (decompress) / lengths (compress)
+    if (dec) {
+        cj::launch_fb_walk(fmt, n, in_base, in_off, in_len, (uint64_t*)e->d_fb.p, nullptr, cj::FbRows{}, nullptr, s);
+        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+        HIP_TRY(hipMemcpyAsync(cnt, e->d_fb.p, 16 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    } else {
+        HIP_TRY(hipMemcpyAsync(cnt, in_len, 8 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    }
+    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    std::memset(h_fr, 0, n * sizeof(cj::FbFrame));
+    uint64_t nb = 0, slot = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t k = dec ? cnt[2 * i] : (cnt[i] + kPiece - 1) / kPiece;
+        h_fr[i].blk0 = nb; h_fr[i].slot0 = slot; h_fr[i].nblk = (uint32_t)k;
+        nb += k;
+        if (dec) slot += up16(cnt[2 * i + 1]);
+    }
+    if (nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    const uint64_t stride = fmt == CJ_FORMAT_LZ4_FRAME ? kLz4Stride : kSnapStride;
+    if (!dec) slot = nb * stride;
+    // d_fb: frames | chain jobs (decompress) / content sums (compress) | block rows | scratch
+    const size_t o_side = tab, o_rows = o_side + up16(n * sizeof(cj::ChainJob)), o_scr = o_rows + cj::kFbRowWords * 8 * nb;
+    rc = fb_reserve(e, o_scr + slot + 16, tab + 16 * n);
+    if (rc != 0) return rc;
+    uint8_t* d = (uint8_t*)e->d_fb.p;
+    cj::FbFrame* fr = reinterpret_cast<cj::FbFrame*>(d);
+    const cj::FbRows r = cj::fb_rows(reinterpret_cast<uint64_t*>(d + o_rows), nb);
+    uint8_t* scratch = d + o_scr;
+    HIP_TRY(hipMemcpyAsync(fr, h_fr, n * sizeof(cj::FbFrame), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    if (dec) {
+        cj::ChainJob* jobs = reinterpret_cast<cj::ChainJob*>(d + o_side);
+        cj::launch_fb_walk(fmt, n, in_base, in_off, in_len, nullptr, fr, r, jobs, s);
+        if (nb) {
+            cj::BatchArgs a;
+            cj::fill_args(a, 0, in_base, scratch, r.b);
+            rc = cj::launch(e, fmt == CJ_FORMAT_LZ4_FRAME ? CJ_CODEC_LZ4_BLOCK : CJ_CODEC_SNAPPY_RAW, CJ_OP_DECOMPRESS, a, s);
+            if (rc != 0) return rc;
+        }
+        if (fmt == CJ_FORMAT_LZ4_FRAME) {
+            cj::launch_lz4_frame_chains(in_base, r.b.in_off, r.word, scratch, r.b.result, jobs, (uint32_t)n, s);
+            cj::launch_xxh32_streams(in_base, r.ck_off, r.ck_len, r.got, nb, s);
+        } else {
+            cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)nb, s);
+            cj::launch_crc32c_pieces(scratch, r.ck_off, r.ck_len, r.got, (uint32_t)nb, s);
+        }
+        cj::launch_fb_finish(fmt, n, fr, r, in_base, scratch, out_base, out_off, out_cap, result, s);
+    } else {
+        uint32_t* sums = reinterpret_cast<uint32_t*>(d + o_side);
+        cj::launch_fb_pieces(n, fr, in_off, in_len, r.b, stride, s);
+        if (nb) {
+            cj::BatchArgs a;
+            cj::fill_args(a, 0, in_base, scratch, r.b);
+            rc = cj::launch(e, fmt == CJ_FORMAT_LZ4_FRAME ? CJ_CODEC_LZ4_BLOCK : CJ_CODEC_SNAPPY_RAW, CJ_OP_COMPRESS, a, s);
+            if (rc != 0) return rc;
+        }
+        if (fmt == CJ_FORMAT_LZ4_FRAME) cj::launch_xxh32_streams(in_base, in_off, in_len, sums, n, s);
+        else cj::launch_crc32c_pieces(in_base, r.b.in_off, r.b.in_len, r.got, (uint32_t)nb, s);
+        cj::launch_fb_assemble(fmt, n, fr, r, sums, in_base, in_len, scratch, stride, out_base, out_off, out_cap, result, s);
+    }
+    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+    HIP_TRY(hipEventRecord(e->fb_free, s), CJ_E_NO_DEVICE);
+    return 0;
+}
+
+bool fb_args_ok(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags) {
+    return e && flags == 0 && (fmt == CJ_FORMAT_LZ4_FRAME || fmt == CJ_FORMAT_SNAPPY_FRAMED) && (op == CJ_OP_DECOMPRESS || op == CJ_OP_COMPRESS);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cj_frame_batch_device(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, size_t n_frames,
+                          const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                          uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                          int64_t* result, void* hip_stream) {
+    if (!fb_args_ok(e, fmt, op, flags) || n_frames > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    if (n_frames == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    return frame_batch(e, fmt, op, n_frames, in_base, in_off, in_len, out_base, out_off, out_cap, result,
+                       hip_stream ? (hipStream_t)hip_stream : e->stream);
+}
+
+int cj_frame_batch_host(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, size_t n,
+                        const uint8_t* const* in_ptrs, const size_t* in_lens,
+                        uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result) {
+    if (!fb_args_ok(e, fmt, op, flags) || (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result))) return CJ_E_BAD_ARG;
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    uint64_t in_total = 0, out_total = 0;
+    const cj::BatchRows h = cj::lay_out(e, CJ_CODEC_LZ4_BLOCK, op, 0u, n, in_lens, out_caps, in_total, out_total, false);
+    if (!e->d_in.reserve(in_total + 16) || !e->d_out.reserve(out_total + 16) || !e->d_meta.reserve(5 * n * 8) || !e->h_in.reserve(in_total))
+        return CJ_E_OOM;
+    uint8_t* d_in = (uint8_t*)e->d_in.p;
+    uint8_t* d_out = (uint8_t*)e->d_out.p;
+    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
+    cj::pack(e, h, 0, n, in_total, in_ptrs, in_lens);
+    if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);     // (the rows up to result)
+    const int rc = frame_batch(e, fmt, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, e->stream);
+    if (rc != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
+    uint64_t span = 0;
+    for (size_t i = 0; i < n; i++)
+        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
+    if (!e->h_out.reserve(span)) return CJ_E_OOM;
+    if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
+    cj::scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
+    return 0;
+}
+
+// debug aid (tests): XXH32 of n device streams by the batch's kernel, on the engine's stream, synchronously
+int cj_debug_xxh32_device(cj_engine* e, const uint8_t* d_base, const uint64_t* d_off, const uint64_t* d_len, uint32_t* d_out, size_t n) {
+    if (!e) return CJ_E_BAD_ARG;
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    cj::launch_xxh32_streams(d_base, d_off, d_len, d_out, n, e->stream);
+    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
+    return 0;
+}
+
+}  // extern "C"

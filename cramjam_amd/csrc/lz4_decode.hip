@@ -121,17 +121,21 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_decode_kernel(BatchArgs a, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// LZ4 FRAME with LINKED blocks (frame.hip): block k may copy from the previous 64 KiB of output, so the blocks of a
-// frame form a chain.  One wavefront walks them in order and decodes straight into the contiguous output; stored
-// blocks are copied.  word[k] = block size | bit 31 (stored).  result[k] = decoded size or CJ_E_CORRUPT; the walk stops
-// at the first bad block.  (Slow by construction — one wave, one dependency chain; frames with independent blocks take
-// the batch path instead.)
+// LZ4 FRAMES with LINKED blocks (frame.hip, frame_batch.hip): block k may copy from the previous 64 KiB of output, so the
+// blocks of a frame form a chain.  One wavefront per frame walks them in order and decodes straight into the frame's
+// contiguous output; stored blocks are copied.  word[k] = block size | bit 31 (stored).  result[k] = decoded size or
+// CJ_E_CORRUPT; the walk stops at the first bad block.  (Slow by construction — one wave, one dependency chain; frames
+// with independent blocks take the batch path instead.)  jobs == nullptr: the one frame `one` (grid of one wavefront).
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void lz4_frame_chain_kernel(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word,
-                                                             uint32_t nblk, uint8_t* out, uint64_t out_cap, uint32_t block_max,
-                                                             int64_t* result) {
+                                                             uint8_t* out_base, int64_t* result, const ChainJob* jobs, ChainJob one) {
+    const ChainJob j = jobs != nullptr ? jobs[blockIdx.x] : one;
+    const uint32_t nblk = uni(j.nblk), block_max = uni(j.block_max);
+    uint8_t* out = out_base + j.out_off;
+    const uint64_t out_cap = j.out_cap;
     uint64_t pos = 0;
-    for (uint32_t k = 0; k < nblk; k++) {
+    for (uint32_t i = 0; i < nblk; i++) {
+        const uint64_t k = j.blk0 + i;
         const uint32_t wd = uni(word[k]);
         const uint32_t sz = wd & 0x7FFFFFFFu;
         const uint8_t* src = in + blk_off[k];
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(64) void lz4_frame_chain_kernel(const uint8_t* in, 
         }
         if (lane_id() == 0) result[k] = r;
         if (r < 0) {
-            for (uint32_t j = k + 1 + lane_id(); j < nblk; j += 64u) result[j] = CJ_E_CORRUPT;
+            for (uint32_t m = i + 1 + lane_id(); m < nblk; m += 64u) result[j.blk0 + m] = CJ_E_CORRUPT;
             return;
         }
         pos += (uint64_t)r;
@@ -157,7 +161,14 @@ __global__ __launch_bounds__(64) void lz4_frame_chain_kernel(const uint8_t* in, 
 void launch_lz4_frame_chain(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint32_t nblk, uint8_t* out,
                             uint64_t out_cap, uint32_t block_max, int64_t* result, hipStream_t s) {
     if (nblk == 0) return;
-    hipLaunchKernelGGL(lz4_frame_chain_kernel, dim3(1), dim3(64), 0, s, in, blk_off, word, nblk, out, out_cap, block_max, result);
+    const ChainJob one = { 0, 0, out_cap, nblk, block_max };
+    hipLaunchKernelGGL(lz4_frame_chain_kernel, dim3(1), dim3(64), 0, s, in, blk_off, word, out, result, (const ChainJob*)nullptr, one);
+}
+
+void launch_lz4_frame_chains(const uint8_t* in, const uint64_t* blk_off, const uint32_t* word, uint8_t* out_base, int64_t* result,
+                             const ChainJob* jobs, uint32_t n_jobs, hipStream_t s) {
+    if (n_jobs == 0) return;
+    hipLaunchKernelGGL(lz4_frame_chain_kernel, dim3(n_jobs), dim3(64), 0, s, in, blk_off, word, out_base, result, jobs, ChainJob{});
 }
 
 void launch_lz4_decode(const BatchArgs& a, hipStream_t s) {

@@ -18,8 +18,9 @@
  *     src/lz4.rs:84,126,163,205; src/snappy.rs:57,75,97,106).
  *   - all codec arithmetic (and the Snappy framing CRC-32C) runs in HIP kernels on the GPU.  There is NO CPU
  *     fallback: without a usable HIP device every compute entry point returns CJ_E_NO_DEVICE.  The one
- *     piece of checksum arithmetic on the host is the LZ4 frame format's XXH32 (a serial recurrence per frame;
- *     it runs on a thread concurrently with the device batch — see DESIGN.md §5.5).
+ *     piece of checksum arithmetic on the host is the single-frame LZ4 exports' XXH32 (a serial recurrence per
+ *     frame; it runs on a thread concurrently with the device batch — see DESIGN.md §5.5).  The frame batches
+ *     (cj_frame_batch_*) compute XXH32 on the device: their streams may have no host copy.
  */
 #ifndef CRAMJAM_HIP_H
 #define CRAMJAM_HIP_H
@@ -238,6 +239,28 @@ CJ_API double cj_batch_device_timed(cj_engine* e, cj_codec codec, cj_op op, uint
                              const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                              uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
                              int64_t* result, int reps);
+
+/* Batches of framed streams: LZ4 frames (cj_lz4_frame_*) or Snappy framed streams (cj_snappy_frame_*), one independent stream
+ * per entry.  Addressing, alignment and stream rules are cj_batch_device's: stream i reads in_base + in_off[i] .. + in_len[i] and
+ * writes only inside out_base + out_off[i] .. + out_cap[i].  flags is reserved (0); an unknown fmt or op is CJ_E_BAD_ARG.
+ *   decompress  result[i] = what cj_lz4_frame_decompress / cj_snappy_frame_decompress return for stream i alone with cap = out_cap[i]
+ *               (the same error, by the same stream-order precedence), and the same bytes when >= 0.
+ *   compress    result[i] = frame size or CJ_E_* (CJ_E_FRAME_WRITE when out_cap[i] is too small; nothing is written then).  The
+ *               single-call layout (LZ4: FLG 0x64 / BD 0x40, 64 KiB independent blocks, content checksum; Snappy: stream identifier,
+ *               64 KiB chunks, masked CRC-32C) with the payloads of cj_batch_device's compress of each 64 KiB piece.
+ * Everything specific to the format runs on the device (grammar walk, XXH32, CRC-32C, verdicts, assembly).  NOT enqueue-only: the
+ * device call waits for hip_stream once — it reads back the streams' block counts (decompress) / in_len (compress) to size the
+ * block table and the grids — then enqueues the rest and returns; synchronise before reading result.  The host call is pack ->
+ * H2D -> the device path -> D2H -> scatter, synchronous.  Frame batches on one engine run one after another (a call holds the engine's
+ * frame-batch scratch across its wait, so a second caller also waits behind what the first queued on its stream). */
+typedef enum { CJ_FORMAT_LZ4_FRAME = 0, CJ_FORMAT_SNAPPY_FRAMED = 1 } cj_format;
+CJ_API int cj_frame_batch_device(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, size_t n_frames,
+                                 const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                 int64_t* result, void* hip_stream);
+CJ_API int cj_frame_batch_host(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, size_t n_frames,
+                               const uint8_t* const* in_ptrs, const size_t* in_lens,
+                               uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 
 /* Thin device-memory helpers so C / ctypes callers need no HIP binding of their own. */
 CJ_API void* cj_device_alloc(cj_engine* e, size_t bytes);

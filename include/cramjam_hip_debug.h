@@ -27,6 +27,10 @@ CJ_API int64_t cj_debug_big_parse(int codec, uint32_t flags, const uint8_t* in, 
 /* bytes of device scratch the engine holds for CJ_FLAG_BIG_CHUNKS batches (list, record areas, summaries, the slab decoder's tables) */
 CJ_API uint64_t cj_debug_big_scratch_bytes(cj_engine* e);
 
+/* XXH32 (seed 0) of n device streams d_base + d_off[i] .. + d_len[i] into d_out[i] by the frame batches' one-wavefront-per-stream kernel;
+ * synchronous (tests hold it to the reference algorithm at every alignment) */
+CJ_API int cj_debug_xxh32_device(cj_engine* e, const uint8_t* d_base, const uint64_t* d_off, const uint64_t* d_len, uint32_t* d_out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
