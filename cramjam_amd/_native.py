@@ -56,6 +56,10 @@ SYMBOLS = {
     "cj_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_frame_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_frame_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_frame_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_frame_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_device_alloc": (_vp, [_vp, _sz]),
     "cj_device_free": (None, [_vp, _vp]),

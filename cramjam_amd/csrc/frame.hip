@@ -41,9 +41,7 @@ size_t cj_snappy_frame_max_compress_len(size_t n) {
 
 int64_t cj_snappy_frame_decompress_len(const uint8_t* in, size_t n) {
     if (n && !in) return CJ_E_BAD_ARG;
-    uint64_t total = 0;
-    const int64_t err = cj::snappy_frame_walk(in, n, [](const Piece&) {}, &total);
-    return err ? err : (int64_t)total;
+    return cj::snappy_frame_len(in, n);
 }
 
 int64_t cj_snappy_frame_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap) {
@@ -296,22 +294,7 @@ size_t cj_lz4_frame_compress_bound(size_t n) {
 
 int64_t cj_lz4_frame_decompress_bound(const uint8_t* in, size_t n) {
     if (n && !in) return CJ_E_BAD_ARG;
-    Lz4Frame f;
-    const int64_t err = lz4_frame_walk(in, n, f, false);
-    if (err) return err;
-    if (f.skippable) return 0;
-    if (f.late_err) return f.late_err;
-    // what the blocks can produce at most: a stored block its own size, a compressed block of c bytes at most 255 c + 64 (an
-    // LZ4 length byte stands for at most 255 bytes) and never more than the frame's block size.  The announced content size
-    // is attacker-controlled: it bounds the result from above, it never raises it (a 19-byte frame announcing 2^46 bytes
-    // used to make the caller allocate that; values >= 2^63 turned into bogus negative "error codes")
-    uint64_t total = 0;
-    for (const Lz4Block& b : f.blocks) {
-        const uint64_t c = b.word & 0x7FFFFFFFu;
-        total += (b.word & 0x80000000u) ? c : std::min<uint64_t>(f.block_max, 255ull * c + 64ull);
-    }
-    if (f.csize && f.content_size < total) return (int64_t)f.content_size;
-    return (int64_t)total;
+    return cj::lz4_frame_bound(in, n);          // (one rule for the host and for the device query: frame_grammar.hpp)
 }
 
 namespace {

@@ -172,4 +172,37 @@ CJ_HD int64_t lz4_frame_walk(const uint8_t* in, size_t n, Lz4Header& f, V&& visi
     return 0;
 }
 
+// Scratch for one LZ4 block: a stored block its size, a compressed block of c bytes min(block_max, 255 c + 64) — what it can decode to
+// at most (cj_lz4_frame_decompress_bound's rule: every sequence yields less than 255 bytes per input byte).  The block is decoded with
+// that capacity instead of block_max: every capacity test of the safe decoder (room for a sequence's literals + 12, for a match + 5)
+// then still passes wherever it passes with block_max, because the output before any sequence lies below 255 times the input before
+// it and the rest of the room is at least 255 times what is left of the input, plus 64 — so the verdict and bytes are the same.
+CJ_HD inline uint64_t lz4_slot_bytes(uint32_t word, uint32_t block_max) {
+    const uint64_t c = word & 0x7FFFFFFFu;
+    if (word & 0x80000000u) return c;
+    return 255ull * c + 64ull < block_max ? 255ull * c + 64ull : block_max;
+}
+
+// cj_lz4_frame_decompress_bound: what the blocks can produce at most — a stored block its own size, a compressed block its slot
+// (above) — or the first error of the headers.  The announced content size is attacker-controlled: it bounds the result from
+// above, it never raises it (a 19-byte frame announcing 2^46 bytes used to make the caller allocate that; values >= 2^63
+// turned into bogus negative "error codes").  Host (frame.hip) and device (batch_sizes.hip: one lane per frame).
+CJ_HD inline int64_t lz4_frame_bound(const uint8_t* in, size_t n) {
+    Lz4Header f;
+    uint64_t total = 0;
+    const int64_t err = lz4_frame_walk(in, n, f, [&](uint64_t, uint32_t w) { total += lz4_slot_bytes(w, f.block_max); return true; });
+    if (err) return err;
+    if (f.skippable) return 0;
+    if (f.late_err) return f.late_err;
+    if (f.csize && f.content_size < total) return (int64_t)f.content_size;
+    return (int64_t)total;
+}
+
+// cj_snappy_frame_decompress_len: the decoded length from the chunk headers alone, or the first header-level error
+CJ_HD inline int64_t snappy_frame_len(const uint8_t* in, size_t n) {
+    uint64_t total = 0;
+    const int64_t err = snappy_frame_walk(in, n, [](const SnapPiece&) {}, &total);
+    return err ? err : (int64_t)total;
+}
+
 }  // namespace cj

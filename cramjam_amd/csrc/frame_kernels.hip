@@ -62,17 +62,7 @@ __device__ __forceinline__ void wave_copy64(uint8_t* dst, const uint8_t* src, ui
 
 __host__ __device__ inline uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
 
-// Scratch for one LZ4 block: a stored block its size, a compressed block of c bytes min(block_max, 255 c + 64) — what it can decode to
-// at most (cj_lz4_frame_decompress_bound's rule: every sequence yields less than 255 bytes per input byte).  The block is decoded with
-// that capacity instead of block_max: every capacity test of the safe decoder (room for a sequence's literals + 12, for a match + 5)
-// then still passes wherever it passes with block_max, because the output before any sequence lies below 255 times the input before
-// it and the rest of the room is at least 255 times what is left of the input, plus 64 — so the verdict and bytes are the same.
-__host__ __device__ inline uint64_t lz4_slot_bytes(uint32_t word, uint32_t block_max) {
-    const uint64_t c = word & 0x7FFFFFFFu;
-    if (word & 0x80000000u) return c;
-    return 255ull * c + 64ull < block_max ? 255ull * c + 64ull : block_max;
-}
-
+// (lz4_slot_bytes, the scratch of one LZ4 block: frame_grammar.hpp)
 __global__ __launch_bounds__(kBlockThreads) void fb_walk_kernel(int fmt, uint32_t n, const uint8_t* in_base, const uint64_t* in_off,
                                                                 const uint64_t* in_len, uint64_t* cnt, FbFrame* fr, FbRows r,
                                                                 ChainJob* jobs) {

@@ -262,6 +262,45 @@ CJ_API int cj_frame_batch_host(cj_engine* e, cj_format fmt, cj_op op, uint32_t f
                                const uint8_t* const* in_ptrs, const size_t* in_lens,
                                uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 
+/* Decoded-size queries: what a caller needs to lay out out_off / out_cap before it can submit cj_batch_device / cj_frame_batch_device,
+ * for chunks that may live in device memory only.  result[i] = the decoded size of chunk i (>= 0) or CJ_E_* (< 0); nothing but result
+ * is written.  Addressing, alignment (the 16-byte granules of a chunk's first and last byte may be read whole), stream and thread
+ * safety are cj_batch_device's.  The _device calls are ENQUEUE-ONLY: no wait on the stream, no read-back, no engine scratch, no lock
+ * — a query may sit in front of a decode on the same stream (compute the capacities from result on the device), and it does not wait
+ * behind a frame batch that runs on another stream of the same engine.  The _host calls are pack -> H2D -> the device path -> D2H of
+ * the results, synchronous.  n == 0 succeeds; a null pointer with n > 0, an unknown codec / fmt, or a flag bit other than
+ * CJ_FLAG_LZ4_SIZE_PREFIX (frames: any bit) is CJ_E_BAD_ARG.  e == NULL: the default engine of device 0; without a usable device
+ * CJ_E_NO_DEVICE.
+ *   Snappy raw          cj_snappy_raw_decompress_len of the chunk: the announced length or its header error, 0 for an empty chunk.
+ *                       Header only (the reference's decompress_raw_len): a later decode may still fail.
+ *   LZ4 block, CJ_FLAG_LZ4_SIZE_PREFIX   the u32 prefix, by the decoder's rules that need no capacity: CJ_E_NO_PREFIX, CJ_E_NEG_PREFIX,
+ *                       CJ_E_PREFIX_TOO_BIG (and CJ_E_CORRUPT for more than 0x7FFFFFF0 bytes behind the prefix).  Header only.
+ *   LZ4 block, raw      the WALK: the length S the safe decoder produces when output room never runs out (LZ4_decompress_safe with a
+ *                       capacity of 255 * in_len + 64, the rule cj_lz4_frame_decompress_bound relies on).  CJ_E_CORRUPT where that
+ *                       decode fails: malformed length fields, input not consumed exactly, offset 0 (this library rejects it), an
+ *                       offset beyond the bytes produced so far, an empty chunk, in_len > 0x7FFFFFF0.  CJ_E_PREFIX_TOO_BIG when
+ *                       S > 0x7E000000: no capacity the decoder accepts can hold it.  The match bytes are not looked at: S is exact.
+ *                       Contract with cj_batch_device (decompress, no prefix): with out_cap[i] >= S + CJ_LZ4_SIZE_SLACK every chunk
+ *                       the query accepted decodes to exactly S bytes; with out_cap[i] == S it does whenever the block obeys LZ4's
+ *                       end-of-block rules (the last sequence is literals only, the last match ends 5 bytes before the end and starts
+ *                       12 before it: every encoder's output does).  The slack is not a measurement: the decoder asks a non-final
+ *                       sequence for cap - op >= literals + 12 and, behind its literals, for cap - op >= match + 5; with
+ *                       cap = S + 12 both hold for every sequence of a stream whose total is S.
+ *                       Chunks of up to 64 KiB of data are the fast case (one lane each); a longer chunk takes one wavefront.
+ *   LZ4 frame           cj_lz4_frame_decompress_bound of the frame: an upper bound by that function's rules, 0 for a skippable frame
+ *   Snappy framed       cj_snappy_frame_decompress_len of the stream */
+#define CJ_LZ4_SIZE_SLACK 12
+CJ_API int cj_batch_sizes_device(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks,
+                                 const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                 int64_t* result, void* hip_stream);
+CJ_API int cj_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks,
+                               const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+CJ_API int cj_frame_batch_sizes_device(cj_engine* e, cj_format fmt, uint32_t flags, size_t n_frames,
+                                       const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                       int64_t* result, void* hip_stream);
+CJ_API int cj_frame_batch_sizes_host(cj_engine* e, cj_format fmt, uint32_t flags, size_t n_frames,
+                                     const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+
 /* Thin device-memory helpers so C / ctypes callers need no HIP binding of their own. */
 CJ_API void* cj_device_alloc(cj_engine* e, size_t bytes);
 CJ_API void  cj_device_free(cj_engine* e, void* p);
