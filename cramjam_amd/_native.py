@@ -19,6 +19,18 @@ FLAG_CHUNKS_LE_32K = 0x40          # decompress: a promise that no chunk is larg
 FLAG_CHUNKS_LE_16K = 0x80
 FLAG_BIG_CHUNKS = 0x800            # decompress: reserve record areas for chunks of 64 KiB .. 256 KiB (cramjam_hip.h)
 E_NO_DEVICE = -100
+E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
+
+
+class BloscParams(C.Structure):
+    """cj_blosc_params"""
+    _fields_ = [("typesize", C.c_uint32), ("filter", C.c_uint32), ("clevel", C.c_int32), ("codec", C.c_uint32), ("blocksize", C.c_uint32)]
+
+
+class BloscInfo(C.Structure):
+    """cj_blosc_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("version", "versionlz", "flags", "typesize", "nbytes", "blocksize", "cbytes", "nblocks")]
+
 
 _vp, _sz, _i64, _u32, _int = C.c_void_p, C.c_size_t, C.c_int64, C.c_uint32, C.c_int
 
@@ -61,6 +73,14 @@ SYMBOLS = {
     "cj_frame_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_frame_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "cj_blosc_chunk_max_compressed_len": (_sz, [_sz]),
+    "cj_blosc_chunk_info": (_i64, [_vp, _sz, _vp]),
+    "cj_blosc_chunk_decompress": (_i64, [_vp, _sz, _vp, _sz]),
+    "cj_blosc_chunk_compress": (_i64, [_vp, _sz, _vp, _sz, _vp]),
+    "cj_blosc_batch_device": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp]),
+    "cj_blosc_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_blosc_chunk_sizes_device": (_int, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_blosc_chunk_sizes_host": (_int, [_vp, _u32, _sz, _vp, _vp, _vp]),
     "cj_device_alloc": (_vp, [_vp, _sz]),
     "cj_device_free": (None, [_vp, _vp]),
     "cj_memcpy_h2d": (_int, [_vp, _vp, _vp, _sz]),
@@ -79,6 +99,7 @@ BENCH_SYMBOLS = {
     "cj_bench_compare": (_int, [_vp, _vp, _vp, C.c_uint64, _u32, C.c_uint64, _u32, _vp, _vp]),
     "cj_debug_big_scratch_bytes": (C.c_uint64, [_vp]),
     "cj_debug_xxh32_device": (_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
 }
 
 _lib = None
@@ -182,21 +203,25 @@ class Engine:
         check(lib().cj_frame_batch_device(self.h, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off,
                                           out_cap, result, stream))
 
-    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host"):
+    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host", params=None):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
         Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
         fn: "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
         from . import _cramjam                      # the CPython host layer: the engine scatters straight into the bytes objects
         try:
+            if params is not None:                  # cj_blosc_batch_host: the bytes of a cj_blosc_params (b"" = decompress)
+                return _cramjam.batch_host(self.h.value or 0, 0, int(op), int(flags), inputs, out_caps, _batch_host_addr("cj_blosc_batch_host"), params)
             return _cramjam.batch_host(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, _batch_host_addr(fn))
         except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
             raise EngineError(_with_hip_error(ex)) from None
 
-    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host"):
+    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host", params=None):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
         from . import _cramjam
         try:
+            if params is not None:
+                return _cramjam.batch_host_into(self.h.value or 0, 0, int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr("cj_blosc_batch_host"), params)
             return _cramjam.batch_host_into(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr(fn))
         except RuntimeError as ex:
             raise EngineError(_with_hip_error(ex)) from None

@@ -16,7 +16,7 @@ def _engine(device):
 _BLOCKS, _FRAMES = "cj_batch_host", "cj_frame_batch_host"      # the native call: raw blocks, or framed streams (codec is a FORMAT_*)
 
 
-def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS):
+def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS, params=None):
     """results + memoryviews into `out` (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output byte"""
     devices = list(devices) if devices is not None else [0]
     n = len(inputs)
@@ -25,13 +25,13 @@ def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS):
         offsets.append(run); run += int(c)
     mv = memoryview(out).cast("B")
     if len(devices) == 1:
-        res = _engine(devices[0]).batch_host_into(codec, op, flags, inputs, out_caps, out, offsets, fn)
+        res = _engine(devices[0]).batch_host_into(codec, op, flags, inputs, out_caps, out, offsets, fn, params)
     else:
         shards = [list(range(g, n, len(devices))) for g in range(len(devices))]
 
         def work(g):
             idx = shards[g]
-            return _engine(devices[g]).batch_host_into(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], out, [offsets[i] for i in idx], fn)
+            return _engine(devices[g]).batch_host_into(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], out, [offsets[i] for i in idx], fn, params)
         with ThreadPoolExecutor(len(devices)) as ex:
             parts = list(ex.map(work, range(len(devices))))
         res = [None] * n
@@ -41,18 +41,19 @@ def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS):
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
 
 
-def _run(codec, op, flags, inputs, out_caps, devices, out=None, fn=_BLOCKS):
+def _run(codec, op, flags, inputs, out_caps, devices, out=None, fn=_BLOCKS, params=None):
+    """params: the bytes of a cj_blosc_params — the batch is one of Blosc chunks (cj_blosc_batch_host; b"" = decompress)"""
     if out is not None:
-        return _run_into(codec, op, flags, inputs, out_caps, devices, out, fn)
+        return _run_into(codec, op, flags, inputs, out_caps, devices, out, fn, params)
     devices = list(devices) if devices is not None else [0]
     n = len(inputs)
     if len(devices) == 1:
-        return _engine(devices[0]).batch_host(codec, op, flags, inputs, out_caps, fn)
+        return _engine(devices[0]).batch_host(codec, op, flags, inputs, out_caps, fn, params)
     shards = [list(range(g, n, len(devices))) for g in range(len(devices))]   # chunk i -> gpu i mod G
 
     def work(g):
         idx = shards[g]
-        return _engine(devices[g]).batch_host(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], fn)
+        return _engine(devices[g]).batch_host(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], fn, params)
     with ThreadPoolExecutor(len(devices)) as ex:
         parts = list(ex.map(work, range(len(devices))))
     res, outs = [None] * n, [None] * n
@@ -436,7 +437,7 @@ def snappy_framed_sizes_device(inp, in_off, in_len, result=None, device=None, st
     return _device_sizes(N.FORMAT_SNAPPY_FRAMED, 0, inp, in_off, in_len, result, device, stream, sync, True)
 
 
-def _host_sizes(what, flags, buffers, devices, frames=False):
+def _host_sizes(what, flags, buffers, devices, frames=False, blosc=False):
     """sharded like _run: buffer i -> engine i mod G"""
     import numpy as np
     devices = list(devices) if devices is not None else [0]
@@ -450,7 +451,10 @@ def _host_sizes(what, flags, buffers, devices, frames=False):
         ptrs = (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
         lens = (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
         res = np.empty(k, np.int64)
-        N.check(fn(_engine(devices[g]).h, what, flags, k, ptrs, lens, res.ctypes.data))
+        if blosc:
+            N.check(N.lib().cj_blosc_chunk_sizes_host(_engine(devices[g]).h, flags, k, ptrs, lens, res.ctypes.data))
+        else:
+            N.check(fn(_engine(devices[g]).h, what, flags, k, ptrs, lens, res.ctypes.data))
         return idx, res
     if len(devices) == 1:
         return [int(x) for x in work(0)[1]]
@@ -478,3 +482,78 @@ def lz4_frame_bounds(frames, devices=None):
 
 def snappy_framed_sizes(streams, devices=None):
     return _host_sizes(N.FORMAT_SNAPPY_FRAMED, 0, streams, devices, True)
+
+
+# ---- Blosc chunks (cj_blosc_batch_* / cj_blosc_chunk_sizes_*): LZ4 streams behind shuffle / bitshuffle -----------------------------
+# One Blosc1-format chunk per entry (what Zarr / numcodecs, PyTables and bcolz store; cramjam_amd.blosc2 is the single-chunk case).
+# result[i] = nbytes (decompress) / the chunk's size (compress) or a negative CJ_E_* code: -30 a malformed chunk, -31 one this
+# library does not read (another compressor format, C-Blosc2's extended header), -7 a bad LZ4 stream, -6 / -2 a capacity too small.
+def _blosc_params(typesize, filter, clevel, codec, blocksize):
+    from . import blosc2
+    return bytes(blosc2._params(typesize, clevel, filter, codec, blocksize))
+
+
+def _chunk_nbytes(c):
+    """nbytes of a chunk on the host from its header alone, 0 for one that will be refused"""
+    info = N.BloscInfo()
+    return info.nbytes if N.lib().cj_blosc_chunk_info(*_addr_len(c), _C.byref(info)) == 0 else 0
+
+
+def blosc_decompress_chunks(chunks, devices=None, out=None):
+    """decode many Blosc chunks; returns (results, outputs) as lz4_decompress_blocks.  The capacities are the chunks' own nbytes
+    (read on the host from their headers); out: ONE writable buffer of at least their sum, the outputs are then views into it."""
+    return _run(0, N.OP_DECOMPRESS, 0, chunks, [_chunk_nbytes(c) for c in chunks], devices, out, params=b"")
+
+
+def blosc_compress_chunks(buffers, typesize, filter=1, clevel=5, codec=1, blocksize=0, devices=None, out=None):
+    """one Blosc chunk per buffer: LZ4 streams behind `filter` (0 none, 1 shuffle, 2 bitshuffle; cramjam_amd.blosc2.Filter) over
+    elements of `typesize` bytes.  out has to hold sum(len(buffer) + 32) bytes."""
+    caps = [memoryview(b).nbytes + 32 for b in buffers]
+    return _run(0, N.OP_COMPRESS, 0, buffers, caps, devices, out, params=_blosc_params(typesize, filter, clevel, codec, blocksize))
+
+
+def blosc_chunk_sizes(chunks, devices=None):
+    """nbytes of many Blosc chunks held on the host (list of ints; negative = the header's CJ_E_* code)"""
+    return _host_sizes(0, 0, chunks, devices, blosc=True)
+
+
+def _blosc_device(op, params, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync):
+    call = _DeviceCall(stream, sync)
+    try:
+        vin, vout = call.buffer(inp), call.buffer(out)
+        eng = call.engine(device, vin, vout)
+        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
+        p_out_off, p_out_cap = call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap")
+        p_res = call.result(result)
+        N.check(N.lib().cj_blosc_batch_device(eng.h, op, vin.ptr, p_in_off, p_in_len, vout.ptr, p_out_off, p_out_cap, p_res, call.n,
+                                              _C.byref(params) if params is not None else None, 0, stream))
+        return call.finish(p_res, result)
+    finally:
+        call.close()
+
+
+def blosc_decompress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of Blosc chunks (arguments as lz4_decompress_frames_device; the call waits for the stream once)."""
+    return _blosc_device(N.OP_DECOMPRESS, None, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def blosc_compress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, typesize, filter=1, clevel=5, codec=1, blocksize=0,
+                                 result=None, device=None, stream=None, sync=True):
+    """One Blosc chunk per device-resident buffer; out_cap[i] >= in_len[i] + 32 always suffices."""
+    from . import blosc2
+    return _blosc_device(N.OP_COMPRESS, blosc2._params(typesize, clevel, filter, codec, blocksize), inp, in_off, in_len, out, out_off, out_cap,
+                         result, device, stream, sync)
+
+
+def blosc_chunk_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
+    """nbytes of every chunk of a device-resident batch after the header checks, or their error; enqueue-only like lz4_block_sizes_device"""
+    call = _DeviceCall(stream, sync)
+    try:
+        vin = call.buffer(inp)
+        eng = call.engine(device, vin)
+        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
+        p_res = call.result(result)
+        N.check(N.lib().cj_blosc_chunk_sizes_device(eng.h, 0, call.n, vin.ptr, p_in_off, p_in_len, p_res, stream))
+        return call.finish(p_res, result)
+    finally:
+        call.close()

@@ -1,0 +1,138 @@
+"""Blosc chunks on the MI355X: the chunk API of the reference's `blosc2` module (src/blosc2.rs:133-210, :592-680, :702-706) —
+`compress_chunk`, `compress_chunk_into`, `decompress_chunk`, `decompress_chunk_into`, `max_compressed_len` and the enums `Filter`,
+`CLevel`, `Codec` — as the single-chunk case of the chunk batches (cramjam_amd.batch.blosc_*; C-ABI cj_blosc_chunk_*).
+
+What is read and written: Blosc1-format chunks (16-byte header, format version 2) whose streams are LZ4, behind no filter, the
+byte shuffle or the bitshuffle.  Refused with an error (never a wrong result): the other compressor formats (BloscLZ, Zlib, Zstd,
+Snappy; on compress `Codec.BloscLz / ZLIB / ZSTD`), `Filter.Delta / TruncPrec`, and C-Blosc2's extended 32-byte header.  Not here:
+`SChunk`, the `compress` / `decompress` frame container, `Compressor` / `Decompressor`, `set_nthreads`.
+Deviations: `codec=None` means LZ4 (the reference's default is BloscLZ; every Blosc reader decodes either); `clevel` 1-9 select the
+one matcher of the engine, `clevel=0` stores; `typesize=None` is the itemsize of the buffer handed in (1 for `bytes`) as the
+reference's `Chunk.compress` does — what its plain `compress_chunk` does with None lies in a crate that was not at hand."""
+import enum as _enum
+
+from . import _native as _N
+
+__all__ = ["compress_chunk", "compress_chunk_into", "decompress_chunk", "decompress_chunk_into", "max_compressed_len", "Filter", "CLevel", "Codec"]
+
+
+class Filter(_enum.IntEnum):
+    NoFilter = 0
+    Shuffle = 1
+    BitShuffle = 2
+    Delta = 3
+    TruncPrec = 4
+    LastFilter = 5
+    LastRegisteredFilter = 6
+
+
+class CLevel(_enum.IntEnum):
+    Zero = 0
+    One = 1
+    Two = 2
+    Three = 3
+    Four = 4
+    Five = 5
+    Six = 6
+    Seven = 7
+    Eight = 8
+    Nine = 9
+
+
+class Codec(_enum.IntEnum):
+    BloscLz = 0
+    LZ4 = 1
+    LZ4HC = 2
+    ZLIB = 3
+    ZSTD = 4
+    LastCodec = 5
+    LastRegisteredCodec = 6
+
+
+def _errors():
+    from . import _cramjam
+    return _cramjam.CompressionError, _cramjam.DecompressionError
+
+
+def _params(typesize, clevel, filter, codec, blocksize=0):
+    typesize = 1 if typesize is None else int(typesize)
+    if not 1 <= typesize <= 255:
+        raise ValueError("blosc2: typesize must be 1 .. 255, got %d" % typesize)
+    clevel = 5 if clevel is None else int(clevel)
+    if not 0 <= clevel <= 9:
+        raise ValueError("blosc2: clevel must be 0 .. 9, got %d" % clevel)
+    return _N.BloscParams(typesize, int(Filter.Shuffle if filter is None else filter), clevel, int(Codec.LZ4 if codec is None else codec), int(blocksize))
+
+
+def _view(data):
+    """(contiguous byte view, itemsize of what was handed in)"""
+    mv = memoryview(data)
+    return (mv if mv.ndim == 1 and mv.format == "B" and mv.contiguous else mv.cast("B")), mv.itemsize
+
+
+def _raise(exc, rc):
+    raise exc("blosc2: %s" % _N.strerror(rc))
+
+
+def _one(op, data, cap, out, params, exc):
+    from .batch import _engine
+    try:
+        eng = _engine(0)
+        if out is None:
+            res, outs = eng.batch_host(0, op, 0, [data], [cap], params=params)
+        else:
+            res, outs = eng.batch_host_into(0, op, 0, [data], [cap], out, None, params=params), None
+    except _N.EngineError as ex:
+        raise RuntimeError(str(ex)) from None
+    if res[0] < 0:
+        _raise(exc, res[0])
+    return res[0], outs
+
+
+def max_compressed_len(len_bytes):
+    """upper bound of the chunk of `len_bytes` bytes: len_bytes + 32"""
+    return _N.lib().cj_blosc_chunk_max_compressed_len(int(len_bytes))
+
+
+def compress_chunk(data, typesize=None, clevel=None, filter=None, codec=None):
+    """Blosc compression, chunk format -> cramjam.Buffer"""
+    from . import _cramjam
+    mv, item = _view(data)
+    p = _params(item if typesize is None else typesize, clevel, filter, codec)
+    _, outs = _one(_N.OP_COMPRESS, mv, mv.nbytes + 32, None, bytes(p), _errors()[0])
+    return _cramjam.Buffer(outs[0])
+
+
+def compress_chunk_into(input, output, typesize=None, clevel=None, filter=None, codec=None):
+    """Compress a chunk into `output`; returns the chunk's size"""
+    mv, item = _view(input)
+    out = memoryview(output).cast("B")
+    p = _params(item if typesize is None else typesize, clevel, filter, codec)
+    return _one(_N.OP_COMPRESS, mv, out.nbytes, out, bytes(p), _errors()[0])[0]
+
+
+def _nbytes(mv, exc):
+    import ctypes as C
+    import numpy as np
+    info = _N.BloscInfo()
+    a = np.frombuffer(mv, dtype=np.uint8)
+    rc = _N.lib().cj_blosc_chunk_info(a.ctypes.data if a.size else None, a.size, C.byref(info))
+    if rc != 0:
+        _raise(exc, rc)
+    return info.nbytes
+
+
+def decompress_chunk(data, output_len=None):
+    """Blosc chunk decompression -> cramjam.Buffer (output_len is accepted and ignored, as in the reference: the chunk names its size)"""
+    from . import _cramjam
+    mv, _ = _view(data)
+    exc = _errors()[1]
+    _, outs = _one(_N.OP_DECOMPRESS, mv, _nbytes(mv, exc), None, b"", exc)
+    return _cramjam.Buffer(outs[0])
+
+
+def decompress_chunk_into(input, output):
+    """Decompress a chunk into `output`; returns nbytes"""
+    mv, _ = _view(input)
+    out = memoryview(output).cast("B")
+    return _one(_N.OP_DECOMPRESS, mv, out.nbytes, out, b"", _errors()[1])[0]

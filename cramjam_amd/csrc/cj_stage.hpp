@@ -54,6 +54,14 @@ void launch_fb_pieces(size_t n, const FbFrame* fr, const uint64_t* in_off, const
 void launch_fb_assemble(int fmt, size_t n, const FbFrame* fr, FbRows r, const uint32_t* sums, const uint8_t* in_base, const uint64_t* in_len, const uint8_t* scratch, uint64_t stride, uint8_t* out_base, const uint64_t* out_off,
                         const uint64_t* out_cap, int64_t* result, hipStream_t s);
 
+// the frame batch's scratch (e->d_fb, e->h_fb; Blosc chunk batches use it too) is reused by the next call: it waits for this one on the
+// device; growing it waits on the host
+inline int fb_reserve(cj_engine* e, size_t dev_bytes, size_t host_bytes) {
+    if ((dev_bytes > e->d_fb.cap || host_bytes > e->h_fb.cap) && e->fb_free) HIP_TRY(hipEventSynchronize(e->fb_free), CJ_E_NO_DEVICE);
+    if (!e->d_fb.reserve(dev_bytes) || !e->h_fb.reserve(host_bytes)) return CJ_E_OOM;
+    return 0;
+}
+
 // Compress in[0, n), cut into pieces of `piece` bytes, as ONE batch into e->d_out (`stride` bytes apart), the input staged at e->d_in + H
 // behind the last H bytes before it (hist: linked LZ4 blocks, kFlagLinkedEnc — piece 0 may refer to those H bytes, every other piece to
 // the piece before it).  Queues the results' copy into res and, with `first`, the stitch plan kernel (first[i] = literal length of piece

@@ -414,6 +414,8 @@ const char* cj_strerror(int64_t code) {
     case CJ_E_LZ4F_CONTENT_SIZE: return "LZ4 error: ERROR_frameSize_wrong";
     case CJ_E_LZ4F_INCOMPLETE: return "Finish runned before read end of compressed stream";
     case CJ_E_LZ4F_DECOMPRESS: return "LZ4 error: ERROR_decompressionFailed";
+    case CJ_E_BLOSC_HEADER: return "blosc: corrupt chunk (invalid header, block table or stream length)";
+    case CJ_E_BLOSC_UNSUPPORTED: return "blosc: unsupported chunk (only format version 2 with LZ4 streams; shuffle, bitshuffle or no filter)";
     case CJ_E_NO_DEVICE: return "cramjam_hip: no usable HIP device (no CPU fallback exists)";
     case CJ_E_BAD_ARG: return "cramjam_hip: bad argument";
     case CJ_E_OOM: return "cramjam_hip: out of memory";

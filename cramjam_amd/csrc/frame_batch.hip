@@ -14,13 +14,6 @@ constexpr uint64_t kPiece = 65536;
 
 inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 
-// the frame batch's scratch (e->d_fb, e->h_fb) is reused by the next call: it waits for this one on the device; growing it waits on the host
-int fb_reserve(cj_engine* e, size_t dev_bytes, size_t host_bytes) {
-    if ((dev_bytes > e->d_fb.cap || host_bytes > e->h_fb.cap) && e->fb_free) HIP_TRY(hipEventSynchronize(e->fb_free), CJ_E_NO_DEVICE);
-    if (!e->d_fb.reserve(dev_bytes) || !e->h_fb.reserve(host_bytes)) return CJ_E_OOM;
-    return 0;
-}
-
 int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     // (the lock is held across the one wait below: frame batches on one engine run one after another, and a call waits for everything
@@ -30,7 +23,7 @@ int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* 
     if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
     else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);          // the previous user of the scratch
     const size_t tab = up16(n * sizeof(cj::FbFrame));
-    int rc = fb_reserve(e, std::max(16 * n, tab), tab + 16 * n);
+    int rc = cj::fb_reserve(e, std::max(16 * n, tab), tab + 16 * n);
     if (rc != 0) return rc;
     uint64_t* cnt = (uint64_t*)e->h_fb.p;                                         // read back: [2i] blocks, [2i + 1] scratch bytes / in_len
     cj::FbFrame* h_fr = reinterpret_cast<cj::FbFrame*>(e->h_fb.p + 16 * n);
@@ -57,7 +50,7 @@ int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* 
     if (!dec) slot = nb * stride;
     // d_fb: frames | chain jobs (decompress) / content sums (compress) | block rows | scratch
     const size_t o_side = tab, o_rows = o_side + up16(n * sizeof(cj::ChainJob)), o_scr = o_rows + cj::kFbRowWords * 8 * nb;
-    rc = fb_reserve(e, o_scr + slot + 16, tab + 16 * n);
+    rc = cj::fb_reserve(e, o_scr + slot + 16, tab + 16 * n);
     if (rc != 0) return rc;
     uint8_t* d = (uint8_t*)e->d_fb.p;
     cj::FbFrame* fr = reinterpret_cast<cj::FbFrame*>(d);

@@ -1338,9 +1338,29 @@ PyMethodDef snappy_methods[] = {
 // them, and the outputs are `bytes` objects the engine scatters INTO — the ctypes marshalling this replaces copied every
 // input and every output once more and spent 130 ms of a 160 ms call on 16 384 chunks in Python objects.
 typedef int (*batch_host_fn)(cj_engine*, cj_codec, cj_op, uint32_t, size_t, const uint8_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*);
+// ... and batches of Blosc chunks (cj_blosc_batch_host): `params` = the bytes of a cj_blosc_params (empty: decompress); codec is not used
+typedef int (*blosc_host_fn)(cj_engine*, cj_op, uint32_t, size_t, const uint8_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*, const cj_blosc_params*);
+struct BloscArg {
+    Py_buffer view = {};
+    bool given = false;
+    cj_blosc_params p = {};
+    ~BloscArg() { if (view.obj) PyBuffer_Release(&view); }
+    bool parse() {
+        given = view.obj != nullptr;
+        if (given && view.len != 0 && view.len != (Py_ssize_t)sizeof(cj_blosc_params)) { PyErr_SetString(PyExc_ValueError, "params must be the bytes of a cj_blosc_params"); return false; }
+        if (given && view.len) std::memcpy(&p, view.buf, sizeof p);
+        return true;
+    }
+    int call(unsigned long long fn_addr, cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
+             uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* res) const {
+        const blosc_host_fn f = fn_addr ? (blosc_host_fn)(uintptr_t)fn_addr : &cj_blosc_batch_host;
+        return f(e, op, flags, n, in_ptrs, in_lens, out_ptrs, out_caps, res, view.len ? &p : nullptr);
+    }
+};
 PyObject* root_batch_host(PyObject*, PyObject* args) {
     unsigned long long handle, fn_addr = 0; int codec, op; unsigned int flags; PyObject *inputs_o, *caps_o;
-    if (!PyArg_ParseTuple(args, "KiiIOO|K", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr)) return nullptr;
+    BloscArg blosc;
+    if (!PyArg_ParseTuple(args, "KiiIOO|Ky*", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr, &blosc.view) || !blosc.parse()) return nullptr;
     // (fn_addr: cj_batch_host of the library the engine handle came from — a tuning variant loaded through CJ_HIP_LIB; 0 = the one this module links)
     const batch_host_fn call = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
     PyObject* inputs = PySequence_Fast(inputs_o, "inputs must be a sequence of bytes-like objects");
@@ -1373,7 +1393,8 @@ PyObject* root_batch_host(PyObject*, PyObject* args) {
     int rc = 0;
     if (ok && n > 0) {
         Py_BEGIN_ALLOW_THREADS
-        rc = call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
+        rc = blosc.given ? blosc.call(fn_addr, (cj_engine*)(uintptr_t)handle, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data())
+                         : call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
         Py_END_ALLOW_THREADS
     }
     for (Py_ssize_t i = 0; i < got; i++) PyBuffer_Release(&views[(size_t)i]);
@@ -1409,7 +1430,8 @@ PyObject* root_batch_host(PyObject*, PyObject* args) {
 // of the caller's (chunk i at out[offsets[i] : offsets[i] + out_caps[i]], back to back when offsets is None) — no object per output
 PyObject* root_batch_host_into(PyObject*, PyObject* args) {
     unsigned long long handle, fn_addr = 0; int codec, op; unsigned int flags; PyObject *inputs_o, *caps_o, *out_o, *offs_o = Py_None;
-    if (!PyArg_ParseTuple(args, "KiiIOOO|OK", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &out_o, &offs_o, &fn_addr)) return nullptr;
+    BloscArg blosc;
+    if (!PyArg_ParseTuple(args, "KiiIOOO|OKy*", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &out_o, &offs_o, &fn_addr, &blosc.view) || !blosc.parse()) return nullptr;
     const batch_host_fn call = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
     Py_buffer ob;
     if (PyObject_GetBuffer(out_o, &ob, PyBUF_WRITABLE | PyBUF_C_CONTIGUOUS) != 0) return nullptr;
@@ -1443,7 +1465,8 @@ PyObject* root_batch_host_into(PyObject*, PyObject* args) {
     int rc = 0;
     if (ok && n > 0) {
         Py_BEGIN_ALLOW_THREADS
-        rc = call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
+        rc = blosc.given ? blosc.call(fn_addr, (cj_engine*)(uintptr_t)handle, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data())
+                         : call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
         Py_END_ALLOW_THREADS
     }
     for (Py_ssize_t i = 0; i < got; i++) PyBuffer_Release(&views[(size_t)i]);

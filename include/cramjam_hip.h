@@ -62,6 +62,8 @@ extern "C" {
 #define CJ_E_LZ4F_CONTENT_SIZE  (-25) /* LZ4F ERROR_frameSize_wrong */
 #define CJ_E_LZ4F_INCOMPLETE    (-26) /* lz4 crate Decoder::finish: "Finish runned before read end of compressed stream" */
 #define CJ_E_LZ4F_DECOMPRESS    (-27) /* LZ4F ERROR_decompressionFailed (malformed block) */
+#define CJ_E_BLOSC_HEADER       (-30) /* Blosc chunk: malformed header, block table or stream word (c-blosc returns -1) */
+#define CJ_E_BLOSC_UNSUPPORTED  (-31) /* Blosc chunk this library does not read or write: see "Blosc chunks" below */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -300,6 +302,60 @@ CJ_API int cj_frame_batch_sizes_device(cj_engine* e, cj_format fmt, uint32_t fla
                                        int64_t* result, void* hip_stream);
 CJ_API int cj_frame_batch_sizes_host(cj_engine* e, cj_format fmt, uint32_t flags, size_t n_frames,
                                      const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+
+/* =====================================================================================
+ * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706
+ * max_compressed_len): LZ4 streams behind a byte or bit transposition.  The transposition runs in its own kernels
+ * (blosc_filters.hip), the streams of ALL chunks of a call go through the batch engine as one batch.
+ *   READ     Blosc1-format chunks (c-blosc 1.x, format version 2, 16-byte header: what Zarr / numcodecs, PyTables and bcolz store,
+ *            and what C-Blosc2 also reads) whose compressor format is LZ4 (codecs lz4 and lz4hc), filters none / shuffle / bitshuffle,
+ *            typesize 1 .. 255, split and unsplit blocks, stored streams, memcpyed chunks (of any compressor format), the leftover block.
+ *   WRITTEN  the same format: blocks of 64 KiB x typesize split into typesize streams for typesize 2 .. 16 (else 64 KiB unsplit,
+ *            flag 0x10), every stream at most 64 KiB; a stream that does not shrink is stored, a chunk that would not be smaller than
+ *            nbytes + 16 (and every clevel 0 chunk) is memcpyed.  clevel 1 .. 9 select the one matcher of cj_batch_device.
+ *   REFUSED  CJ_E_BLOSC_UNSUPPORTED: a format version other than 2 — above all C-Blosc2's extended 32-byte header (version > 2, with its
+ *            filter pipeline: delta, truncated precision); nothing that writes such a chunk was at hand when this was built, so there is
+ *            no decoder guessed from memory — and the compressor formats BloscLZ, Snappy, Zlib, Zstd (on compress: any codec but
+ *            CJ_BLOSC_LZ4 / CJ_BLOSC_LZ4HC, any filter but the three above).
+ *            CJ_E_BLOSC_HEADER: a malformed container (short header, reserved flag, both shuffle bits, typesize 0, cbytes beyond the
+ *            bytes given, blocksize 0 or above nbytes, a block start or stream word outside the chunk).
+ *            CJ_E_CORRUPT: a stream that is not an LZ4 block of exactly its length.  CJ_E_OUT_TOO_SMALL: nbytes above the capacity.
+ *            A chunk refused for its header or its size writes nothing; one with a bad stream may have written inside its own slot.
+ * ===================================================================================== */
+typedef enum { CJ_BLOSC_NOFILTER = 0, CJ_BLOSC_SHUFFLE = 1, CJ_BLOSC_BITSHUFFLE = 2 } cj_blosc_filter;      /* the reference's Filter */
+typedef enum { CJ_BLOSC_BLOSCLZ = 0, CJ_BLOSC_LZ4 = 1, CJ_BLOSC_LZ4HC = 2, CJ_BLOSC_ZLIB = 3, CJ_BLOSC_ZSTD = 4 } cj_blosc_codec;   /* its Codec */
+typedef struct {
+    uint32_t typesize;    /* 1 .. 255 */
+    uint32_t filter;      /* cj_blosc_filter */
+    int32_t clevel;       /* 0 .. 9; 0 = memcpyed chunk */
+    uint32_t codec;       /* cj_blosc_codec: CJ_BLOSC_LZ4 or CJ_BLOSC_LZ4HC (the same streams) */
+    uint32_t blocksize;   /* 0 = default; a value above the default block size is cut to it */
+} cj_blosc_params;
+typedef struct { uint32_t version, versionlz, flags, typesize, nbytes, blocksize, cbytes, nblocks; } cj_blosc_info;
+
+/* src/blosc2.rs:702  upper bound of a chunk of n bytes: n + 32 (this library needs n + 16: the memcpyed chunk). No device. */
+CJ_API size_t cj_blosc_chunk_max_compressed_len(size_t n);
+/* the header of a chunk after its checks (0, CJ_E_BLOSC_HEADER or CJ_E_BLOSC_UNSUPPORTED; info is filled from the 16 bytes whenever
+ * there are that many).  No device. */
+CJ_API int64_t cj_blosc_chunk_info(const uint8_t* in, size_t n, cj_blosc_info* info);
+/* src/blosc2.rs:143,153  decompress_chunk / decompress_chunk_into: returns nbytes */
+CJ_API int64_t cj_blosc_chunk_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap);
+/* src/blosc2.rs:170,192  compress_chunk / compress_chunk_into: returns the chunk's size, CJ_E_COMPRESS_FAILED when cap is too small */
+CJ_API int64_t cj_blosc_chunk_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, const cj_blosc_params* params);
+/* Batches of chunks, device-resident or on the host: addressing, alignment, stream rules and the one wait of cj_frame_batch_device /
+ * _host (decompress reads back the chunks' stream counts, compress in_len).  result[i] = nbytes (decompress) / the chunk's size
+ * (compress) or CJ_E_*; nothing is written outside out_off[i] .. + out_cap[i] (a chunk with a header or size error writes nothing at all).  params:
+ * compress only (one set for the batch); flags is reserved (0).  e == NULL: the default engine of device 0. */
+CJ_API int cj_blosc_batch_device(cj_engine* e, cj_op op, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, size_t n_chunks,
+                                 const cj_blosc_params* params, uint32_t flags, void* hip_stream);
+CJ_API int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* const* in_ptrs, const size_t* in_lens,
+                               uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, const cj_blosc_params* params);
+/* result[i] = nbytes of chunk i after the header checks of cj_blosc_chunk_info, or their error.  Enqueue-only like cj_batch_sizes_device. */
+CJ_API int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
+                                       const uint64_t* in_len, int64_t* result, void* hip_stream);
+CJ_API int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n_chunks, const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                     int64_t* result);
 
 /* Thin device-memory helpers so C / ctypes callers need no HIP binding of their own. */
 CJ_API void* cj_device_alloc(cj_engine* e, size_t bytes);

@@ -31,6 +31,12 @@ CJ_API uint64_t cj_debug_big_scratch_bytes(cj_engine* e);
  * synchronous (tests hold it to the reference algorithm at every alignment) */
 CJ_API int cj_debug_xxh32_device(cj_engine* e, const uint8_t* d_base, const uint64_t* d_off, const uint64_t* d_len, uint32_t* d_out, size_t n);
 
+/* the Blosc filter kernels alone: n_blocks blocks of `bytes` bytes, `stride` apart, from d_src to d_dst (filter: a cj_blosc_filter, applied
+ * by a chunk's rules for that block size, or 3: the yardstick, one device-to-device hipMemcpyAsync of the same span; forward = 0: unfilter);
+ * synchronous.  ms (may be NULL): the time between two HIP events around the launch alone */
+CJ_API int cj_debug_blosc_filter(cj_engine* e, int forward, uint32_t filter, uint32_t typesize, const uint8_t* d_src, uint8_t* d_dst,
+                                 uint64_t bytes, uint64_t stride, size_t n_blocks, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
