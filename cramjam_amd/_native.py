@@ -133,16 +133,38 @@ def check(rc):
         raise EngineError("%s (%s)" % (strerror(rc), lib().cj_last_hip_error().decode()))
 
 
-def _with_hip_error(ex):
-    """the host module's message; the HIP error text of THIS library's thread-local slot when the call went through its entry point"""
-    msg = str(ex)
-    return msg if msg.endswith(")") else "%s (%s)" % (msg, lib().cj_last_hip_error().decode())
+def _with_hip_error(msg):
+    """the host module's message and the HIP error text behind it — from THIS library's thread-local slot: the module's calls go through
+    this library's entry points (_batch_host_addr), so the text lies here and not in the library the module links"""
+    return "%s (%s)" % (msg, lib().cj_last_hip_error().decode())
 
 
 def _batch_host_addr(name="cj_batch_host"):
     """address of cj_batch_host (or of cj_frame_batch_host, which has the same signature) in the library the engines of this process
     come from (CJ_HIP_LIB may name a tuning variant; the CPython module links the product library)"""
     return C.cast(getattr(lib(), name), C.c_void_p).value
+
+
+class Kind:
+    """One kind of batch: its four C symbols, and how `what` (a CODEC_* / FORMAT_*; Blosc chunks have none) and `params` (a BloscParams
+    or None) enter their argument lists.  i = (in_base, in_off, in_len) / (in_ptrs, in_lens); o = (out_base, out_off, out_cap)."""
+
+    def __init__(self, host, device, sizes_host, sizes_device, blosc=False):
+        self.host, self.device, self.sizes_host, self.sizes_device, self.blosc = host, device, sizes_host, sizes_device, blosc
+
+    def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
+        if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)
+            return (h, op) + i + o + (result, n, C.byref(params) if params is not None else None, flags, stream)
+        return (h, what, op, flags, n) + i + o + (result, stream)
+
+    def sizes_args(self, h, what, flags, n, *rest):
+        """rest = i + (result,) [+ (stream,)]"""
+        return ((h, flags, n) if self.blosc else (h, what, flags, n)) + rest
+
+
+BLOCKS = Kind("cj_batch_host", "cj_batch_device", "cj_batch_sizes_host", "cj_batch_sizes_device")
+FRAMES = Kind("cj_frame_batch_host", "cj_frame_batch_device", "cj_frame_batch_sizes_host", "cj_frame_batch_sizes_device")
+BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
 
 
 class Engine:
@@ -203,26 +225,23 @@ class Engine:
         check(lib().cj_frame_batch_device(self.h, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off,
                                           out_cap, result, stream))
 
+    def _host(self, entry, codec, op, flags, args, fn, params):
+        """entry: batch_host or batch_host_into of the CPython host layer (the engine scatters straight into the bytes objects / the buffer).
+        params: the bytes of a cj_blosc_params (b"" = decompress) — the batch is one of Blosc chunks, codec is not used"""
+        from . import _cramjam
+        tail = (_batch_host_addr(fn),) if params is None else (_batch_host_addr(BLOSC.host), params)
+        try:
+            return getattr(_cramjam, entry)(self.h.value or 0, 0 if params is not None else int(codec), int(op), int(flags), *args, *tail)
+        except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
+            raise EngineError(_with_hip_error(str(ex))) from None
+
     def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host", params=None):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
         Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
         fn: "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
-        from . import _cramjam                      # the CPython host layer: the engine scatters straight into the bytes objects
-        try:
-            if params is not None:                  # cj_blosc_batch_host: the bytes of a cj_blosc_params (b"" = decompress)
-                return _cramjam.batch_host(self.h.value or 0, 0, int(op), int(flags), inputs, out_caps, _batch_host_addr("cj_blosc_batch_host"), params)
-            return _cramjam.batch_host(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, _batch_host_addr(fn))
-        except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
-            raise EngineError(_with_hip_error(ex)) from None
+        return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params)
 
     def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host", params=None):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
-        from . import _cramjam
-        try:
-            if params is not None:
-                return _cramjam.batch_host_into(self.h.value or 0, 0, int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr("cj_blosc_batch_host"), params)
-            return _cramjam.batch_host_into(self.h.value or 0, int(codec), int(op), int(flags), inputs, out_caps, out, offsets, _batch_host_addr(fn))
-        except RuntimeError as ex:
-            raise EngineError(_with_hip_error(ex)) from None
-
+        return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params)

@@ -13,54 +13,41 @@ def _engine(device):
     return _engines[device]
 
 
-_BLOCKS, _FRAMES = "cj_batch_host", "cj_frame_batch_host"      # the native call: raw blocks, or framed streams (codec is a FORMAT_*)
-
-
-def _run_into(codec, op, flags, inputs, out_caps, devices, out, fn=_BLOCKS, params=None):
-    """results + memoryviews into `out` (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output byte"""
+def _shard(devices, n, work):
+    """index i -> devices[i mod G], one thread per device.  work(device, idx) -> a tuple of lists with one entry per index of idx each;
+    returns the same tuple of lists for all n indices, in the caller's order"""
     devices = list(devices) if devices is not None else [0]
+    G = len(devices)
+    if G == 1:
+        return work(devices[0], range(n))
+    shards = [range(g, n, G) for g in range(G)]
+    with ThreadPoolExecutor(G) as ex:
+        parts = list(ex.map(work, devices, shards))
+    cols = tuple([None] * n for _ in parts[0])
+    for idx, part in zip(shards, parts):
+        for col, p in zip(cols, part):
+            for k, i in enumerate(idx):
+                col[i] = p[k]
+    return cols
+
+
+def _pick(seq, idx):
+    return seq if len(idx) == len(seq) else [seq[i] for i in idx]
+
+
+def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None):
+    """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*) or N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress).
+    out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
+    if out is None:
+        return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind.host, params))
     offsets, run = [], 0
     for c in out_caps:
         offsets.append(run); run += int(c)
     mv = memoryview(out).cast("B")
-    if len(devices) == 1:
-        res = _engine(devices[0]).batch_host_into(codec, op, flags, inputs, out_caps, out, offsets, fn, params)
-    else:
-        shards = [list(range(g, n, len(devices))) for g in range(len(devices))]
-
-        def work(g):
-            idx = shards[g]
-            return _engine(devices[g]).batch_host_into(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], out, [offsets[i] for i in idx], fn, params)
-        with ThreadPoolExecutor(len(devices)) as ex:
-            parts = list(ex.map(work, range(len(devices))))
-        res = [None] * n
-        for g, r in enumerate(parts):
-            for k, i in enumerate(shards[g]):
-                res[i] = r[k]
+    res, = _shard(devices, n, lambda dev, idx: (_engine(dev).batch_host_into(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), out,
+                                                                             _pick(offsets, idx), kind.host, params),))
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
-
-
-def _run(codec, op, flags, inputs, out_caps, devices, out=None, fn=_BLOCKS, params=None):
-    """params: the bytes of a cj_blosc_params — the batch is one of Blosc chunks (cj_blosc_batch_host; b"" = decompress)"""
-    if out is not None:
-        return _run_into(codec, op, flags, inputs, out_caps, devices, out, fn, params)
-    devices = list(devices) if devices is not None else [0]
-    n = len(inputs)
-    if len(devices) == 1:
-        return _engine(devices[0]).batch_host(codec, op, flags, inputs, out_caps, fn, params)
-    shards = [list(range(g, n, len(devices))) for g in range(len(devices))]   # chunk i -> gpu i mod G
-
-    def work(g):
-        idx = shards[g]
-        return _engine(devices[g]).batch_host(codec, op, flags, [inputs[i] for i in idx], [out_caps[i] for i in idx], fn, params)
-    with ThreadPoolExecutor(len(devices)) as ex:
-        parts = list(ex.map(work, range(len(devices))))
-    res, outs = [None] * n, [None] * n
-    for g, (r, o) in enumerate(parts):
-        for k, i in enumerate(shards[g]):
-            res[i], outs[i] = r[k], o[k]
-    return res, outs
 
 
 def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=None, out=None):
@@ -122,7 +109,7 @@ def lz4_decompress_frames(frames, output_lens=None, devices=None, out=None):
     if output_lens is None:
         L = N.lib()
         output_lens = [max(L.cj_lz4_frame_decompress_bound(*_addr_len(f)), 0) for f in frames]
-    return _run(N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, frames, output_lens, devices, out, _FRAMES)
+    return _run(N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, frames, output_lens, devices, out, N.FRAMES)
 
 
 def lz4_compress_frames(buffers, devices=None, out=None):
@@ -130,7 +117,7 @@ def lz4_compress_frames(buffers, devices=None, out=None):
     sum(cj_lz4_frame_compress_bound(len(buffer))) bytes"""
     L = N.lib()
     return _run(N.FORMAT_LZ4_FRAME, N.OP_COMPRESS, 0, buffers, [L.cj_lz4_frame_compress_bound(len(memoryview(b).cast("B"))) for b in buffers],
-                devices, out, _FRAMES)
+                devices, out, N.FRAMES)
 
 
 def snappy_decompress_framed_many(streams, output_lens=None, devices=None, out=None):
@@ -138,14 +125,14 @@ def snappy_decompress_framed_many(streams, output_lens=None, devices=None, out=N
     if output_lens is None:
         L = N.lib()
         output_lens = [max(L.cj_snappy_frame_decompress_len(*_addr_len(f)), 0) for f in streams]
-    return _run(N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, streams, output_lens, devices, out, _FRAMES)
+    return _run(N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, streams, output_lens, devices, out, N.FRAMES)
 
 
 def snappy_compress_framed_many(buffers, devices=None, out=None):
     """one Snappy framed stream per buffer"""
     L = N.lib()
     return _run(N.FORMAT_SNAPPY_FRAMED, N.OP_COMPRESS, 0, buffers, [L.cj_snappy_frame_max_compress_len(len(memoryview(b).cast("B"))) for b in buffers],
-                devices, out, _FRAMES)
+                devices, out, N.FRAMES)
 
 
 # ---- device-resident batches: no host copy, no ctypes at the call site ---------------------------------------------------------
@@ -314,30 +301,28 @@ class _DeviceCall:
             v.release()
 
 
-def _device_batch(codec, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, frames=False):
+def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, params=None):
     call = _DeviceCall(stream, sync)
     try:
         vin, vout = call.buffer(inp), call.buffer(out)
         eng = call.engine(device, vin, vout)
-        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
-        p_out_off, p_out_cap = call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap")
+        i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
+        o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
         p_res = call.result(result)
-        submit = eng.frame_batch_device if frames else eng.batch_device
-        submit(codec, op, flags, call.n, vin.ptr, p_in_off, p_in_len, vout.ptr, p_out_off, p_out_cap, p_res, stream)
+        N.check(getattr(N.lib(), kind.device)(*kind.device_args(eng.h, what, op, flags, call.n, i, o, p_res, params, stream)))
         return call.finish(p_res, result)
     finally:
         call.close()
 
 
-def _device_sizes(what, flags, inp, in_off, in_len, result, device, stream, sync, frames=False):
+def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream, sync):
     call = _DeviceCall(stream, sync)
     try:
         vin = call.buffer(inp)
         eng = call.engine(device, vin)
         p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
         p_res = call.result(result)
-        fn = N.lib().cj_frame_batch_sizes_device if frames else N.lib().cj_batch_sizes_device
-        N.check(fn(eng.h, what, flags, call.n, vin.ptr, p_in_off, p_in_len, p_res, stream))
+        N.check(getattr(N.lib(), kind.sizes_device)(*kind.sizes_args(eng.h, what, flags, call.n, vin.ptr, p_in_off, p_in_len, p_res, stream)))
         return call.finish(p_res, result)
     finally:
         call.close()
@@ -355,46 +340,46 @@ def lz4_decompress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, sto
     buffers are ready (torch.cuda.synchronize()).  sync=False returns right after submission (device-resident metadata and result
     only).  In a process that also uses torch, import torch FIRST: both link libamdhip64.so.7, torch loads its own copy by path, and
     two HIP runtimes in one process do not share a device."""
-    return _device_batch(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
+    return _device_batch(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
                          inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def lz4_compress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, store_size=True, result=None, device=None, stream=None, sync=True):
     """Compress a device-resident batch into LZ4 blocks (src/lz4.rs:113-131); out_cap[i] >= cramjam.lz4.compress_block_bound(in_len[i])."""
-    return _device_batch(N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
+    return _device_batch(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
                          inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def snappy_decompress_raw_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Decode a device-resident batch of Snappy raw blocks (src/snappy.rs:52-59)."""
-    return _device_batch(N.CODEC_SNAPPY_RAW, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    return _device_batch(N.BLOCKS, N.CODEC_SNAPPY_RAW, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def snappy_compress_raw_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Compress a device-resident batch into Snappy raw blocks (src/snappy.rs:70-78); out_cap[i] >= cramjam.snappy.compress_raw_max_len(in_len[i])."""
-    return _device_batch(N.CODEC_SNAPPY_RAW, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    return _device_batch(N.BLOCKS, N.CODEC_SNAPPY_RAW, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 # ---- device-resident batches of framed streams (cj_frame_batch_device): the same arguments; stream i is inp[in_off[i] : + in_len[i]] and
 # its output goes to out[out_off[i] : + out_cap[i]].  The call waits for the stream once (it reads back the block counts / in_len).
 def lz4_decompress_frames_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Decode a device-resident batch of LZ4 frames (result[i] as cramjam_amd.lz4.decompress of frame i with that capacity)."""
-    return _device_batch(N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+    return _device_batch(N.FRAMES, N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def lz4_compress_frames_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """One LZ4 frame per device-resident buffer; out_cap[i] >= cj_lz4_frame_compress_bound(in_len[i])."""
-    return _device_batch(N.FORMAT_LZ4_FRAME, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+    return _device_batch(N.FRAMES, N.FORMAT_LZ4_FRAME, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def snappy_decompress_framed_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Decode a device-resident batch of Snappy framed streams."""
-    return _device_batch(N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+    return _device_batch(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def snappy_compress_framed_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """One Snappy framed stream per device-resident buffer; out_cap[i] >= cj_snappy_frame_max_compress_len(in_len[i])."""
-    return _device_batch(N.FORMAT_SNAPPY_FRAMED, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, True)
+    return _device_batch(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 # ---- decoded sizes (cj_batch_sizes_* / cj_frame_batch_sizes_*): what out_off / out_cap of the calls above are computed from -----------
@@ -418,70 +403,55 @@ def lz4_block_sizes_device(inp, in_off, in_len, store_size=False, result=None, d
     """Decoded sizes of a device-resident batch of LZ4 blocks.  store_size=True: the u32 prefix of each block (header only).
     store_size=False (raw blocks: Parquet LZ4_RAW, ORC, Arrow IPC): the token chain of every block is walked to its end — the exact
     size the decoder produces, CJ_E_CORRUPT (-7) for a block it would reject with any capacity."""
-    return _device_sizes(N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, inp, in_off, in_len, result, device, stream, sync)
+    return _device_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, inp, in_off, in_len, result, device, stream, sync)
 
 
 def snappy_raw_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
     """Announced lengths of a device-resident batch of Snappy raw blocks (cramjam.snappy.decompress_raw_len of each; header only)."""
-    return _device_sizes(N.CODEC_SNAPPY_RAW, 0, inp, in_off, in_len, result, device, stream, sync)
+    return _device_sizes(N.BLOCKS, N.CODEC_SNAPPY_RAW, 0, inp, in_off, in_len, result, device, stream, sync)
 
 
 def lz4_frame_bounds_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
     """cj_lz4_frame_decompress_bound of every frame of a device-resident batch: an upper bound of its decoded size (the content size
     where the frame stores one), 0 for a skippable frame, or its header error."""
-    return _device_sizes(N.FORMAT_LZ4_FRAME, 0, inp, in_off, in_len, result, device, stream, sync, True)
+    return _device_sizes(N.FRAMES, N.FORMAT_LZ4_FRAME, 0, inp, in_off, in_len, result, device, stream, sync)
 
 
 def snappy_framed_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
     """cj_snappy_frame_decompress_len of every stream of a device-resident batch: its decoded length, or its first header-level error."""
-    return _device_sizes(N.FORMAT_SNAPPY_FRAMED, 0, inp, in_off, in_len, result, device, stream, sync, True)
+    return _device_sizes(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, 0, inp, in_off, in_len, result, device, stream, sync)
 
 
-def _host_sizes(what, flags, buffers, devices, frames=False, blosc=False):
+def _host_sizes(kind, what, flags, buffers, devices):
     """sharded like _run: buffer i -> engine i mod G"""
     import numpy as np
-    devices = list(devices) if devices is not None else [0]
-    n = len(buffers)
-    fn = N.lib().cj_frame_batch_sizes_host if frames else N.lib().cj_batch_sizes_host
 
-    def work(g):
-        idx = range(g, n, len(devices))
+    def work(dev, idx):
         arrs = [np.frombuffer(buffers[i], dtype=np.uint8) for i in idx]          # borrowed, not copied
         k = len(arrs)
         ptrs = (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
         lens = (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
         res = np.empty(k, np.int64)
-        if blosc:
-            N.check(N.lib().cj_blosc_chunk_sizes_host(_engine(devices[g]).h, flags, k, ptrs, lens, res.ctypes.data))
-        else:
-            N.check(fn(_engine(devices[g]).h, what, flags, k, ptrs, lens, res.ctypes.data))
-        return idx, res
-    if len(devices) == 1:
-        return [int(x) for x in work(0)[1]]
-    with ThreadPoolExecutor(len(devices)) as ex:
-        parts = list(ex.map(work, range(len(devices))))
-    out = [None] * n
-    for idx, res in parts:
-        for k, i in enumerate(idx):
-            out[i] = int(res[k])
-    return out
+        N.check(getattr(N.lib(), kind.sizes_host)(*kind.sizes_args(_engine(dev).h, what, flags, k, ptrs, lens, res.ctypes.data)))
+        return ([int(x) for x in res],)
+    return _shard(devices, len(buffers), work)[0]
 
 
 def lz4_block_sizes(blocks, store_size=False, devices=None):
     """decoded sizes of many LZ4 blocks held on the host (list of ints; negative = CJ_E_* code), as lz4_block_sizes_device"""
-    return _host_sizes(N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, blocks, devices)
+    return _host_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, blocks, devices)
 
 
 def snappy_raw_sizes(blocks, devices=None):
-    return _host_sizes(N.CODEC_SNAPPY_RAW, 0, blocks, devices)
+    return _host_sizes(N.BLOCKS, N.CODEC_SNAPPY_RAW, 0, blocks, devices)
 
 
 def lz4_frame_bounds(frames, devices=None):
-    return _host_sizes(N.FORMAT_LZ4_FRAME, 0, frames, devices, True)
+    return _host_sizes(N.FRAMES, N.FORMAT_LZ4_FRAME, 0, frames, devices)
 
 
 def snappy_framed_sizes(streams, devices=None):
-    return _host_sizes(N.FORMAT_SNAPPY_FRAMED, 0, streams, devices, True)
+    return _host_sizes(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, 0, streams, devices)
 
 
 # ---- Blosc chunks (cj_blosc_batch_* / cj_blosc_chunk_sizes_*): LZ4 streams behind shuffle / bitshuffle -----------------------------
@@ -502,58 +472,34 @@ def _chunk_nbytes(c):
 def blosc_decompress_chunks(chunks, devices=None, out=None):
     """decode many Blosc chunks; returns (results, outputs) as lz4_decompress_blocks.  The capacities are the chunks' own nbytes
     (read on the host from their headers); out: ONE writable buffer of at least their sum, the outputs are then views into it."""
-    return _run(0, N.OP_DECOMPRESS, 0, chunks, [_chunk_nbytes(c) for c in chunks], devices, out, params=b"")
+    return _run(0, N.OP_DECOMPRESS, 0, chunks, [_chunk_nbytes(c) for c in chunks], devices, out, N.BLOSC, b"")
 
 
 def blosc_compress_chunks(buffers, typesize, filter=1, clevel=5, codec=1, blocksize=0, devices=None, out=None):
     """one Blosc chunk per buffer: LZ4 streams behind `filter` (0 none, 1 shuffle, 2 bitshuffle; cramjam_amd.blosc2.Filter) over
     elements of `typesize` bytes.  out has to hold sum(len(buffer) + 32) bytes."""
     caps = [memoryview(b).nbytes + 32 for b in buffers]
-    return _run(0, N.OP_COMPRESS, 0, buffers, caps, devices, out, params=_blosc_params(typesize, filter, clevel, codec, blocksize))
+    return _run(0, N.OP_COMPRESS, 0, buffers, caps, devices, out, N.BLOSC, _blosc_params(typesize, filter, clevel, codec, blocksize))
 
 
 def blosc_chunk_sizes(chunks, devices=None):
     """nbytes of many Blosc chunks held on the host (list of ints; negative = the header's CJ_E_* code)"""
-    return _host_sizes(0, 0, chunks, devices, blosc=True)
-
-
-def _blosc_device(op, params, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync):
-    call = _DeviceCall(stream, sync)
-    try:
-        vin, vout = call.buffer(inp), call.buffer(out)
-        eng = call.engine(device, vin, vout)
-        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
-        p_out_off, p_out_cap = call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap")
-        p_res = call.result(result)
-        N.check(N.lib().cj_blosc_batch_device(eng.h, op, vin.ptr, p_in_off, p_in_len, vout.ptr, p_out_off, p_out_cap, p_res, call.n,
-                                              _C.byref(params) if params is not None else None, 0, stream))
-        return call.finish(p_res, result)
-    finally:
-        call.close()
+    return _host_sizes(N.BLOSC, 0, 0, chunks, devices)
 
 
 def blosc_decompress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
     """Decode a device-resident batch of Blosc chunks (arguments as lz4_decompress_frames_device; the call waits for the stream once)."""
-    return _blosc_device(N.OP_DECOMPRESS, None, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    return _device_batch(N.BLOSC, 0, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def blosc_compress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, typesize, filter=1, clevel=5, codec=1, blocksize=0,
                                  result=None, device=None, stream=None, sync=True):
     """One Blosc chunk per device-resident buffer; out_cap[i] >= in_len[i] + 32 always suffices."""
     from . import blosc2
-    return _blosc_device(N.OP_COMPRESS, blosc2._params(typesize, clevel, filter, codec, blocksize), inp, in_off, in_len, out, out_off, out_cap,
-                         result, device, stream, sync)
+    return _device_batch(N.BLOSC, 0, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync,
+                         blosc2._params(typesize, clevel, filter, codec, blocksize))
 
 
 def blosc_chunk_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
     """nbytes of every chunk of a device-resident batch after the header checks, or their error; enqueue-only like lz4_block_sizes_device"""
-    call = _DeviceCall(stream, sync)
-    try:
-        vin = call.buffer(inp)
-        eng = call.engine(device, vin)
-        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
-        p_res = call.result(result)
-        N.check(N.lib().cj_blosc_chunk_sizes_device(eng.h, 0, call.n, vin.ptr, p_in_off, p_in_len, p_res, stream))
-        return call.finish(p_res, result)
-    finally:
-        call.close()
+    return _device_sizes(N.BLOSC, 0, 0, inp, in_off, in_len, result, device, stream, sync)

@@ -212,7 +212,7 @@ int sizes_device(Query q, cj_engine* e, int what, uint32_t flags, size_t n, cons
     return sizes_launch(q, what, flags, n, in_base, in_off, in_len, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
 }
 
-// lay_out -> pack -> H2D -> the device path -> D2H of the results.  No output staging.
+// the host batch's staging (cj::host_batch) as a size query: no output
 int sizes_host(Query q, cj_engine* e, int what, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
     if (!known(q, what) || !flags_ok(q, flags) || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
     if (n == 0) return 0;
@@ -220,22 +220,9 @@ int sizes_host(Query q, cj_engine* e, int what, uint32_t flags, size_t n, const 
         if (in_lens[i] && !in_ptrs[i]) return CJ_E_BAD_ARG;
     if (!e) e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
-    std::lock_guard<std::mutex> lock(e->mu);
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    uint64_t in_total = 0, out_total = 0;
-    const std::vector<size_t> no_caps(n, 0);
-    const cj::BatchRows h = cj::lay_out(e, CJ_CODEC_LZ4_BLOCK, CJ_OP_DECOMPRESS, 0u, n, in_lens, no_caps.data(), in_total, out_total, false);
-    if (!e->d_in.reserve(in_total + 16) || !e->d_meta.reserve(5 * n * 8) || !e->h_in.reserve(in_total)) return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
-    cj::pack(e, h, 0, n, in_total, in_ptrs, in_lens);
-    if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 2 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);      // (in_off, in_len)
-    const int rc = sizes_launch(q, what, flags, n, d_in, d.in_off, d.in_len, d.result, e->stream);
-    if (rc != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
-    return 0;
+    return cj::host_batch(e, n, in_ptrs, in_lens, nullptr, nullptr, result, -1, [&](const uint8_t* d_in, uint8_t*, const cj::BatchRows& d, hipStream_t s) {
+        return sizes_launch(q, what, flags, n, d_in, d.in_off, d.in_len, d.result, s);
+    });
 }
 
 }  // namespace

@@ -232,10 +232,8 @@ int run_rows(cj_engine* e, cj_op op, uint32_t flags, const uint8_t* in_base, uin
 
 int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                 const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const cj_blosc_params* params, hipStream_t s) {
-    // (the frame batches' lock and scratch: chunk batches and frame batches on one engine run one after another)
-    std::lock_guard<std::mutex> lock(e->fb_mu);
-    if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
-    else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);
+    cj::FbTurn turn(e, s);                     // (the frame batches' scratch: chunk batches and frame batches on one engine run one after another)
+    if (turn.rc != 0) return turn.rc;
     const bool dec = op == CJ_OP_DECOMPRESS;
     const size_t tab = up16(n * sizeof(BlChunk)), cnt_bytes = n * sizeof(BlCount);
     int rc = cj::fb_reserve(e, std::max(cnt_bytes, tab), tab + cnt_bytes);
@@ -315,9 +313,7 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
         hipLaunchKernelGGL(cj::bl_assemble_kernel, dim3((uint32_t)((n + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock)), dim3(cj::kBlockThreads), 0, s,
                            (uint32_t)n, (const BlChunk*)d_tab, *params, r.b, in_base, in_off, scratch, packed, out_base, out_off, out_cap, result);
     }
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipEventRecord(e->fb_free, s), CJ_E_NO_DEVICE);
-    return 0;
+    return turn.done(s);
 }
 
 }  // namespace
@@ -359,29 +355,9 @@ int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n, const 
         if ((in_lens[i] && !in_ptrs[i]) || (out_caps[i] && !out_ptrs[i])) return CJ_E_BAD_ARG;
     if (!e) e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
-    std::lock_guard<std::mutex> lock(e->mu);
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    uint64_t in_total = 0, out_total = 0;
-    const cj::BatchRows h = cj::lay_out(e, CJ_CODEC_LZ4_BLOCK, op, 0u, n, in_lens, out_caps, in_total, out_total, false);
-    if (!e->d_in.reserve(in_total + 16) || !e->d_out.reserve(out_total + 16) || !e->d_meta.reserve(5 * n * 8) || !e->h_in.reserve(in_total))
-        return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint8_t* d_out = (uint8_t*)e->d_out.p;
-    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
-    cj::pack(e, h, 0, n, in_total, in_ptrs, in_lens);
-    if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    const int rc = blosc_batch(e, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, params, e->stream);
-    if (rc != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
-    uint64_t span = 0;
-    for (size_t i = 0; i < n; i++)
-        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
-    if (!e->h_out.reserve(span)) return CJ_E_OOM;
-    if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-    cj::scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
-    return 0;
+    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+        return blosc_batch(e, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, params, s);
+    });
 }
 
 int64_t cj_blosc_chunk_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap) {

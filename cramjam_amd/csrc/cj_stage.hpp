@@ -4,6 +4,7 @@
 #pragma once
 #include "cj_engine.hpp"
 
+#include <functional>
 #include <initializer_list>
 
 namespace cj {
@@ -54,8 +55,28 @@ void launch_fb_pieces(size_t n, const FbFrame* fr, const uint64_t* in_off, const
 void launch_fb_assemble(int fmt, size_t n, const FbFrame* fr, FbRows r, const uint32_t* sums, const uint8_t* in_base, const uint64_t* in_len, const uint8_t* scratch, uint64_t stride, uint8_t* out_base, const uint64_t* out_off,
                         const uint64_t* out_cap, int64_t* result, hipStream_t s);
 
-// the frame batch's scratch (e->d_fb, e->h_fb; Blosc chunk batches use it too) is reused by the next call: it waits for this one on the
-// device; growing it waits on the host
+// One turn at the container batches' scratch (e->d_fb, e->h_fb: frame batches and Blosc chunk batches).  The lock is held across the
+// call's one wait: such batches on one engine run one after another, and a call waits for everything its caller queued on `s` before
+// it, so a second caller's batch also waits behind that (engines are cheap: one per thread or stream avoids it).  The next turn waits
+// for this one on the device, from done(s) on — a call that returns an error before that records nothing.
+struct FbTurn {
+    cj_engine* e;
+    std::lock_guard<std::mutex> lock;
+    int rc;                        // of the construction: 0 or CJ_E_*
+    FbTurn(cj_engine* e_, hipStream_t s) : e(e_), lock(e_->fb_mu), rc(open(s)) {}
+    int done(hipStream_t s) {
+        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+        HIP_TRY(hipEventRecord(e->fb_free, s), CJ_E_NO_DEVICE);
+        return 0;
+    }
+private:
+    int open(hipStream_t s) {
+        if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
+        else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);      // the previous user of the scratch
+        return 0;
+    }
+};
+// growing the scratch waits for its previous user on the host
 inline int fb_reserve(cj_engine* e, size_t dev_bytes, size_t host_bytes) {
     if ((dev_bytes > e->d_fb.cap || host_bytes > e->h_fb.cap) && e->fb_free) HIP_TRY(hipEventSynchronize(e->fb_free), CJ_E_NO_DEVICE);
     if (!e->d_fb.reserve(dev_bytes) || !e->h_fb.reserve(host_bytes)) return CJ_E_OOM;
@@ -114,16 +135,16 @@ inline int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lea
     return assemble(e, size, lead, lead_len, lists, 0, [](uint8_t*) { return 0; }, out);
 }
 
-// A host batch (engine.hip): lay_out puts the rows of n buffers in e->h_meta — inputs and outputs one after another, 16 bytes aligned,
-// their sizes added to in_total / out_total (widen: LZ4 block compress gets a full LZ4_compressBound of room on the device); pack
-// copies the inputs of [a0, b0) into e->h_in, scatter the results res of [a0, b0) into result (within_cap) and their outputs from
-// e->h_out to the caller
-BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const size_t* in_lens, const size_t* out_caps,
-                  uint64_t& in_total, uint64_t& out_total, bool widen = true);
-int64_t within_cap(int64_t r, size_t cap);
-void pack(cj_engine* e, const BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const uint8_t* const* in_ptrs, const size_t* in_lens);
-void scatter(cj_engine* e, const BatchRows& h, size_t a0, size_t b0, uint64_t bytes, const int64_t* res, uint8_t* const* out_ptrs,
-             const size_t* out_caps, int64_t* result);
+// A host batch (engine.hip), the one staging of cj_batch_host, cj_frame_batch_host, cj_blosc_batch_host and the size queries: under
+// e->mu, on the engine's device and stream — the rows of the n buffers laid out one after another, 16 bytes aligned; the inputs packed
+// into pinned staging and uploaded with the rows; run(d_in, d_out, d, s) = the device path over the device rows d; the results read
+// back and waited for; the span of d_out that was produced copied back and scattered to out_ptrs (a result above its capacity becomes
+// CJ_E_COMPRESS_FAILED).  out_ptrs == nullptr is a size query: no output is staged or reserved (d_out = nullptr), only in_off / in_len
+// travel.  lz4_room 0 / 1: LZ4 block compress without / with the size prefix — every chunk gets at least its
+// cj_lz4_block_compress_bound on the device; -1: the capacities as given.  Returns 0 or CJ_E_*.
+using HostRun = std::function<int(const uint8_t* d_in, uint8_t* d_out, const BatchRows& d, hipStream_t s)>;
+int host_batch(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, uint8_t* const* out_ptrs, const size_t* out_caps,
+               int64_t* result, int lz4_room, const HostRun& run);
 
 // The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
 int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);

@@ -269,21 +269,20 @@ int64_t single(cj_codec codec, cj_op op, uint32_t flags, const uint8_t* in, size
 
 }  // namespace
 
-namespace cj {
+namespace {
 
-// The rows of a host batch in e->h_meta: inputs and outputs one after another, 16 bytes aligned, their sizes added to in_total / out_total.
-// LZ4 compress: the kernel gets a full LZ4_compressBound of room on the device; the caller's capacity applies when copying back (within_cap).
-cj::BatchRows lay_out(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const size_t* in_lens, const size_t* out_caps,
-                      uint64_t& in_total, uint64_t& out_total, bool widen) {
+// The rows of a host batch in e->h_meta: inputs and outputs one after another, 16 bytes aligned, their sizes added to in_total / out_total
+// (out_caps == nullptr: a size query, no output).  lz4_room 0 / 1 (LZ4 block compress, without / with the size prefix): the kernel gets a
+// full LZ4_compressBound of room on the device; the caller's capacity applies when copying back (within_cap).  -1: the capacities as given.
+cj::BatchRows lay_out(cj_engine* e, size_t n, const size_t* in_lens, const size_t* out_caps, int lz4_room, uint64_t& in_total, uint64_t& out_total) {
     e->h_meta.assign(5 * n, 0);
     const cj::BatchRows h = cj::batch_rows(e->h_meta.data(), n);
     for (size_t i = 0; i < n; i++) {
         h.in_off[i] = in_total;
         h.in_len[i] = in_lens[i];
         in_total += (in_lens[i] + 15u) & ~(uint64_t)15u;
-        uint64_t dcap = out_caps[i];
-        if (widen && codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS)
-            dcap = std::max<uint64_t>(dcap, cj_lz4_block_compress_bound(in_lens[i], (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0));
+        uint64_t dcap = out_caps ? out_caps[i] : 0;
+        if (lz4_room >= 0) dcap = std::max<uint64_t>(dcap, cj_lz4_block_compress_bound(in_lens[i], lz4_room));
         h.out_off[i] = out_total;
         h.out_cap[i] = dcap;
         out_total += (dcap + 15u) & ~(uint64_t)15u;
@@ -313,12 +312,46 @@ void scatter(cj_engine* e, const cj::BatchRows& h, size_t a0, size_t b0, uint64_
     });
 }
 
-}  // namespace cj
+// The one-shot staging of a host batch whose rows h are laid out and whose device buffers are reserved (e->mu held): pack -> H2D of
+// the data and the rows -> run -> D2H of the results -> wait -> D2H of the span that was produced -> scatter.  out_ptrs == nullptr
+// (a size query): the two input rows travel, nothing comes back but the results.
+int staged(cj_engine* e, const cj::BatchRows& h, uint64_t in_total, const uint8_t* const* in_ptrs, const size_t* in_lens, uint8_t* const* out_ptrs,
+           const size_t* out_caps, int64_t* result, const cj::HostRun& run) {
+    const size_t n = h.n;
+    hipStream_t s = e->stream;
+    if (!e->h_in.reserve(in_total)) return CJ_E_OOM;
+    const uint8_t* d_in = (const uint8_t*)e->d_in.p;
+    uint8_t* d_out = out_ptrs ? (uint8_t*)e->d_out.p : nullptr;
+    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
+    pack(e, h, 0, n, in_total, in_ptrs, in_lens);
+    if (in_total) HIP_TRY(hipMemcpyAsync(e->d_in.p, e->h_in.p, in_total, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, (out_ptrs ? 4 : 2) * n * 8, hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);      // (the rows up to result / up to out_off)
+    const int rc = run(d_in, d_out, d, s);
+    if (rc != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
+    if (!out_ptrs) return 0;
+    // copy back only the span that was produced
+    uint64_t span = 0;
+    for (size_t i = 0; i < n; i++)
+        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
+    if (!e->h_out.reserve(span)) return CJ_E_OOM;
+    if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
+    scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
+    return 0;
+}
 
-using cj::lay_out;
-using cj::within_cap;
-using cj::pack;
-using cj::scatter;
+}  // namespace
+
+int cj::host_batch(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, uint8_t* const* out_ptrs, const size_t* out_caps,
+                   int64_t* result, int lz4_room, const cj::HostRun& run) {
+    std::lock_guard<std::mutex> lock(e->mu);
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    uint64_t in_total = 0, out_total = 0;
+    const cj::BatchRows h = lay_out(e, n, in_lens, out_ptrs ? out_caps : nullptr, lz4_room, in_total, out_total);
+    if (!e->d_in.reserve(in_total + 16) || (out_ptrs && !e->d_out.reserve(out_total + 16)) || !e->d_meta.reserve(5 * n * 8)) return CJ_E_OOM;
+    return staged(e, h, in_total, in_ptrs, in_lens, out_ptrs, out_caps, result, run);
+}
 
 namespace {
 
@@ -580,44 +613,32 @@ int cj_batch_host(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
 
     uint64_t in_total = 0, out_total = 0;
-    const cj::BatchRows h = lay_out(e, codec, op, flags, n, in_lens, out_caps, in_total, out_total);
+    const int lz4_room = codec == CJ_CODEC_LZ4_BLOCK && op == CJ_OP_COMPRESS ? ((flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0) : -1;
+    const cj::BatchRows h = lay_out(e, n, in_lens, out_caps, lz4_room, in_total, out_total);
     if (!e->d_in.reserve(in_total + 16) || !e->d_out.reserve(out_total + 16) || !e->d_meta.reserve(5 * n * 8)) return CJ_E_OOM;
 
     // (a large batch: sliced, so that packing, the two directions of the link, the kernels and the scattering overlap)
     if (n >= 512 && in_total + out_total >= (128ull << 20))
         return batch_host_sliced(e, codec, op, flags, h, in_ptrs, in_lens, out_ptrs, out_caps, result, in_total, out_total);
 
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
+    const auto run = [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+        cj::BatchArgs a;
+        fill_args(a, flags, d_in, d_out, d);
+        return launch(e, codec, op, a, s);
+    };
+    if (n > 1) return staged(e, h, in_total, in_ptrs, in_lens, out_ptrs, out_caps, result, run);
+
+    // one chunk: nothing to pack or scatter, the copies go straight from and to the caller's buffers
     uint8_t* d_out = (uint8_t*)e->d_out.p;
     const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
-    if (n == 1) {
-        if (in_lens[0]) HIP_TRY(hipMemcpyAsync(d_in, in_ptrs[0], in_lens[0], hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    } else {
-        if (!e->h_in.reserve(in_total)) return CJ_E_OOM;
-        pack(e, h, 0, n, in_total, in_ptrs, in_lens);
-        if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    }
+    if (in_lens[0]) HIP_TRY(hipMemcpyAsync(e->d_in.p, in_ptrs[0], in_lens[0], hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);     // (the rows up to result)
-
-    cj::BatchArgs a;
-    fill_args(a, flags, d_in, d_out, d);
-    int rc = launch(e, codec, op, a, e->stream);
+    const int rc = run((const uint8_t*)e->d_in.p, d_out, d, e->stream);
     if (rc != 0) return rc;
     HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
-
-    if (n == 1) {
-        result[0] = within_cap(result[0], out_caps[0]);
-        if (result[0] > 0) HIP_TRY(hipMemcpy(out_ptrs[0], d_out, (size_t)result[0], hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-        return 0;
-    }
-    // copy back only the span that was produced
-    uint64_t span = 0;
-    for (size_t i = 0; i < n; i++)
-        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
-    if (!e->h_out.reserve(span)) return CJ_E_OOM;
-    if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-    scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
+    result[0] = within_cap(result[0], out_caps[0]);
+    if (result[0] > 0) HIP_TRY(hipMemcpy(out_ptrs[0], d_out, (size_t)result[0], hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
     return 0;
 }
 

@@ -16,12 +16,8 @@ inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 
 int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    // (the lock is held across the one wait below: frame batches on one engine run one after another, and a call waits for everything
-    //  its caller queued on `s` before it, so a second caller's batch also waits behind that.  Engines are cheap: one per thread or stream
-    //  avoids it.)
-    std::lock_guard<std::mutex> lock(e->fb_mu);
-    if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
-    else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);          // the previous user of the scratch
+    cj::FbTurn turn(e, s);
+    if (turn.rc != 0) return turn.rc;
     const size_t tab = up16(n * sizeof(cj::FbFrame));
     int rc = cj::fb_reserve(e, std::max(16 * n, tab), tab + 16 * n);
     if (rc != 0) return rc;
@@ -87,9 +83,7 @@ int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* 
         else cj::launch_crc32c_pieces(in_base, r.b.in_off, r.b.in_len, r.got, (uint32_t)nb, s);
         cj::launch_fb_assemble(fmt, n, fr, r, sums, in_base, in_len, scratch, stride, out_base, out_off, out_cap, result, s);
     }
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipEventRecord(e->fb_free, s), CJ_E_NO_DEVICE);
-    return 0;
+    return turn.done(s);
 }
 
 bool fb_args_ok(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags) {
@@ -117,29 +111,9 @@ int cj_frame_batch_host(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, s
     if (!fb_args_ok(e, fmt, op, flags) || (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result))) return CJ_E_BAD_ARG;
     if (n == 0) return 0;
     if (n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    std::lock_guard<std::mutex> lock(e->mu);
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    uint64_t in_total = 0, out_total = 0;
-    const cj::BatchRows h = cj::lay_out(e, CJ_CODEC_LZ4_BLOCK, op, 0u, n, in_lens, out_caps, in_total, out_total, false);
-    if (!e->d_in.reserve(in_total + 16) || !e->d_out.reserve(out_total + 16) || !e->d_meta.reserve(5 * n * 8) || !e->h_in.reserve(in_total))
-        return CJ_E_OOM;
-    uint8_t* d_in = (uint8_t*)e->d_in.p;
-    uint8_t* d_out = (uint8_t*)e->d_out.p;
-    const cj::BatchRows d = cj::batch_rows((uint64_t*)e->d_meta.p, n);
-    cj::pack(e, h, 0, n, in_total, in_ptrs, in_lens);
-    if (in_total) HIP_TRY(hipMemcpyAsync(d_in, e->h_in.p, in_total, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(d.in_off, h.in_off, 4 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);     // (the rows up to result)
-    const int rc = frame_batch(e, fmt, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, e->stream);
-    if (rc != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, d.result, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
-    uint64_t span = 0;
-    for (size_t i = 0; i < n; i++)
-        if (result[i] > 0 && h.out_off[i] + (uint64_t)result[i] > span) span = h.out_off[i] + (uint64_t)result[i];
-    if (!e->h_out.reserve(span)) return CJ_E_OOM;
-    if (span) HIP_TRY(hipMemcpy(e->h_out.p, d_out, span, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
-    cj::scatter(e, h, 0, n, span, result, out_ptrs, out_caps, result);
-    return 0;
+    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+        return frame_batch(e, fmt, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+    });
 }
 
 // debug aid (tests): XXH32 of n device streams by the batch's kernel, on the engine's stream, synchronously

@@ -1351,73 +1351,102 @@ struct BloscArg {
         if (given && view.len) std::memcpy(&p, view.buf, sizeof p);
         return true;
     }
-    int call(unsigned long long fn_addr, cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
-             uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* res) const {
-        const blosc_host_fn f = fn_addr ? (blosc_host_fn)(uintptr_t)fn_addr : &cj_blosc_batch_host;
-        return f(e, op, flags, n, in_ptrs, in_lens, out_ptrs, out_caps, res, view.len ? &p : nullptr);
+};
+
+// What batch_host and batch_host_into share: the borrowed inputs, the arrays of the native call, the call itself and its report.
+// Where the output pointers come from is the entries' own.
+struct HostBatch {
+    PyObject *inputs = nullptr, *caps = nullptr;
+    Py_ssize_t n = 0, got = 0;
+    std::vector<Py_buffer> views;
+    std::vector<const uint8_t*> in_ptrs;
+    std::vector<size_t> in_lens, out_caps;
+    std::vector<uint8_t*> out_ptrs;
+    std::vector<int64_t> res;
+    ~HostBatch() { release(); Py_XDECREF(inputs); Py_XDECREF(caps); }
+    void release() { while (got > 0) PyBuffer_Release(&views[(size_t)--got]); }
+    bool open(PyObject* inputs_o, PyObject* caps_o) {
+        if (!(inputs = PySequence_Fast(inputs_o, "inputs must be a sequence of bytes-like objects"))) return false;
+        if (!(caps = PySequence_Fast(caps_o, "out_caps must be a sequence of integers"))) return false;
+        n = PySequence_Fast_GET_SIZE(inputs);
+        if (PySequence_Fast_GET_SIZE(caps) != n) { PyErr_SetString(PyExc_ValueError, "inputs and out_caps differ in length"); return false; }
+        views.resize((size_t)n); in_ptrs.resize((size_t)n); in_lens.resize((size_t)n); out_caps.resize((size_t)n); out_ptrs.resize((size_t)n); res.resize((size_t)n);
+        return true;
+    }
+    // input i (buffer protocol, no copy) and its capacity
+    bool borrow(Py_ssize_t i) {
+        Py_buffer& v = views[(size_t)i];
+        if (PyObject_GetBuffer(PySequence_Fast_GET_ITEM(inputs, i), &v, PyBUF_CONTIG_RO) != 0) return false;
+        got = i + 1;
+        in_lens[(size_t)i] = (size_t)v.len;
+        in_ptrs[(size_t)i] = v.len ? (const uint8_t*)v.buf : nullptr;
+        out_caps[(size_t)i] = PyLong_AsSize_t(PySequence_Fast_GET_ITEM(caps, i));
+        return !(out_caps[(size_t)i] == (size_t)-1 && PyErr_Occurred());
+    }
+    // The native call of all three kinds, without the GIL.  fn_addr: the entry point in the library the engine handle came from (a tuning
+    // variant loaded through CJ_HIP_LIB; 0 = the one this module links) — cj_batch_host or cj_frame_batch_host, which share a
+    // signature, or with `blosc` cj_blosc_batch_host (codec is not used).
+    int call(unsigned long long handle, unsigned long long fn_addr, int codec, int op, unsigned int flags, const BloscArg& blosc) {
+        int rc = 0;
+        if (n > 0) {
+            cj_engine* e = (cj_engine*)(uintptr_t)handle;
+            Py_BEGIN_ALLOW_THREADS
+            if (blosc.given) {
+                const blosc_host_fn f = fn_addr ? (blosc_host_fn)(uintptr_t)fn_addr : &cj_blosc_batch_host;
+                rc = f(e, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data(), blosc.view.len ? &blosc.p : nullptr);
+            } else {
+                const batch_host_fn f = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
+                rc = f(e, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
+            }
+            Py_END_ALLOW_THREADS
+        }
+        release();
+        return rc;
+    }
+    PyObject* results() const {
+        PyObject* l = PyList_New(n);
+        for (Py_ssize_t i = 0; l && i < n; i++) {
+            PyObject* r = PyLong_FromLongLong((long long)res[(size_t)i]);
+            if (!r) { Py_DECREF(l); return nullptr; }
+            PyList_SET_ITEM(l, i, r);
+        }
+        return l;
     }
 };
+
+// A CJ_E_* return code of the call itself.  The HIP error text behind it is thread-local PER LIBRARY: the caller, who knows which
+// library fn_addr came from (cramjam_amd/_native.py), appends it.
+bool raise_rc(int rc) {
+    PyErr_Format(PyExc_RuntimeError, "cramjam_hip error %d: %s", rc, cj_strerror(rc));
+    return false;
+}
+
 PyObject* root_batch_host(PyObject*, PyObject* args) {
     unsigned long long handle, fn_addr = 0; int codec, op; unsigned int flags; PyObject *inputs_o, *caps_o;
     BloscArg blosc;
-    if (!PyArg_ParseTuple(args, "KiiIOO|Ky*", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr, &blosc.view) || !blosc.parse()) return nullptr;
-    // (fn_addr: cj_batch_host of the library the engine handle came from — a tuning variant loaded through CJ_HIP_LIB; 0 = the one this module links)
-    const batch_host_fn call = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
-    PyObject* inputs = PySequence_Fast(inputs_o, "inputs must be a sequence of bytes-like objects");
-    if (!inputs) return nullptr;
-    PyObject* caps = PySequence_Fast(caps_o, "out_caps must be a sequence of integers");
-    if (!caps) { Py_DECREF(inputs); return nullptr; }
-    const Py_ssize_t n = PySequence_Fast_GET_SIZE(inputs);
-    if (PySequence_Fast_GET_SIZE(caps) != n) { Py_DECREF(inputs); Py_DECREF(caps); PyErr_SetString(PyExc_ValueError, "inputs and out_caps differ in length"); return nullptr; }
-    std::vector<Py_buffer> views((size_t)n);
-    std::vector<const uint8_t*> in_ptrs((size_t)n);
-    std::vector<size_t> in_lens((size_t)n), out_caps((size_t)n);
-    std::vector<uint8_t*> out_ptrs((size_t)n);
-    std::vector<int64_t> res((size_t)n);
-    Py_ssize_t got = 0;
-    PyObject* outs = PyList_New(n);
+    HostBatch b;
+    if (!PyArg_ParseTuple(args, "KiiIOO|Ky*", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr, &blosc.view) || !blosc.parse() || !b.open(inputs_o, caps_o)) return nullptr;
+    PyObject* outs = PyList_New(b.n);
     bool ok = outs != nullptr;
-    for (Py_ssize_t i = 0; ok && i < n; i++) {
-        if (PyObject_GetBuffer(PySequence_Fast_GET_ITEM(inputs, i), &views[(size_t)i], PyBUF_CONTIG_RO) != 0) { ok = false; break; }
-        got = i + 1;
-        in_lens[(size_t)i] = (size_t)views[(size_t)i].len;
-        in_ptrs[(size_t)i] = views[(size_t)i].len ? (const uint8_t*)views[(size_t)i].buf : nullptr;
-        const size_t cap = PyLong_AsSize_t(PySequence_Fast_GET_ITEM(caps, i));
-        if (cap == (size_t)-1 && PyErr_Occurred()) { ok = false; break; }
-        PyObject* b = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(cap ? cap : 1));      // (a zero capacity still gets an address)
-        if (!b) { ok = false; break; }
-        PyList_SET_ITEM(outs, i, b);
-        out_caps[(size_t)i] = cap;
-        out_ptrs[(size_t)i] = (uint8_t*)PyBytes_AS_STRING(b);
+    for (Py_ssize_t i = 0; ok && i < b.n; i++) {
+        if (!b.borrow(i)) { ok = false; break; }
+        const size_t cap = b.out_caps[(size_t)i];
+        PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(cap ? cap : 1));      // (a zero capacity still gets an address)
+        if (!o) { ok = false; break; }
+        PyList_SET_ITEM(outs, i, o);
+        b.out_ptrs[(size_t)i] = (uint8_t*)PyBytes_AS_STRING(o);
     }
-    int rc = 0;
-    if (ok && n > 0) {
-        Py_BEGIN_ALLOW_THREADS
-        rc = blosc.given ? blosc.call(fn_addr, (cj_engine*)(uintptr_t)handle, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data())
-                         : call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
-        Py_END_ALLOW_THREADS
-    }
-    for (Py_ssize_t i = 0; i < got; i++) PyBuffer_Release(&views[(size_t)i]);
-    Py_DECREF(inputs); Py_DECREF(caps);
-    if (ok && rc != 0) {
-        // (the HIP error text is thread-local PER LIBRARY: through a tuning variant's entry point it lies in that library, and the caller —
-        //  cramjam_amd/_native.py, which holds the variant's handle — appends it; round-5 advisor)
-        if (fn_addr) PyErr_Format(PyExc_RuntimeError, "cramjam_hip error %d: %s", rc, cj_strerror(rc));
-        else PyErr_Format(PyExc_RuntimeError, "cramjam_hip error %d: %s (%s)", rc, cj_strerror(rc), cj_last_hip_error());
-        ok = false;
-    }
-    PyObject* results = ok ? PyList_New(n) : nullptr;
+    const int rc = ok ? b.call(handle, fn_addr, codec, op, flags, blosc) : 0;
+    if (rc != 0) ok = raise_rc(rc);
+    PyObject* results = ok ? b.results() : nullptr;
     if (!results) ok = false;
-    for (Py_ssize_t i = 0; ok && i < n; i++) {
-        PyObject* r = PyLong_FromLongLong((long long)res[(size_t)i]);
-        if (!r) { ok = false; break; }
-        PyList_SET_ITEM(results, i, r);
-        const Py_ssize_t want = res[(size_t)i] > 0 ? (Py_ssize_t)res[(size_t)i] : 0;
-        PyObject* b = PyList_GET_ITEM(outs, i);
-        if (PyBytes_GET_SIZE(b) != want) {                       // (the list holds the only reference: resized in place or moved)
+    for (Py_ssize_t i = 0; ok && i < b.n; i++) {
+        const Py_ssize_t want = b.res[(size_t)i] > 0 ? (Py_ssize_t)b.res[(size_t)i] : 0;
+        PyObject* o = PyList_GET_ITEM(outs, i);
+        if (PyBytes_GET_SIZE(o) != want) {                       // (the list holds the only reference: resized in place or moved)
             PyList_SET_ITEM(outs, i, nullptr);
-            if (_PyBytes_Resize(&b, want) != 0) { ok = false; break; }
-            PyList_SET_ITEM(outs, i, b);
+            if (_PyBytes_Resize(&o, want) != 0) { ok = false; break; }
+            PyList_SET_ITEM(outs, i, o);
         }
     }
     if (!ok) { Py_XDECREF(outs); Py_XDECREF(results); return nullptr; }
@@ -1431,60 +1460,32 @@ PyObject* root_batch_host(PyObject*, PyObject* args) {
 PyObject* root_batch_host_into(PyObject*, PyObject* args) {
     unsigned long long handle, fn_addr = 0; int codec, op; unsigned int flags; PyObject *inputs_o, *caps_o, *out_o, *offs_o = Py_None;
     BloscArg blosc;
+    HostBatch b;
+    struct Out {
+        Py_buffer view = {}; PyObject* offs = nullptr;
+        ~Out() { if (view.obj) PyBuffer_Release(&view); Py_XDECREF(offs); }
+    } out;
     if (!PyArg_ParseTuple(args, "KiiIOOO|OKy*", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &out_o, &offs_o, &fn_addr, &blosc.view) || !blosc.parse()) return nullptr;
-    const batch_host_fn call = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
-    Py_buffer ob;
-    if (PyObject_GetBuffer(out_o, &ob, PyBUF_WRITABLE | PyBUF_C_CONTIGUOUS) != 0) return nullptr;
-    PyObject* inputs = PySequence_Fast(inputs_o, "inputs must be a sequence of bytes-like objects");
-    PyObject* caps = inputs ? PySequence_Fast(caps_o, "out_caps must be a sequence of integers") : nullptr;
-    PyObject* offs = (caps && offs_o != Py_None) ? PySequence_Fast(offs_o, "offsets must be a sequence of integers") : nullptr;
-    bool ok = inputs && caps && (offs_o == Py_None || offs);
-    const Py_ssize_t n = ok ? PySequence_Fast_GET_SIZE(inputs) : 0;
-    if (ok && (PySequence_Fast_GET_SIZE(caps) != n || (offs && PySequence_Fast_GET_SIZE(offs) != n))) { PyErr_SetString(PyExc_ValueError, "inputs, out_caps and offsets differ in length"); ok = false; }
-    std::vector<Py_buffer> views((size_t)n);
-    std::vector<const uint8_t*> in_ptrs((size_t)n);
-    std::vector<size_t> in_lens((size_t)n), out_caps((size_t)n);
-    std::vector<uint8_t*> out_ptrs((size_t)n);
-    std::vector<int64_t> res((size_t)n);
-    Py_ssize_t got = 0;
+    if (PyObject_GetBuffer(out_o, &out.view, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
+    if (out.view.readonly) { PyErr_SetString(PyExc_ValueError, "out must be a writable buffer"); return nullptr; }
+    if (!b.open(inputs_o, caps_o)) return nullptr;
+    if (offs_o != Py_None) {
+        if (!(out.offs = PySequence_Fast(offs_o, "offsets must be a sequence of integers"))) return nullptr;
+        if (PySequence_Fast_GET_SIZE(out.offs) != b.n) { PyErr_SetString(PyExc_ValueError, "inputs, out_caps and offsets differ in length"); return nullptr; }
+    }
     size_t run = 0;
-    for (Py_ssize_t i = 0; ok && i < n; i++) {
-        if (PyObject_GetBuffer(PySequence_Fast_GET_ITEM(inputs, i), &views[(size_t)i], PyBUF_CONTIG_RO) != 0) { ok = false; break; }
-        got = i + 1;
-        in_lens[(size_t)i] = (size_t)views[(size_t)i].len;
-        in_ptrs[(size_t)i] = views[(size_t)i].len ? (const uint8_t*)views[(size_t)i].buf : nullptr;
-        const size_t cap = PyLong_AsSize_t(PySequence_Fast_GET_ITEM(caps, i));
-        if (cap == (size_t)-1 && PyErr_Occurred()) { ok = false; break; }
+    for (Py_ssize_t i = 0; i < b.n; i++) {
+        if (!b.borrow(i)) return nullptr;
+        const size_t cap = b.out_caps[(size_t)i];
         size_t off = run;
-        if (offs) { off = PyLong_AsSize_t(PySequence_Fast_GET_ITEM(offs, i)); if (off == (size_t)-1 && PyErr_Occurred()) { ok = false; break; } }
-        if (off > (size_t)ob.len || cap > (size_t)ob.len - off) { PyErr_SetString(PyExc_ValueError, "out is too small for the capacities given"); ok = false; break; }
-        out_caps[(size_t)i] = cap;
-        out_ptrs[(size_t)i] = (uint8_t*)ob.buf + off;
+        if (out.offs) { off = PyLong_AsSize_t(PySequence_Fast_GET_ITEM(out.offs, i)); if (off == (size_t)-1 && PyErr_Occurred()) return nullptr; }
+        if (off > (size_t)out.view.len || cap > (size_t)out.view.len - off) { PyErr_SetString(PyExc_ValueError, "out is too small for the capacities given"); return nullptr; }
+        b.out_ptrs[(size_t)i] = (uint8_t*)out.view.buf + off;
         run = off + cap;
     }
-    int rc = 0;
-    if (ok && n > 0) {
-        Py_BEGIN_ALLOW_THREADS
-        rc = blosc.given ? blosc.call(fn_addr, (cj_engine*)(uintptr_t)handle, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data())
-                         : call((cj_engine*)(uintptr_t)handle, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
-        Py_END_ALLOW_THREADS
-    }
-    for (Py_ssize_t i = 0; i < got; i++) PyBuffer_Release(&views[(size_t)i]);
-    PyBuffer_Release(&ob);
-    Py_XDECREF(inputs); Py_XDECREF(caps); Py_XDECREF(offs);
-    if (ok && rc != 0) { // (the HIP error text is thread-local PER LIBRARY: through a tuning variant's entry point it lies in that library, and the caller —
-        //  cramjam_amd/_native.py, which holds the variant's handle — appends it; round-5 advisor)
-        if (fn_addr) PyErr_Format(PyExc_RuntimeError, "cramjam_hip error %d: %s", rc, cj_strerror(rc));
-        else PyErr_Format(PyExc_RuntimeError, "cramjam_hip error %d: %s (%s)", rc, cj_strerror(rc), cj_last_hip_error()); ok = false; }
-    if (!ok) return nullptr;
-    PyObject* results = PyList_New(n);
-    if (!results) return nullptr;
-    for (Py_ssize_t i = 0; i < n; i++) {
-        PyObject* r = PyLong_FromLongLong((long long)res[(size_t)i]);
-        if (!r) { Py_DECREF(results); return nullptr; }
-        PyList_SET_ITEM(results, i, r);
-    }
-    return results;
+    const int rc = b.call(handle, fn_addr, codec, op, flags, blosc);
+    if (rc != 0) { raise_rc(rc); return nullptr; }
+    return b.results();
 }
 
 PyMethodDef root_methods[] = {

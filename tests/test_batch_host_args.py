@@ -1,0 +1,126 @@
+"""The argument handling of the CPython host layer's batch entries (_cramjam.batch_host / batch_host_into), the error text helper and
+the shard loop of cramjam_amd.batch — no device: engine handle 0, and every case returns or raises before any native call."""
+import pytest
+
+from cramjam_amd import _cramjam as M
+from cramjam_amd import _native as N
+from cramjam_amd import batch
+
+
+def _host(inputs, caps, *tail):
+    return M.batch_host(0, 0, 0, 0, inputs, caps, *tail)
+
+
+def _into(inputs, caps, *tail, out=None, offsets=None):
+    return M.batch_host_into(0, 0, 0, 0, inputs, caps, bytearray(64) if out is None else out, offsets, *tail)
+
+
+ENTRIES = [_host, _into]
+
+
+def test_empty_batches_return_without_a_call():
+    assert M.batch_host(0, 0, 0, 0, [], []) == ([], [])
+    assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), None) == []
+    assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(0)) == []
+    assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), []) == []
+    assert M.batch_host(0, 0, 0, 0, (), (), 0, b"") == ([], [])                     # (a Blosc batch)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_lengths_that_differ(entry):
+    with pytest.raises(ValueError):
+        entry([b"a", b"b"], [1])
+    with pytest.raises(ValueError):
+        entry([], [1])
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("params", [b"x", bytes(19), bytes(21)])
+def test_params_of_a_wrong_length(entry, params):
+    with pytest.raises(ValueError):
+        entry([b"a"], [1], 0, params)
+    with pytest.raises(ValueError):
+        entry([], [], 0, params)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("inputs, caps", [([b"a", 5], [1, 1]), ([b"a", None], [1, 1]), ([b"a", "text"], [1, 1]),
+                                          ([b"a", b"b"], [1, -1]), ([b"a", b"b"], [1, 1.5]), ([b"a", b"b"], [1, "1"]), ([b"a", b"b"], [1, None])])
+def test_an_input_that_is_no_buffer_or_a_capacity_that_is_no_size(entry, inputs, caps):
+    with pytest.raises((TypeError, ValueError, OverflowError)):
+        entry(inputs, caps)
+
+
+def test_into_offsets_of_the_wrong_length():
+    for offs in ([0], [0, 1, 2], []):
+        with pytest.raises(ValueError):
+            _into([b"a", b"b"], [1, 1], offsets=offs)
+
+
+def test_into_out_too_small():
+    with pytest.raises(ValueError):
+        _into([b"a", b"b"], [4, 5], out=bytearray(8))                               # back to back: 4 + 5 > 8
+    with pytest.raises(ValueError):
+        _into([b"a", b"b"], [4, 4], out=bytearray(8), offsets=[0, 5])
+    with pytest.raises(ValueError):
+        _into([b"a"], [0], out=bytearray(8), offsets=[9])
+    with pytest.raises(ValueError):
+        _into([b"a"], [2 ** 64 - 1], out=bytearray(8), offsets=[2])                # (offset + capacity wraps)
+
+
+def test_into_read_only_out():
+    for out in (bytes(8), memoryview(bytearray(8)).toreadonly()):
+        with pytest.raises(ValueError):
+            _into([b"a"], [1], out=out)
+
+
+def _failing(first):
+    """calls that fail on the entry BEHIND `first`, whose buffer has been borrowed by then"""
+    yield lambda: _host([first, 5], [1, 1])
+    yield lambda: _host([first, b"b"], [1, -1])
+    yield lambda: _into([first, 5], [1, 1])
+    yield lambda: _into([first, b"b"], [1, -1])
+    yield lambda: _into([first, b"b"], [8, 8], out=bytearray(12))
+    yield lambda: _into([first, b"b"], [1, 1], offsets=[0, "x"])
+    yield lambda: _into([first, b"b"], [1, 1], offsets=[0])
+    yield lambda: _host([first, b"b"], [1])
+    yield lambda: _host([first], [1], 0, b"xyz")
+
+
+def test_a_failure_releases_the_inputs_it_borrowed():
+    for k in range(9):
+        first = bytearray(b"0123456789")
+        call = list(_failing(first))[k]
+        with pytest.raises((TypeError, ValueError, OverflowError)):
+            call()
+        first.extend(b"more")                # BufferError while a buffer export of the call is still alive
+        del first[:]
+
+
+def test_the_hip_error_text_is_always_appended():
+    """_cramjam formats "cramjam_hip error %d: %s" and leaves the HIP text to the caller, which appends it whatever the message ends
+    with: cj_strerror(CJ_E_NO_DEVICE) — the code of every failed HIP call — ends with a parenthesis itself"""
+    hip = N.lib().cj_last_hip_error().decode()
+    no_device = "cramjam_hip error %d: %s" % (N.E_NO_DEVICE, N.strerror(N.E_NO_DEVICE))
+    assert no_device.endswith(")")
+    for msg in (no_device, "cramjam_hip error -101: cramjam_hip: bad argument", ""):
+        assert N._with_hip_error(msg) == "%s (%s)" % (msg, hip)
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 5])
+@pytest.mark.parametrize("g", [1, 2, 3])
+def test_shard_visits_every_index_once_and_keeps_the_callers_order(n, g):
+    devices = ["dev%d" % k for k in range(g)]
+    seen = []
+
+    def work(dev, idx):
+        idx = list(idx)
+        seen.append((dev, idx))
+        return [i * 10 for i in idx], [(dev, i) for i in idx]
+
+    a, b = batch._shard(devices, n, work)
+    assert list(a) == [i * 10 for i in range(n)]
+    assert list(b) == [(devices[i % g], i) for i in range(n)]                       # index i went to device i mod G
+    assert sorted(i for _, idx in seen for i in idx) == list(range(n))
+    assert sorted(dev for dev, _ in seen) == devices                                # one piece of work per device
+    assert batch._shard(None, n, lambda dev, idx: ([dev] * len(idx),)) == ([0] * n,)        # (no devices given: device 0)
