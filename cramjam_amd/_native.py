@@ -20,6 +20,7 @@ FLAG_CHUNKS_LE_16K = 0x80
 FLAG_BIG_CHUNKS = 0x800            # decompress: reserve record areas for chunks of 64 KiB .. 256 KiB (cramjam_hip.h)
 E_NO_DEVICE = -100
 E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
+BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
 
 
 class BloscParams(C.Structure):
@@ -151,6 +152,12 @@ class Kind:
 
     def __init__(self, host, device, sizes_host, sizes_device, blosc=False):
         self.host, self.device, self.sizes_host, self.sizes_device, self.blosc = host, device, sizes_host, sizes_device, blosc
+
+    def read_flags(self, blosclz=False):
+        """the flags word of a reading call of this kind: `blosclz` (Blosc chunks only) asks for BloscLZ streams to be read too"""
+        if blosclz and not self.blosc:
+            raise ValueError("blosclz applies to Blosc chunks only")
+        return BLOSC_FLAG_READ_BLOSCLZ if blosclz else 0
 
     def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
         if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)

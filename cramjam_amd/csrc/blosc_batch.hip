@@ -3,7 +3,8 @@
 //   decompress  walk pass 1 (one lane per chunk: streams, blocks, scratch) -> the one wait (prefix sums on the host) -> walk pass 2
 //               (stream rows, filter block rows) -> the LZ4 streams of all chunks through the engine: those of transposed blocks as
 //               one batch into the scratch, those of blocks that need no transposition (no filter, typesize 1 under shuffle,
-//               bitshuffle's odd blocks) as one batch straight into the callers' slots — no scratch, no second pass; stored streams
+//               bitshuffle's odd blocks) as one batch straight into the callers' slots — no scratch, no second pass; the BloscLZ
+//               streams (CJ_BLOSC_FLAG_READ_BLOSCLZ) the same two ways through blosclz_decode.hip; stored streams
 //               by copy_segments likewise -> the verdict (one lane per chunk) -> ONE unfilter launch from the scratch into the
 //               callers' slots (blocks of a chunk with an error are skipped)
 //   compress    in_len read back -> rows -> ONE filter launch into the scratch (transposed blocks only) -> the engine over all
@@ -16,11 +17,11 @@ namespace cj {
 
 // pass 1 of the decode walk, read back by the host.  A stream is DIRECT when its block needs no transposition (blosc_block_mode ==
 // kBloscCopy): it decodes straight into the caller's slot; every other stream decodes into the scratch, which the unfilter launch reads
-struct BlCount { uint32_t nstr, ndir, nblk, nbytes, scratch, maxlen, tiles, pad; int64_t err; };      // nblk: filtered blocks (memcpyed: copy pieces)
+struct BlCount { uint32_t nstr, ndir, nblk, nbytes, scratch, maxlen, tiles, format; int64_t err; };   // nblk: filtered blocks (memcpyed: copy pieces); format: kBloscFormat* of the streams
 // one row per chunk: where its streams (scratch / direct), filter blocks and scratch begin (host prefix sums)
 struct BlChunk { uint64_t strm0, dstrm0, blk0, slot0, cslot0; int64_t err; uint32_t nstr, ndir, nblk, nbytes; };
 // the per-stream rows: the engine's batch and the stored streams' copy_segments rows; rows [0, na) are the scratch streams of all
-// chunks, [na, na + nd) the direct ones
+// chunks, [na, na + nd) the direct ones; in either range the streams of LZ4 chunks come first, those of BloscLZ chunks behind them
 struct BlRows { BatchRows b; uint64_t *cp_src, *cp_dst, *cp_len; };
 constexpr size_t kBlRowWords = 8;
 inline BlRows bl_rows(uint64_t* base, size_t ns) {
@@ -41,7 +42,7 @@ __host__ __device__ inline uint32_t bl_block_bytes(uint32_t nbytes, uint32_t blo
 
 __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                                                                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
-                                                                BlCount* cnt, const BlChunk* tab, BlRows r, BloscBlockRow* blocks, uint8_t* scratch) {
+                                                                BlCount* cnt, const BlChunk* tab, BlRows r, BloscBlockRow* blocks, uint8_t* scratch, uint32_t rflags) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     const uint8_t* in = in_base + in_off[i];
@@ -53,9 +54,9 @@ __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, cons
         c.err = blosc_walk(in, len, h, [&](const BloscStream& s) {
             if (direct(s.block)) c.ndir++; else c.nstr++;
             if (!s.stored && s.dst_len > c.maxlen) c.maxlen = s.dst_len;
-        });
+        }, rflags);
         if (c.err == 0 && h.nbytes > out_cap[i]) c.err = CJ_E_OUT_TOO_SMALL;
-        c.nbytes = h.nbytes;
+        c.nbytes = h.nbytes; c.format = h.format;
         if (c.err != 0 || h.nbytes == 0) { c.nstr = 0; c.ndir = 0; c.maxlen = 0; }
         else if (h.flags & kBloscMemcpyed) { c.nblk = (h.nbytes + kMemcpyPiece - 1) / kMemcpyPiece; c.tiles = kMemcpyPiece / kBloscTileBytes; }
         else {
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, cons
     }
     const BlChunk ch = tab[i];
     if (ch.err != 0 || ch.nstr + ch.ndir + ch.nblk == 0) return;
-    if (blosc_header(in, len, h) != 0) return;                        // (pass 1 accepted it: cannot happen)
+    if (blosc_header(in, len, h, rflags) != 0) return;                // (pass 1 accepted it: cannot happen)
     uint8_t* dst = out_base + out_off[i];
     if (h.flags & kBloscMemcpyed) {
         for (uint32_t k = 0; k < ch.nblk; k++) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, cons
         r.b.in_off[g] = at; r.b.in_len[g] = s.stored ? 0 : s.src_len;
         r.b.out_off[g] = to; r.b.out_cap[g] = s.stored ? 0 : s.dst_len;
         r.cp_src[g] = (uint64_t)(uintptr_t)(in_base + at); r.cp_dst[g] = to; r.cp_len[g] = s.stored ? s.dst_len : 0;
-    });
+    }, rflags);
     uint64_t k = ch.blk0;
     for (uint32_t b = 0; b < h.nblocks; b++) {
         if (direct(b)) continue;
@@ -197,11 +198,12 @@ __global__ __launch_bounds__(kBlockThreads) void bl_assemble_kernel(uint32_t n, 
 }
 
 // nbytes of each chunk after the header checks (cj_blosc_chunk_sizes_*): one lane per chunk
-__global__ __launch_bounds__(kBlockThreads) void bl_sizes_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result) {
+__global__ __launch_bounds__(kBlockThreads) void bl_sizes_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result,
+                                                                 uint32_t rflags) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     BloscHeader h;
-    const int64_t err = blosc_header(in_base + in_off[i], (size_t)in_len[i], h);
+    const int64_t err = blosc_header(in_base + in_off[i], (size_t)in_len[i], h, rflags);
     result[i] = err != 0 ? err : (int64_t)h.nbytes;
 }
 
@@ -214,6 +216,9 @@ using cj::BlCount;
 
 inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 inline dim3 per_lane(size_t n) { return dim3((uint32_t)((n + cj::kBlockThreads - 1) / cj::kBlockThreads)); }
+
+// flags: 0 or CJ_BLOSC_FLAG_READ_BLOSCLZ (bit 0 stays reserved), the latter for reading only
+bool flags_ok(uint32_t flags, bool reading) { return flags == 0 || (reading && flags == CJ_BLOSC_FLAG_READ_BLOSCLZ); }
 
 int params_check(cj_op op, const cj_blosc_params* p) {
     if (op == CJ_OP_DECOMPRESS) return 0;
@@ -230,8 +235,16 @@ int run_rows(cj_engine* e, cj_op op, uint32_t flags, const uint8_t* in_base, uin
     return cj::launch(e, CJ_CODEC_LZ4_BLOCK, op, a, s);
 }
 
+// the BloscLZ streams in rows [a0, a0 + k) of r: one wavefront each
+void run_blosclz_rows(const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, size_t a0, size_t k, hipStream_t s) {
+    if (k == 0) return;
+    cj::BatchArgs a;
+    cj::fill_args(a, 0, in_base, out_base, r.sub(a0, k));
+    cj::launch_blosclz_decode(a, s);
+}
+
 int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const cj_blosc_params* params, hipStream_t s) {
+                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const cj_blosc_params* params, uint32_t rflags, hipStream_t s) {
     cj::FbTurn turn(e, s);                     // (the frame batches' scratch: chunk batches and frame batches on one engine run one after another)
     if (turn.rc != 0) return turn.rc;
     const bool dec = op == CJ_OP_DECOMPRESS;
@@ -243,24 +256,28 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     // the one wait: stream and block counts (decompress) / lengths (compress) size the rows, the scratch and the grids
     if (dec) {
         hipLaunchKernelGGL(cj::bl_walk_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
-                           (BlCount*)e->d_fb.p, (const BlChunk*)nullptr, cj::BlRows{}, (cj::BloscBlockRow*)nullptr, (uint8_t*)nullptr);
+                           (BlCount*)e->d_fb.p, (const BlChunk*)nullptr, cj::BlRows{}, (cj::BloscBlockRow*)nullptr, (uint8_t*)nullptr, rflags);
         HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
         HIP_TRY(hipMemcpyAsync(h_cnt, e->d_fb.p, cnt_bytes, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     } else {
         HIP_TRY(hipMemcpyAsync(h_cnt, in_len, 8 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     }
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    uint64_t na = 0, nd = 0, nb = 0, slot = 0, cslot = 0;
+    // na / nd: scratch / direct streams of LZ4 chunks, za / zd: of BloscLZ chunks (a chunk's streams are all of its one format)
+    uint64_t na = 0, nd = 0, za = 0, zd = 0, nb = 0, slot = 0, cslot = 0;
     uint32_t maxlen = 0, tiles = 1;
     std::memset(h_tab, 0, n * sizeof(BlChunk));
+    const auto blosclz = [&](size_t i) { return dec && reinterpret_cast<const BlCount*>(h_cnt)[i].format == cj::kBloscFormatBlosclz; };
     for (size_t i = 0; i < n; i++) {
         BlChunk& c = h_tab[i];
-        c.strm0 = na; c.dstrm0 = nd; c.blk0 = nb; c.slot0 = slot; c.cslot0 = cslot;
+        const bool z = blosclz(i);
+        c.strm0 = z ? za : na; c.dstrm0 = z ? zd : nd; c.blk0 = nb; c.slot0 = slot; c.cslot0 = cslot;
         if (dec) {
             const BlCount& k = reinterpret_cast<const BlCount*>(h_cnt)[i];
             c.err = k.err; c.nstr = k.nstr; c.ndir = k.ndir; c.nblk = k.nblk; c.nbytes = k.nbytes;
             if (k.scratch) slot += up16(k.nbytes);
-            maxlen = std::max(maxlen, k.maxlen); tiles = std::max(tiles, k.tiles);
+            if (!z) maxlen = std::max(maxlen, k.maxlen);              // (the engine's size classes are about the LZ4 streams alone)
+            tiles = std::max(tiles, k.tiles);
         } else {
             const uint64_t len = reinterpret_cast<const uint64_t*>(h_cnt)[i];
             if (len > cj::kBloscMaxBytes) { c.err = CJ_E_INPUT_TOO_LARGE; continue; }
@@ -277,11 +294,15 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
             if (c.nblk) { slot += up16(c.nbytes); tiles = std::max(tiles, cj::blosc_tiles(params->typesize, l.blocksize)); }
             cslot += (uint64_t)full * per * cj::bl_enc_room(l.blocksize / per) + (rest ? cj::bl_enc_room(rest) : 0);
         }
-        na += c.nstr; nd += c.ndir; nb += c.nblk;
+        (z ? za : na) += c.nstr; (z ? zd : nd) += c.ndir; nb += c.nblk;
     }
-    const uint64_t ns = na + nd;
+    const uint64_t ns = na + za + nd + zd;
     if (ns > 0xFFFFFFF0ull || nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    for (size_t i = 0; i < n; i++) h_tab[i].dstrm0 += na;                   // (the direct streams' rows lie behind all scratch streams')
+    // rows: scratch LZ4 | scratch BloscLZ | direct LZ4 | direct BloscLZ
+    for (size_t i = 0; i < n; i++) {
+        const bool z = blosclz(i);
+        h_tab[i].strm0 += z ? na : 0; h_tab[i].dstrm0 += na + za + (z ? nd : 0);
+    }
     // d_fb: chunk table | stream rows | block rows | scratch (the filtered images of chunks with transposed blocks) | compressed slots (compress)
     const size_t o_rows = tab, o_blocks = o_rows + cj::kBlRowWords * 8 * ns, o_scr = up16(o_blocks + nb * sizeof(cj::BloscBlockRow));
     const size_t o_packed = o_scr + slot + 16;
@@ -296,13 +317,16 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     HIP_TRY(hipMemcpyAsync(d_tab, h_tab, n * sizeof(BlChunk), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     if (dec) {
         hipLaunchKernelGGL(cj::bl_walk_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
-                           (BlCount*)nullptr, (const BlChunk*)d_tab, r, blocks, scratch);
+                           (BlCount*)nullptr, (const BlChunk*)d_tab, r, blocks, scratch, rflags);
         const uint32_t flags = maxlen <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : maxlen <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : maxlen > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
         // streams of transposed blocks into the scratch, the others straight into the callers' slots
+        const uint64_t ta = na + za;                                        // all scratch streams
         if ((rc = run_rows(e, op, flags, in_base, scratch, r.b, 0, na, s)) != 0) return rc;
-        if ((rc = run_rows(e, op, flags, in_base, out_base, r.b, na, nd, s)) != 0) return rc;
-        cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)na, s);
-        cj::launch_copy_segments(r.cp_src + na, out_base, r.cp_dst + na, r.cp_len + na, nullptr, 0, (uint32_t)nd, s);
+        if ((rc = run_rows(e, op, flags, in_base, out_base, r.b, ta, nd, s)) != 0) return rc;
+        run_blosclz_rows(in_base, scratch, r.b, na, za, s);
+        run_blosclz_rows(in_base, out_base, r.b, ta + nd, zd, s);
+        cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)ta, s);
+        cj::launch_copy_segments(r.cp_src + ta, out_base, r.cp_dst + ta, r.cp_len + ta, nullptr, 0, (uint32_t)(nd + zd), s);
         hipLaunchKernelGGL(cj::bl_verdict_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, r, result);
         cj::launch_blosc_filter(blocks, nb, tiles, false, result, s);
     } else {
@@ -333,7 +357,7 @@ int64_t cj_blosc_chunk_info(const uint8_t* in, size_t n, cj_blosc_info* info) {
 int cj_blosc_batch_device(cj_engine* e, cj_op op, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                           const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, size_t n, const cj_blosc_params* params, uint32_t flags,
                           void* hip_stream) {
-    if (flags != 0 || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
+    if (!flags_ok(flags, op == CJ_OP_DECOMPRESS) || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
     const int pc = params_check(op, params);
     if (pc != 0) return pc;
     if (n == 0) return 0;
@@ -341,12 +365,12 @@ int cj_blosc_batch_device(cj_engine* e, cj_op op, const uint8_t* in_base, const 
     if (!e) e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return blosc_batch(e, op, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, params, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    return blosc_batch(e, op, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, params, flags, hip_stream ? (hipStream_t)hip_stream : e->stream);
 }
 
 int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
                         uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, const cj_blosc_params* params) {
-    if (flags != 0 || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
+    if (!flags_ok(flags, op == CJ_OP_DECOMPRESS) || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
     const int pc = params_check(op, params);
     if (pc != 0) return pc;
     if (n == 0) return 0;
@@ -356,7 +380,7 @@ int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n, const 
     if (!e) e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
     return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return blosc_batch(e, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, params, s);
+        return blosc_batch(e, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, params, flags, s);
     });
 }
 
@@ -376,19 +400,19 @@ int64_t cj_blosc_chunk_compress(const uint8_t* in, size_t n, uint8_t* out, size_
 
 int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                                 int64_t* result, void* hip_stream) {
-    if (flags != 0 || n > 0xFFFFFFF0ull || (n && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
+    if (!flags_ok(flags, true) || n > 0xFFFFFFF0ull || (n && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
     if (n == 0) return 0;
     if (!e) e = cj::default_engine();
     if (!e) return CJ_E_NO_DEVICE;
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
     hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, hip_stream ? (hipStream_t)hip_stream : e->stream, (uint32_t)n,
-                       in_base, in_off, in_len, result);
+                       in_base, in_off, in_len, result, flags);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
 
 int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
-    if (flags != 0 || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
+    if (!flags_ok(flags, true) || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
     if (n == 0) return 0;
     for (size_t i = 0; i < n; i++)
         if (in_lens[i] && !in_ptrs[i]) return CJ_E_BAD_ARG;
@@ -409,7 +433,7 @@ int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n, const uint
     HIP_TRY(hipMemcpyAsync(e->d_in.p, e->h_in.p, 16 * n, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(d_rows, h_rows, 2 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, e->stream, (uint32_t)n, (const uint8_t*)e->d_in.p, d_rows, d_rows + n,
-                       (int64_t*)(d_rows + 2 * n));
+                       (int64_t*)(d_rows + 2 * n), flags);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(result, d_rows + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);

@@ -29,4 +29,8 @@ CJ_HD inline uint32_t blosc_tiles(uint32_t typesize, uint32_t bytes) {
 // chunk with a negative one are skipped (nullptr: none are).  Enqueue only.
 void launch_blosc_filter(const BloscBlockRow* rows, size_t n_rows, uint32_t tiles_max, bool forward, const int64_t* gate, hipStream_t s);
 
+// blosclz_decode.hip: one wavefront per row of a decodes a BloscLZ stream of in_len bytes into exactly out_cap bytes: result = out_cap or
+// CJ_E_CORRUPT; a row with out_cap == 0 is skipped (result 0).  Nothing is written beyond out_off + out_cap.  Enqueue only.
+void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
+
 }  // namespace cj
