@@ -73,6 +73,10 @@ SYMBOLS = {
     "cj_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_frame_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_frame_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_dict_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cj_dict_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "cj_dict_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cj_dict_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _sz]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_blosc_chunk_max_compressed_len": (_sz, [_sz]),
     "cj_blosc_chunk_info": (_i64, [_vp, _sz, _vp]),
@@ -101,6 +105,7 @@ BENCH_SYMBOLS = {
     "cj_debug_big_scratch_bytes": (C.c_uint64, [_vp]),
     "cj_debug_xxh32_device": (_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
+    "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
 }
 
 _lib = None
@@ -150,8 +155,9 @@ class Kind:
     """One kind of batch: its four C symbols, and how `what` (a CODEC_* / FORMAT_*; Blosc chunks have none) and `params` (a BloscParams
     or None) enter their argument lists.  i = (in_base, in_off, in_len) / (in_ptrs, in_lens); o = (out_base, out_off, out_cap)."""
 
-    def __init__(self, host, device, sizes_host, sizes_device, blosc=False):
+    def __init__(self, host, device, sizes_host, sizes_device, blosc=False, dictionary=False):
         self.host, self.device, self.sizes_host, self.sizes_device, self.blosc = host, device, sizes_host, sizes_device, blosc
+        self.dictionary = dictionary                # the calls take (dict, dict_len) / (dict_len,) behind result: `params` = that tuple
 
     def read_flags(self, blosclz=False):
         """the flags word of a reading call of this kind: `blosclz` (Blosc chunks only) asks for BloscLZ streams to be read too"""
@@ -162,15 +168,16 @@ class Kind:
     def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
         if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)
             return (h, op) + i + o + (result, n, C.byref(params) if params is not None else None, flags, stream)
-        return (h, what, op, flags, n) + i + o + (result, stream)
+        return (h, what, op, flags, n) + i + o + (result,) + (tuple(params) if self.dictionary else ()) + (stream,)
 
-    def sizes_args(self, h, what, flags, n, *rest):
-        """rest = i + (result,) [+ (stream,)]"""
-        return ((h, flags, n) if self.blosc else (h, what, flags, n)) + rest
+    def sizes_args(self, h, what, flags, n, body, tail=(), dict_len=0):
+        """body = i + (result,); tail = (stream,) for the device form; dict_len (dictionary batches only) goes between them"""
+        return ((h, flags, n) if self.blosc else (h, what, flags, n)) + body + ((dict_len,) if self.dictionary else ()) + tail
 
 
 BLOCKS = Kind("cj_batch_host", "cj_batch_device", "cj_batch_sizes_host", "cj_batch_sizes_device")
 FRAMES = Kind("cj_frame_batch_host", "cj_frame_batch_device", "cj_frame_batch_sizes_host", "cj_frame_batch_sizes_device")
+DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_host", "cj_dict_batch_sizes_device", dictionary=True)
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
 
 

@@ -50,19 +50,58 @@ def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, pa
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
 
 
-def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=None, out=None):
+def _run_dict(op, flags, inputs, out_caps, devices, out, dictionary):
+    """_run for LZ4 blocks against one dictionary (cj_dict_batch_host; any bytes-like, borrowed): the same results and outputs"""
+    import ctypes as C
+    import numpy as np
+    d = np.frombuffer(dictionary, dtype=np.uint8)
+    n = len(inputs)
+    offsets, run = [], 0
+    for c in out_caps:
+        offsets.append(run); run += int(c)
+    own = out is None
+    if own:
+        out = bytearray(run)
+    mv = memoryview(out).cast("B")
+    if mv.readonly or mv.nbytes < run:
+        raise ValueError("cramjam_amd.batch: out must be a writable buffer of at least %d bytes" % run)
+    base = np.frombuffer(mv, dtype=np.uint8).ctypes.data if mv.nbytes else 0
+
+    def work(dev, idx):
+        arrs = [np.frombuffer(inputs[i], dtype=np.uint8) for i in idx]          # borrowed, not copied
+        k = len(arrs)
+        iptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        ilens = (C.c_size_t * max(k, 1))(*[a.size for a in arrs])
+        optrs = (C.c_void_p * max(k, 1))(*[base + offsets[i] for i in idx])
+        ocaps = (C.c_size_t * max(k, 1))(*[int(out_caps[i]) for i in idx])
+        res = np.empty(max(k, 1), np.int64)
+        N.check(N.lib().cj_dict_batch_host(_engine(dev).h, N.CODEC_LZ4_BLOCK, op, flags, k, iptrs, ilens, optrs, ocaps, res.ctypes.data,
+                                           d.ctypes.data if d.size else None, d.size))
+        return ([int(x) for x in res[:k]],)
+    res, = _shard(devices, n, work)
+    views = [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
+    return res, ([bytes(v) for v in views] if own else views)
+
+
+def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=None, out=None, dictionary=None):
     """decode many LZ4 blocks; returns (results, outputs) with results[i] = length or a negative CJ_E_* code.
     output_lens=None: the sizes are asked for first (lz4_block_sizes: the prefix, or for raw blocks the walk of their token chains):
     a block the query accepts gets exactly its size as capacity, a block it rejects gets the query's code as its result and an empty
     output.  The input then crosses the link TWICE (once for the query, once for the decode): 16 384 x 64 KiB chunks decode at
     0.52 of the rate (75.7 ms against 39.7 ms) of a call that passes output_lens — pass the lengths where the container stores them.
     out: ONE writable buffer (bytearray, numpy array) of at least sum(output_lens) bytes — the outputs are then memoryviews into it
-    (chunk i behind chunk i - 1's capacity) instead of new `bytes` objects: the C-ABI's host rate without an allocation per chunk."""
+    (chunk i behind chunk i - 1's capacity) instead of new `bytes` objects: the C-ABI's host rate without an allocation per chunk.
+    dictionary: bytes-like — the ONE dictionary every block of the call was written against (LZ4_loadDict + LZ4_compress_fast_continue;
+    only its last 64 KiB count).  Such a batch always runs one wavefront per block.  None: no dictionary."""
     flags = N.FLAG_LZ4_SIZE_PREFIX if store_size else 0
+    if dictionary is None:
+        run = lambda caps: _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, caps, devices, out)
+    else:
+        run = lambda caps: _run_dict(N.OP_DECOMPRESS, flags, blocks, caps, devices, out, dictionary)
     if output_lens is not None:
-        return _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, output_lens, devices, out)
-    sizes = lz4_block_sizes(blocks, store_size, devices)
-    res, outs = _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, [max(s, 0) for s in sizes], devices, out)
+        return run(output_lens)
+    sizes = lz4_block_sizes(blocks, store_size, devices, dictionary)
+    res, outs = run([max(s, 0) for s in sizes])
     bad = [i for i, s in enumerate(sizes) if s < 0]
     if bad:
         res = list(res)
@@ -72,10 +111,14 @@ def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=No
     return res, outs
 
 
-def lz4_compress_blocks(chunks, store_size=True, devices=None, out=None):
-    """out: as in lz4_decompress_blocks; it has to hold sum(compress_block_bound(len(chunk))) bytes"""
+def lz4_compress_blocks(chunks, store_size=True, devices=None, out=None, dictionary=None):
+    """out: as in lz4_decompress_blocks; it has to hold sum(compress_block_bound(len(chunk))) bytes.
+    dictionary: bytes-like — every chunk may refer to its last 64 KiB (what LZ4_decompress_safe_usingDict reads, and
+    lz4_decompress_blocks(..., dictionary=...)); chunks of at most 65 536 bytes, a longer one gets -1 as its result."""
     L = N.lib()
     caps = [L.cj_lz4_block_compress_bound(len(c), 1 if store_size else 0) for c in chunks]
+    if dictionary is not None:
+        return _run_dict(N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, chunks, caps, devices, out, dictionary)
     return _run(N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, chunks, caps, devices, out)
 
 
@@ -301,11 +344,15 @@ class _DeviceCall:
             v.release()
 
 
-def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, params=None):
+def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, params=None, dictionary=None):
+    """dictionary (LZ4 blocks only): a device buffer — the batch goes through N.DICT with (its address, its length) behind result"""
     call = _DeviceCall(stream, sync)
     try:
         vin, vout = call.buffer(inp), call.buffer(out)
         eng = call.engine(device, vin, vout)
+        if dictionary is not None:
+            vd = call.buffer(dictionary)
+            kind, params = N.DICT, (vd.ptr or None, vd.nbytes)
         i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
         o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
         p_res = call.result(result)
@@ -315,20 +362,24 @@ def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_
         call.close()
 
 
-def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream, sync):
+def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream, sync, dictionary=None):
     call = _DeviceCall(stream, sync)
     try:
         vin = call.buffer(inp)
         eng = call.engine(device, vin)
+        dict_len = 0
+        if dictionary is not None:                  # (only its length enters the walk)
+            kind, dict_len = N.DICT, call.buffer(dictionary).nbytes
         p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
         p_res = call.result(result)
-        N.check(getattr(N.lib(), kind.sizes_device)(*kind.sizes_args(eng.h, what, flags, call.n, vin.ptr, p_in_off, p_in_len, p_res, stream)))
+        N.check(getattr(N.lib(), kind.sizes_device)(*kind.sizes_args(eng.h, what, flags, call.n, (vin.ptr, p_in_off, p_in_len, p_res), (stream,), dict_len)))
         return call.finish(p_res, result)
     finally:
         call.close()
 
 
-def lz4_decompress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, store_size=False, result=None, device=None, stream=None, sync=True):
+def lz4_decompress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, store_size=False, result=None, device=None, stream=None, sync=True,
+                                 dictionary=None):
     """Decode a batch of LZ4 blocks that already sits in HBM (reference call per buffer: src/lz4.rs:78-95).
 
     inp / out: device byte buffers (torch tensor, cupy array, anything with __cuda_array_interface__ or __dlpack__);
@@ -339,15 +390,18 @@ def lz4_decompress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, sto
     batch behind the producer of the buffers; without it the batch runs on the engine's own stream and the caller makes sure the
     buffers are ready (torch.cuda.synchronize()).  sync=False returns right after submission (device-resident metadata and result
     only).  In a process that also uses torch, import torch FIRST: both link libamdhip64.so.7, torch loads its own copy by path, and
-    two HIP runtimes in one process do not share a device."""
+    two HIP runtimes in one process do not share a device.
+    dictionary: a device byte buffer — the one dictionary of the batch, as in lz4_decompress_blocks."""
     return _device_batch(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
-                         inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+                         inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, dictionary=dictionary)
 
 
-def lz4_compress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, store_size=True, result=None, device=None, stream=None, sync=True):
-    """Compress a device-resident batch into LZ4 blocks (src/lz4.rs:113-131); out_cap[i] >= cramjam.lz4.compress_block_bound(in_len[i])."""
+def lz4_compress_blocks_device(inp, in_off, in_len, out, out_off, out_cap, store_size=True, result=None, device=None, stream=None, sync=True,
+                               dictionary=None):
+    """Compress a device-resident batch into LZ4 blocks (src/lz4.rs:113-131); out_cap[i] >= cramjam.lz4.compress_block_bound(in_len[i]).
+    dictionary: a device byte buffer, as in lz4_compress_blocks (chunks of at most 65 536 bytes)."""
     return _device_batch(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0,
-                         inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+                         inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, dictionary=dictionary)
 
 
 def snappy_decompress_raw_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
@@ -399,11 +453,12 @@ def snappy_compress_framed_many_device(inp, in_off, in_len, out, out_off, out_ca
 LZ4_SIZE_SLACK = 12
 
 
-def lz4_block_sizes_device(inp, in_off, in_len, store_size=False, result=None, device=None, stream=None, sync=True):
+def lz4_block_sizes_device(inp, in_off, in_len, store_size=False, result=None, device=None, stream=None, sync=True, dictionary=None):
     """Decoded sizes of a device-resident batch of LZ4 blocks.  store_size=True: the u32 prefix of each block (header only).
     store_size=False (raw blocks: Parquet LZ4_RAW, ORC, Arrow IPC): the token chain of every block is walked to its end — the exact
-    size the decoder produces, CJ_E_CORRUPT (-7) for a block it would reject with any capacity."""
-    return _device_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, inp, in_off, in_len, result, device, stream, sync)
+    size the decoder produces, CJ_E_CORRUPT (-7) for a block it would reject with any capacity.
+    dictionary: the device buffer of the batch's dictionary (only its length enters: matches may reach that far behind a block's start)."""
+    return _device_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, inp, in_off, in_len, result, device, stream, sync, dictionary)
 
 
 def snappy_raw_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
@@ -422,7 +477,7 @@ def snappy_framed_sizes_device(inp, in_off, in_len, result=None, device=None, st
     return _device_sizes(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, 0, inp, in_off, in_len, result, device, stream, sync)
 
 
-def _host_sizes(kind, what, flags, buffers, devices):
+def _host_sizes(kind, what, flags, buffers, devices, dict_len=0):
     """sharded like _run: buffer i -> engine i mod G"""
     import numpy as np
 
@@ -432,14 +487,17 @@ def _host_sizes(kind, what, flags, buffers, devices):
         ptrs = (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
         lens = (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
         res = np.empty(k, np.int64)
-        N.check(getattr(N.lib(), kind.sizes_host)(*kind.sizes_args(_engine(dev).h, what, flags, k, ptrs, lens, res.ctypes.data)))
+        N.check(getattr(N.lib(), kind.sizes_host)(*kind.sizes_args(_engine(dev).h, what, flags, k, (ptrs, lens, res.ctypes.data), (), dict_len)))
         return ([int(x) for x in res],)
     return _shard(devices, len(buffers), work)[0]
 
 
-def lz4_block_sizes(blocks, store_size=False, devices=None):
+def lz4_block_sizes(blocks, store_size=False, devices=None, dictionary=None):
     """decoded sizes of many LZ4 blocks held on the host (list of ints; negative = CJ_E_* code), as lz4_block_sizes_device"""
-    return _host_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, blocks, devices)
+    flags = N.FLAG_LZ4_SIZE_PREFIX if store_size else 0
+    if dictionary is not None:
+        return _host_sizes(N.DICT, N.CODEC_LZ4_BLOCK, flags, blocks, devices, memoryview(dictionary).nbytes)
+    return _host_sizes(N.BLOCKS, N.CODEC_LZ4_BLOCK, flags, blocks, devices)
 
 
 def snappy_raw_sizes(blocks, devices=None):

@@ -106,6 +106,10 @@ struct cj_engine {
     cj::DevBuf d_fb;
     cj::PinnedBuf h_fb;
     hipEvent_t fb_free = nullptr;  // ... recorded after the last kernel that uses them
+    std::mutex dict_mu;            // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows
+    cj::DevBuf d_dict_stage;
+    hipEvent_t dict_free = nullptr;   // ... recorded after the last kernel that uses them
+    cj::DevBuf d_dict;             // ... the dictionary of a host batch (under `mu`)
 };
 
 namespace cj {

@@ -507,6 +507,8 @@ void cj_engine_destroy(cj_engine* e) {
     if (e->scratch_free) (void)hipEventDestroy(e->scratch_free);
     e->d_fb.release(); e->h_fb.release();
     if (e->fb_free) (void)hipEventDestroy(e->fb_free);
+    e->d_dict_stage.release(); e->d_dict.release();
+    if (e->dict_free) (void)hipEventDestroy(e->dict_free);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }

@@ -109,6 +109,15 @@ CJ_HD inline bool lz4_size_commit(const SizeSeq& s, uint64_t& op) {
     op += s.mlen;
     return true;
 }
+// ... of a block written against a dictionary (lz4_dict.hip): a match may also reach `hist` <= 65536 bytes behind the block's start.
+// Only the dictionary's length enters, not its bytes.
+CJ_HD inline bool lz4_size_commit(const SizeSeq& s, uint64_t& op, uint32_t hist) {
+    op += s.lit;
+    if (s.last) return true;
+    if (s.offset == 0u || (uint64_t)s.offset > op + hist) return false;
+    op += s.mlen;
+    return true;
+}
 
 // the size of a block that walked to its end: no capacity the decoder accepts holds more than kLz4OutMax
 CJ_HD inline int64_t lz4_size_verdict(uint64_t size) { return size > kLz4OutMax ? (int64_t)CJ_E_PREFIX_TOO_BIG : (int64_t)size; }
@@ -121,6 +130,19 @@ CJ_HD inline int64_t lz4_size_walk(const Rd& rd, const Ff& ff, uint32_t ip, uint
     for (;;) {
         SizeSeq s;
         if (!lz4_size_seq(rd, ff, ip, iend, s) || !lz4_size_commit(s, op)) return CJ_E_CORRUPT;
+        if (s.last) break;
+        ip = s.next;
+    }
+    return lz4_size_verdict(op);
+}
+// ... with a dictionary of which `hist` bytes count
+template <class Rd, class Ff>
+CJ_HD inline int64_t lz4_size_walk(const Rd& rd, const Ff& ff, uint32_t ip, uint32_t iend, uint32_t hist) {
+    if (ip >= iend) return CJ_E_CORRUPT;
+    uint64_t op = 0;
+    for (;;) {
+        SizeSeq s;
+        if (!lz4_size_seq(rd, ff, ip, iend, s) || !lz4_size_commit(s, op, hist)) return CJ_E_CORRUPT;
         if (s.last) break;
         ip = s.next;
     }

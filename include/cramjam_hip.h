@@ -303,6 +303,40 @@ CJ_API int cj_frame_batch_sizes_device(cj_engine* e, cj_format fmt, uint32_t fla
 CJ_API int cj_frame_batch_sizes_host(cj_engine* e, cj_format fmt, uint32_t flags, size_t n_frames,
                                      const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
 
+/* Batches of LZ4 blocks against ONE dictionary shared by every chunk of the call: the blocks LZ4_loadDict + LZ4_compress_fast_continue
+ * write and LZ4_decompress_safe_usingDict reads (the block stores of small records: RocksDB-style blocks, message logs, column pages).
+ * Arguments, addressing, alignment, result[i] and stream rules are cj_batch_device's / cj_batch_host's / the size queries'; the
+ * dictionary (dict_dev: device memory, dict_host: host memory, uploaded once per call) is borrowed for the call.  Only its last
+ * 65 536 bytes count, as in liblz4; dict_len == 0 IS the plain call (cj_batch_device, cj_batch_host, cj_batch_sizes_*), result for
+ * result and byte for byte.  e == NULL: the default engine of device 0.
+ *   codec       CJ_CODEC_LZ4_BLOCK.  Snappy has no dictionaries: CJ_E_BAD_ARG.
+ *   flags       0 or CJ_FLAG_LZ4_SIZE_PREFIX.  Every other bit — the mapping overrides included — is REFUSED with CJ_E_BAD_ARG: a
+ *               dictionary batch has one mapping (one wavefront per chunk; the workgroup decoders hold no dictionary window).
+ *   decompress  lz4_wave_decode's rules; a match of `offset` > the bytes produced so far begins offset - produced bytes before the
+ *               dictionary's end.  CJ_E_CORRUPT: offset 0, or offset > produced + min(dict_len, 65536).  Chunks of any size.
+ *   sizes       the walk of cj_batch_sizes_device with that offset rule: it needs dict_len only, not the bytes.  Same contract with the
+ *               decode (CJ_LZ4_SIZE_SLACK).  With CJ_FLAG_LZ4_SIZE_PREFIX: the prefix, as without a dictionary.
+ *   compress    chunks of at most 65 536 bytes; a longer one gets CJ_E_INPUT_TOO_LARGE in its own result[i].  Capacities as for
+ *               cj_batch_device (cj_lz4_block_compress_bound).  The engine stages `dictionary tail | chunk` per chunk in its scratch (in
+ *               slices of at most 1 GiB) and runs the linked-block encoder of cj_lz4_frame_compress_linked over it: every chunk indexes
+ *               the dictionary again, a pass over n x (min(dict_len, 65536) + chunk) bytes.
+ *   a null dict with dict_len > 0, an unknown op, a null batch pointer with n_chunks > 0: CJ_E_BAD_ARG.  n_chunks == 0 succeeds.
+ * The _device calls only enqueue (like every call, one that has to GROW the engine's scratch — compress — waits for its previous user
+ * while it reallocates).  The _host calls are cj_batch_host's one-shot staging, synchronous. */
+CJ_API int cj_dict_batch_device(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n_chunks,
+                                const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                int64_t* result, const uint8_t* dict_dev, size_t dict_len, void* hip_stream);
+CJ_API int cj_dict_batch_host(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n_chunks,
+                              const uint8_t* const* in_ptrs, const size_t* in_lens,
+                              uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result,
+                              const uint8_t* dict_host, size_t dict_len);
+CJ_API int cj_dict_batch_sizes_device(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks,
+                                      const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                      int64_t* result, size_t dict_len, void* hip_stream);
+CJ_API int cj_dict_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks,
+                                    const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result, size_t dict_len);
+
 /* =====================================================================================
  * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706
  * max_compressed_len): LZ4 streams behind a byte or bit transposition.  The transposition runs in its own kernels

@@ -37,6 +37,10 @@ CJ_API int cj_debug_xxh32_device(cj_engine* e, const uint8_t* d_base, const uint
 CJ_API int cj_debug_blosc_filter(cj_engine* e, int forward, uint32_t filter, uint32_t typesize, const uint8_t* d_src, uint8_t* d_dst,
                                  uint64_t bytes, uint64_t stride, size_t n_blocks, double* ms);
 
+/* dictionary compress (cj_dict_batch_*): the bytes of staged `dictionary tail | chunk` slots per slice (0 = the default, 1 GiB); returns the
+ * previous value.  Tests force more than one slice with it. */
+CJ_API uint64_t cj_debug_dict_stage_budget(uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif
