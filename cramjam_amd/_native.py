@@ -146,8 +146,8 @@ def _with_hip_error(msg):
 
 
 def _batch_host_addr(name="cj_batch_host"):
-    """address of cj_batch_host (or of cj_frame_batch_host, which has the same signature) in the library the engines of this process
-    come from (CJ_HIP_LIB may name a tuning variant; the CPython module links the product library)"""
+    """address of a host-batch entry (a Kind's .host) in the library the engines of this process come from (CJ_HIP_LIB may name a tuning
+    variant; the CPython module links the product library)"""
     return C.cast(getattr(lib(), name), C.c_void_p).value
 
 
@@ -239,23 +239,28 @@ class Engine:
         check(lib().cj_frame_batch_device(self.h, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off,
                                           out_cap, result, stream))
 
-    def _host(self, entry, codec, op, flags, args, fn, params):
+    def _host(self, entry, codec, op, flags, args, fn, params, dictionary):
         """entry: batch_host or batch_host_into of the CPython host layer (the engine scatters straight into the bytes objects / the buffer).
-        params: the bytes of a cj_blosc_params (b"" = decompress) — the batch is one of Blosc chunks, codec is not used"""
+        The call's signature follows from what is given: params, the bytes of a cj_blosc_params (b"" = decompress) — a batch of Blosc
+        chunks, codec is not used; dictionary, bytes-like (borrowed) — LZ4 blocks against it; neither — fn, one of the two entries of
+        cj_batch_host's signature.  Both: ValueError."""
         from . import _cramjam
-        tail = (_batch_host_addr(fn),) if params is None else (_batch_host_addr(BLOSC.host), params)
+        if dictionary is not None:
+            fn = DICT.host
+        elif params is not None:
+            fn, codec = BLOSC.host, 0
         try:
-            return getattr(_cramjam, entry)(self.h.value or 0, 0 if params is not None else int(codec), int(op), int(flags), *args, *tail)
+            return getattr(_cramjam, entry)(self.h.value or 0, int(codec), int(op), int(flags), *args, _batch_host_addr(fn), params, dictionary)
         except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
             raise EngineError(_with_hip_error(str(ex))) from None
 
-    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host", params=None):
+    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host", params=None, dictionary=None):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
         Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
         fn: "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
-        return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params)
+        return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params, dictionary)
 
-    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host", params=None):
+    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host", params=None, dictionary=None):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
-        return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params)
+        return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params, dictionary)

@@ -36,51 +36,20 @@ def _pick(seq, idx):
 
 
 def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None):
-    """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*) or N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress).
+    """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress) or
+    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed).
     out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
+    tail = {"dictionary": params} if kind is N.DICT else {"params": params}
     if out is None:
-        return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind.host, params))
+        return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind.host, **tail))
     offsets, run = [], 0
     for c in out_caps:
         offsets.append(run); run += int(c)
     mv = memoryview(out).cast("B")
     res, = _shard(devices, n, lambda dev, idx: (_engine(dev).batch_host_into(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), out,
-                                                                             _pick(offsets, idx), kind.host, params),))
+                                                                             _pick(offsets, idx), kind.host, **tail),))
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
-
-
-def _run_dict(op, flags, inputs, out_caps, devices, out, dictionary):
-    """_run for LZ4 blocks against one dictionary (cj_dict_batch_host; any bytes-like, borrowed): the same results and outputs"""
-    import ctypes as C
-    import numpy as np
-    d = np.frombuffer(dictionary, dtype=np.uint8)
-    n = len(inputs)
-    offsets, run = [], 0
-    for c in out_caps:
-        offsets.append(run); run += int(c)
-    own = out is None
-    if own:
-        out = bytearray(run)
-    mv = memoryview(out).cast("B")
-    if mv.readonly or mv.nbytes < run:
-        raise ValueError("cramjam_amd.batch: out must be a writable buffer of at least %d bytes" % run)
-    base = np.frombuffer(mv, dtype=np.uint8).ctypes.data if mv.nbytes else 0
-
-    def work(dev, idx):
-        arrs = [np.frombuffer(inputs[i], dtype=np.uint8) for i in idx]          # borrowed, not copied
-        k = len(arrs)
-        iptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        ilens = (C.c_size_t * max(k, 1))(*[a.size for a in arrs])
-        optrs = (C.c_void_p * max(k, 1))(*[base + offsets[i] for i in idx])
-        ocaps = (C.c_size_t * max(k, 1))(*[int(out_caps[i]) for i in idx])
-        res = np.empty(max(k, 1), np.int64)
-        N.check(N.lib().cj_dict_batch_host(_engine(dev).h, N.CODEC_LZ4_BLOCK, op, flags, k, iptrs, ilens, optrs, ocaps, res.ctypes.data,
-                                           d.ctypes.data if d.size else None, d.size))
-        return ([int(x) for x in res[:k]],)
-    res, = _shard(devices, n, work)
-    views = [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
-    return res, ([bytes(v) for v in views] if own else views)
 
 
 def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=None, out=None, dictionary=None):
@@ -94,10 +63,8 @@ def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=No
     dictionary: bytes-like — the ONE dictionary every block of the call was written against (LZ4_loadDict + LZ4_compress_fast_continue;
     only its last 64 KiB count).  Such a batch always runs one wavefront per block.  None: no dictionary."""
     flags = N.FLAG_LZ4_SIZE_PREFIX if store_size else 0
-    if dictionary is None:
-        run = lambda caps: _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, caps, devices, out)
-    else:
-        run = lambda caps: _run_dict(N.OP_DECOMPRESS, flags, blocks, caps, devices, out, dictionary)
+    kind = N.BLOCKS if dictionary is None else N.DICT
+    run = lambda caps: _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, caps, devices, out, kind, dictionary)
     if output_lens is not None:
         return run(output_lens)
     sizes = lz4_block_sizes(blocks, store_size, devices, dictionary)
@@ -117,9 +84,8 @@ def lz4_compress_blocks(chunks, store_size=True, devices=None, out=None, diction
     lz4_decompress_blocks(..., dictionary=...)); chunks of at most 65 536 bytes, a longer one gets -1 as its result."""
     L = N.lib()
     caps = [L.cj_lz4_block_compress_bound(len(c), 1 if store_size else 0) for c in chunks]
-    if dictionary is not None:
-        return _run_dict(N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, chunks, caps, devices, out, dictionary)
-    return _run(N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, chunks, caps, devices, out)
+    return _run(N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, N.FLAG_LZ4_SIZE_PREFIX if store_size else 0, chunks, caps, devices, out,
+                N.BLOCKS if dictionary is None else N.DICT, dictionary)
 
 
 def snappy_decompress_raw_many(blocks, devices=None, out=None):

@@ -245,12 +245,12 @@ void run_blosclz_rows(const uint8_t* in_base, uint8_t* out_base, const cj::Batch
 
 int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                 const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const cj_blosc_params* params, uint32_t rflags, hipStream_t s) {
-    cj::FbTurn turn(e, s);                     // (the frame batches' scratch: chunk batches and frame batches on one engine run one after another)
+    cj::ScratchTurn turn(e->fb, s);            // (the frame batches' scratch: chunk batches and frame batches on one engine run one after another)
     if (turn.rc != 0) return turn.rc;
     const bool dec = op == CJ_OP_DECOMPRESS;
     const size_t tab = up16(n * sizeof(BlChunk)), cnt_bytes = n * sizeof(BlCount);
-    int rc = cj::fb_reserve(e, std::max(cnt_bytes, tab), tab + cnt_bytes);
-    if (rc != 0) return rc;
+    int rc;
+    if ((rc = turn.reserve(e->d_fb, std::max(cnt_bytes, tab))) != 0 || (rc = turn.reserve(e->h_fb, tab + cnt_bytes)) != 0) return rc;
     BlChunk* h_tab = reinterpret_cast<BlChunk*>(e->h_fb.p);
     uint8_t* h_cnt = e->h_fb.p + tab;
     // the one wait: stream and block counts (decompress) / lengths (compress) size the rows, the scratch and the grids
@@ -306,8 +306,7 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     // d_fb: chunk table | stream rows | block rows | scratch (the filtered images of chunks with transposed blocks) | compressed slots (compress)
     const size_t o_rows = tab, o_blocks = o_rows + cj::kBlRowWords * 8 * ns, o_scr = up16(o_blocks + nb * sizeof(cj::BloscBlockRow));
     const size_t o_packed = o_scr + slot + 16;
-    rc = cj::fb_reserve(e, o_packed + cslot + 16, tab + cnt_bytes);
-    if (rc != 0) return rc;
+    if ((rc = turn.reserve(e->d_fb, o_packed + cslot + 16)) != 0) return rc;
     uint8_t* d = (uint8_t*)e->d_fb.p;
     BlChunk* d_tab = reinterpret_cast<BlChunk*>(d);
     const cj::BlRows r = cj::bl_rows(reinterpret_cast<uint64_t*>(d + o_rows), ns);

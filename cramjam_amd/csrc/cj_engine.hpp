@@ -24,23 +24,19 @@ inline bool hip_ok(hipError_t e, const char* what) {
 }
 #define HIP_TRY(expr, ret) do { if (!cj::hip_ok((expr), #expr)) return (ret); } while (0)
 
+// Owners: each releases what it holds in its destructor (on the device that is current then: cj_engine_destroy sets it) and is not copyable.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
-    bool reserve(size_t n) {
-        if (n <= cap) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + n / 4 + 4096;
-        if (!hip_ok(hipMalloc(&p, want), "hipMalloc")) { p = nullptr; return false; }
-        cap = want;
-        return true;
-    }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    bool reserve(size_t n) { return n <= cap || reserve_exact(n + n / 4 + 4096); }
     // for buffers of gigabytes (the record areas of big chunks): no growth slack
     bool reserve_exact(size_t n) {
         if (n <= cap) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
+        release();
         if (!hip_ok(hipMalloc(&p, n), "hipMalloc")) { p = nullptr; return false; }
         cap = n;
         return true;
@@ -51,16 +47,73 @@ struct DevBuf {
 struct PinnedBuf {          // page-locked host staging (full PCIe rate, truly asynchronous copies)
     uint8_t* p = nullptr;
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
     bool reserve(size_t n) {
         if (n <= cap) return true;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
+        release();
         size_t want = n + n / 4 + 4096;
         if (!hip_ok(hipHostMalloc((void**)&p, want, hipHostMallocDefault), "hipHostMalloc")) { p = nullptr; return false; }
         cap = want;
         return true;
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// an event / a stream, created where it is first needed (h == nullptr until then); reads as the handle
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    bool create() { return h || hip_ok(hipEventCreateWithFlags(&h, hipEventDisableTiming), "hipEventCreateWithFlags"); }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+    bool create() { return h || hip_ok(hipStreamCreateWithFlags(&h, hipStreamNonBlocking), "hipStreamCreateWithFlags"); }
+};
+
+// A scratch area that the calls on one engine share (its buffers are listed where cj_engine declares it): `mu` serialises the host
+// side of the calls, `free` is recorded behind the last kernel that used the area.
+struct Scratch {
+    std::mutex mu;
+    Event free;
+};
+// One turn at a scratch.  The lock is held for the whole call.  The constructor makes `s` wait for the previous user (rc: 0 or
+// CJ_E_*); a buffer of the scratch that has to grow is reallocated only once that user has finished (reserve: 0 or CJ_E_*); done(s)
+// hands the scratch to the next turn — a call that returns an error before it records nothing.
+struct ScratchTurn {
+    Scratch& sc;
+    std::lock_guard<std::mutex> lock;
+    int rc;
+    ScratchTurn(Scratch& sc_, hipStream_t s) : sc(sc_), lock(sc_.mu), rc(open(s)) {}
+    int wait_host() {
+        if (sc.free) HIP_TRY(hipEventSynchronize(sc.free), CJ_E_NO_DEVICE);
+        return 0;
+    }
+    template <class Buf>
+    int reserve(Buf& buf, size_t bytes) {
+        if (bytes > buf.cap && wait_host() != 0) return CJ_E_NO_DEVICE;
+        return buf.reserve(bytes) ? 0 : CJ_E_OOM;
+    }
+    int done(hipStream_t s) {
+        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+        HIP_TRY(hipEventRecord(sc.free, s), CJ_E_NO_DEVICE);
+        return 0;
+    }
+private:
+    int open(hipStream_t s) {
+        if (!sc.free) return sc.free.create() ? 0 : CJ_E_NO_DEVICE;
+        HIP_TRY(hipStreamWaitEvent(s, sc.free, 0), CJ_E_NO_DEVICE);
+        return 0;
+    }
 };
 
 // host-side pack/scatter of many small buffers is memcpy-bound on one core (~20 GB/s); split it over a few threads
@@ -80,35 +133,32 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 
 }  // namespace cj
 
-struct cj_engine {
+struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
     int device = 0;
-    hipStream_t stream = nullptr;
+    cj::Stream stream;
+    cj::Stream stream_back;        // batch_host_sliced: the copies back to the host (the engine's stream keeps uploading and decoding the next slice)
     std::mutex mu;                 // serialises host-batch staging on this engine
     cj::DevBuf d_in, d_out, d_meta;
-    std::mutex scratch_mu;         // LZ4 parse->decode scratch (sync points, per-chunk meta), reused across calls
+    cj::Scratch scratch;           // the workgroup decoders: LZ4 parse->decode scratch (sync points, per-chunk meta), record tables, big-chunk areas
     cj::DevBuf d_sync, d_pmeta, d_lanelist;   // d_lanelist: word [2] = the workgroup decoder's chunk counter
-    hipEvent_t scratch_free = nullptr;    // recorded after the last kernel that reads the scratch
     cj::PinnedBuf h_in, h_out, h_res;   // h_res: the results of a sliced host batch (engine.hip: batch_host_sliced)
-    hipStream_t stream_back = nullptr;  // ... its copies back to the host (the engine's stream keeps uploading and decoding the next slice)
-    std::vector<hipEvent_t> slice_ev;
+    std::vector<cj::Event> slice_ev;
     std::vector<uint64_t> h_meta;
     cj::DevBuf d_frame;            // frame.hip: assembled / staged framed stream
     cj::DevBuf d_tab;              // LDS decoder variant 2: per-workgroup record tables
     cj::DevBuf d_biglist, d_bigrecs, d_bigmisc, d_bigslabtab;   // chunks of 64 KiB .. 256 KiB in a device batch (big_chunks.hpp, CJ_FLAG_BIG_CHUNKS): record areas; list + summaries + slab items; the slab decoder's tables
-    uint32_t* h_count = nullptr;   // pinned words: the number of big chunks of the last flagged batches, copied back without waiting (engine.hip plan_big)
-    hipEvent_t big_ev[8] = {};     // ... one event per slot (the copy has landed)
+    cj::PinnedBuf h_count;         // pinned words: the number of big chunks of the last flagged batches, copied back without waiting (engine.hip plan_big)
+    cj::Event big_ev[8];           // ... one event per slot (the copy has landed)
     uint32_t big_obs[8] = {};      // ... the counts that have
     int big_state[8] = {};         // 0 = empty, 1 = copy in flight, 2 = count known
     int big_next = 0;
     cj::DevBuf d_big, d_bigtab;    // large.hip: parse scratch / record tables of one large stream (under `mu`)
     int n_cu = 0;
-    std::mutex fb_mu;              // frame_batch.hip: batches of framed streams — frame table, block rows and decode slots, its staging
+    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip: batches of framed streams / Blosc chunks — frame table, block rows and decode slots, its staging
     cj::DevBuf d_fb;
     cj::PinnedBuf h_fb;
-    hipEvent_t fb_free = nullptr;  // ... recorded after the last kernel that uses them
-    std::mutex dict_mu;            // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows
+    cj::Scratch dict_stage;        // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows
     cj::DevBuf d_dict_stage;
-    hipEvent_t dict_free = nullptr;   // ... recorded after the last kernel that uses them
     cj::DevBuf d_dict;             // ... the dictionary of a host batch (under `mu`)
 };
 

@@ -55,34 +55,6 @@ void launch_fb_pieces(size_t n, const FbFrame* fr, const uint64_t* in_off, const
 void launch_fb_assemble(int fmt, size_t n, const FbFrame* fr, FbRows r, const uint32_t* sums, const uint8_t* in_base, const uint64_t* in_len, const uint8_t* scratch, uint64_t stride, uint8_t* out_base, const uint64_t* out_off,
                         const uint64_t* out_cap, int64_t* result, hipStream_t s);
 
-// One turn at the container batches' scratch (e->d_fb, e->h_fb: frame batches and Blosc chunk batches).  The lock is held across the
-// call's one wait: such batches on one engine run one after another, and a call waits for everything its caller queued on `s` before
-// it, so a second caller's batch also waits behind that (engines are cheap: one per thread or stream avoids it).  The next turn waits
-// for this one on the device, from done(s) on — a call that returns an error before that records nothing.
-struct FbTurn {
-    cj_engine* e;
-    std::lock_guard<std::mutex> lock;
-    int rc;                        // of the construction: 0 or CJ_E_*
-    FbTurn(cj_engine* e_, hipStream_t s) : e(e_), lock(e_->fb_mu), rc(open(s)) {}
-    int done(hipStream_t s) {
-        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-        HIP_TRY(hipEventRecord(e->fb_free, s), CJ_E_NO_DEVICE);
-        return 0;
-    }
-private:
-    int open(hipStream_t s) {
-        if (!e->fb_free) HIP_TRY(hipEventCreateWithFlags(&e->fb_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
-        else HIP_TRY(hipStreamWaitEvent(s, e->fb_free, 0), CJ_E_NO_DEVICE);      // the previous user of the scratch
-        return 0;
-    }
-};
-// growing the scratch waits for its previous user on the host
-inline int fb_reserve(cj_engine* e, size_t dev_bytes, size_t host_bytes) {
-    if ((dev_bytes > e->d_fb.cap || host_bytes > e->h_fb.cap) && e->fb_free) HIP_TRY(hipEventSynchronize(e->fb_free), CJ_E_NO_DEVICE);
-    if (!e->d_fb.reserve(dev_bytes) || !e->h_fb.reserve(host_bytes)) return CJ_E_OOM;
-    return 0;
-}
-
 // Compress in[0, n), cut into pieces of `piece` bytes, as ONE batch into e->d_out (`stride` bytes apart), the input staged at e->d_in + H
 // behind the last H bytes before it (hist: linked LZ4 blocks, kFlagLinkedEnc — piece 0 may refer to those H bytes, every other piece to
 // the piece before it).  Queues the results' copy into res and, with `first`, the stitch plan kernel (first[i] = literal length of piece
@@ -135,7 +107,7 @@ inline int assemble(cj_engine* e, uint64_t size, const uint8_t* lead, size_t lea
     return assemble(e, size, lead, lead_len, lists, 0, [](uint8_t*) { return 0; }, out);
 }
 
-// A host batch (engine.hip), the one staging of cj_batch_host, cj_frame_batch_host, cj_blosc_batch_host and the size queries: under
+// A host batch (engine.hip), the one staging of cj_batch_host, cj_frame_batch_host, cj_blosc_batch_host, cj_dict_batch_host and the size queries: under
 // e->mu, on the engine's device and stream — the rows of the n buffers laid out one after another, 16 bytes aligned; the inputs packed
 // into pinned staging and uploaded with the rows; run(d_in, d_out, d, s) = the device path over the device rows d; the results read
 // back and waited for; the span of d_out that was produced copied back and scattered to out_ptrs (a result above its capacity becomes

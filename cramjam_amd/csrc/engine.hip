@@ -30,15 +30,13 @@ namespace {
 constexpr uint32_t kWgsPerCu = CJ_L2_WGS_PER_CU;       // persistent workgroups of the LDS decoder per CU (tuning variants change it together with CJ_L2_WINDOW)
 
 // scratch of the workgroup decoders (per-chunk verdicts, the chunk counter, record tables), shared by every call on the
-// engine: a call waits (on the stream) for the previous user before it overwrites them
-int lds_scratch(cj_engine* e, const cj::BatchArgs& a, hipStream_t s, bool with_sync) {
+// engine: a call takes a turn at it (cj::ScratchTurn) before it overwrites them
+int lds_scratch(cj_engine* e, cj::ScratchTurn& turn, const cj::BatchArgs& a, hipStream_t s, bool with_sync) {
     const size_t list_bytes = 256 + cj::kClaimBytes + (size_t)a.n_chunks * 8;
     const size_t sync_bytes = with_sync ? cj::lz4_lds_scratch_sync_bytes(a.n_chunks) : 0;
-    const bool grow = sync_bytes > e->d_sync.cap || cj::lz4_lds_scratch_meta_bytes(a.n_chunks) > e->d_pmeta.cap || list_bytes > e->d_lanelist.cap;
-    if (grow && e->scratch_free) HIP_TRY(hipEventSynchronize(e->scratch_free), CJ_E_NO_DEVICE);
-    if (!e->d_sync.reserve(sync_bytes) || !e->d_pmeta.reserve(cj::lz4_lds_scratch_meta_bytes(a.n_chunks)) || !e->d_lanelist.reserve(list_bytes)) return CJ_E_OOM;
-    if (!e->scratch_free) HIP_TRY(hipEventCreateWithFlags(&e->scratch_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
-    else HIP_TRY(hipStreamWaitEvent(s, e->scratch_free, 0), CJ_E_NO_DEVICE);   // previous user of the scratch
+    int rc;
+    if ((rc = turn.reserve(e->d_sync, sync_bytes)) != 0 || (rc = turn.reserve(e->d_pmeta, cj::lz4_lds_scratch_meta_bytes(a.n_chunks))) != 0 ||
+        (rc = turn.reserve(e->d_lanelist, list_bytes)) != 0) return rc;
     HIP_TRY(hipMemsetAsync(e->d_lanelist.p, 0, 256 + cj::kClaimBytes, s), CJ_E_NO_DEVICE);        // words [64 ..): the decoders' chunk counters
     if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
     if (!e->d_tab.reserve(cj::lz4_lds2_tab_bytes(kWgsPerCu * (uint32_t)e->n_cu))) return CJ_E_OOM;
@@ -67,31 +65,30 @@ int plan_big(cj_engine* e, cj_codec codec, const cj::BatchArgs& a, hipStream_t s
     const size_t big_list_bytes = ((4 + (size_t)a.n_chunks) * 4 + 255) & ~(size_t)255;
     if (!e->d_biglist.reserve(big_list_bytes)) { (void)hipGetLastError(); return 0; }      // no room for the list: the chunks stay with the wavefront kernel
     uint32_t* big_list = (uint32_t*)e->d_biglist.p;
-    if (!e->h_count) {                                        // (h_count is set last: after a failure here the next call starts over)
-        uint32_t* h = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&h, 64, hipHostMallocDefault), CJ_E_OOM);
-        for (hipEvent_t& ev : e->big_ev)
-            if (!ev && !hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreateWithFlags")) { (void)hipHostFree(h); return CJ_E_NO_DEVICE; }
-        e->h_count = h;
+    if (!e->h_count.p) {                                      // (h_count is set last: after a failure here the next call starts over)
+        for (cj::Event& ev : e->big_ev)
+            if (!ev.create()) return CJ_E_NO_DEVICE;
+        if (!e->h_count.reserve(kBigObs * 4)) return CJ_E_OOM;
     }
+    uint32_t* h_count = (uint32_t*)e->h_count.p;
     cj::launch_big_list(a, codec, big_list, s);
     // counts that have arrived since the last call
     bool any = false;
     uint32_t plan = 0;
     for (int i = 0; i < kBigObs; i++) {
-        if (e->big_state[i] == 1 && hipEventQuery(e->big_ev[i]) == hipSuccess) { e->big_obs[i] = e->h_count[i]; e->big_state[i] = 2; }
+        if (e->big_state[i] == 1 && hipEventQuery(e->big_ev[i]) == hipSuccess) { e->big_obs[i] = h_count[i]; e->big_state[i] = 2; }
         if (e->big_state[i] == 2) { any = true; plan = std::max(plan, e->big_obs[i]); }
     }
     (void)hipGetLastError();                                  // (hipErrorNotReady from the queries)
     const int slot = e->big_next;
     e->big_next = (slot + 1) % kBigObs;
     if (e->big_state[slot] == 1) HIP_TRY(hipEventSynchronize(e->big_ev[slot]), CJ_E_NO_DEVICE);   // (eight flagged calls in flight: the oldest copy must have landed before its slot is reused)
-    HIP_TRY(hipMemcpyAsync(e->h_count + slot, big_list, 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
+    HIP_TRY(hipMemcpyAsync(h_count + slot, big_list, 4, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipEventRecord(e->big_ev[slot], s), CJ_E_NO_DEVICE);
     e->big_state[slot] = 1;
     if (!any) {                                                // an engine that has seen nothing yet: this batch's own count
         HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-        e->big_obs[slot] = e->h_count[slot]; e->big_state[slot] = 2;
+        e->big_obs[slot] = h_count[slot]; e->big_state[slot] = 2;
         plan = e->big_obs[slot];
     }
     *n_plan = (uint32_t)std::min<size_t>(plan, a.n_chunks);
@@ -136,9 +133,10 @@ int launch_decode(cj_engine* e, cj_codec codec, const cj::BatchArgs& a_in, hipSt
     if (a.flags & CJ_FLAG_FORCE_PARSE_KERNEL) fused = false;
     a.flags |= small;                                         // (round 6, f05: the one-kernel path runs on the batch's window too)
     const uint32_t win = cj::lds_window(a.flags);
-    std::lock_guard<std::mutex> lock(e->scratch_mu);
     // (first: it makes `s` wait for the previous user of the engine's shared scratch — the big-chunk list below is part of it)
-    const int rc = lds_scratch(e, a, s, !fused);
+    cj::ScratchTurn turn(e->scratch, s);
+    if (turn.rc != 0) return turn.rc;
+    const int rc = lds_scratch(e, turn, a, s, !fused);
     if (rc != 0) return rc;
     uint32_t n_big = 0;
     uint32_t* big_list = nullptr;
@@ -184,8 +182,7 @@ int launch_decode(cj_engine* e, cj_codec codec, const cj::BatchArgs& a_in, hipSt
     }
     if (lz4) cj::launch_lz4_decode_routed(a, e->d_pmeta.p, s);                // few long runs / oversize chunks / errors
     else cj::launch_snappy_decode_routed(a, e->d_pmeta.p, s);
-    HIP_TRY(hipEventRecord(e->scratch_free, s), CJ_E_NO_DEVICE);
-    return 0;
+    return turn.done(s);
 }
 
 // LZ4 block / Snappy raw encode of a batch of independent chunks: one workgroup of two wavefronts per chunk (lz4_encode.hip)
@@ -363,13 +360,13 @@ int batch_host_sliced(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, co
                       uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, uint64_t in_total, uint64_t out_total) {
     const size_t n = h.n;
     if (!e->h_in.reserve(in_total) || !e->h_out.reserve(out_total) || !e->h_res.reserve(n * 8)) return CJ_E_OOM;
-    if (!e->stream_back) HIP_TRY(hipStreamCreateWithFlags(&e->stream_back, hipStreamNonBlocking), CJ_E_NO_DEVICE);
+    if (!e->stream_back.create()) return CJ_E_NO_DEVICE;
     size_t K = (size_t)((in_total + out_total) >> 26);               // ~64 MiB of traffic per slice
     K = K < 2 ? 2 : (K > 16 ? 16 : K);
     while (e->slice_ev.size() < 2 * K) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming), CJ_E_NO_DEVICE);
-        e->slice_ev.push_back(ev);
+        cj::Event ev;
+        if (!ev.create()) return CJ_E_NO_DEVICE;
+        e->slice_ev.push_back(std::move(ev));
     }
     uint8_t* d_in = (uint8_t*)e->d_in.p;
     uint8_t* d_out = (uint8_t*)e->d_out.p;
@@ -492,7 +489,7 @@ int cj_engine_create(int device, cj_engine** out) {
     HIP_TRY(hipSetDevice(device), CJ_E_NO_DEVICE);
     cj_engine* e = new cj_engine();
     e->device = device;
-    if (!hip_ok(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate")) { delete e; return CJ_E_NO_DEVICE; }
+    if (!e->stream.create()) { delete e; return CJ_E_NO_DEVICE; }
     *out = e;
     return 0;
 }
@@ -500,16 +497,6 @@ int cj_engine_create(int device, cj_engine** out) {
 void cj_engine_destroy(cj_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    e->d_in.release(); e->d_out.release(); e->d_meta.release(); e->d_sync.release(); e->d_bigrecs.release(); e->d_bigmisc.release(); e->d_biglist.release(); if (e->h_count) (void)hipHostFree(e->h_count); for (auto& ev : e->big_ev) if (ev) (void)hipEventDestroy(ev); e->d_bigslabtab.release(); e->d_pmeta.release(); e->d_lanelist.release(); e->d_frame.release(); e->d_tab.release(); e->d_big.release(); e->d_bigtab.release();
-    e->h_in.release(); e->h_out.release(); e->h_res.release();
-    for (hipEvent_t ev : e->slice_ev) (void)hipEventDestroy(ev);
-    if (e->stream_back) (void)hipStreamDestroy(e->stream_back);
-    if (e->scratch_free) (void)hipEventDestroy(e->scratch_free);
-    e->d_fb.release(); e->h_fb.release();
-    if (e->fb_free) (void)hipEventDestroy(e->fb_free);
-    e->d_dict_stage.release(); e->d_dict.release();
-    if (e->dict_free) (void)hipEventDestroy(e->dict_free);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
 
@@ -733,6 +720,6 @@ int cj_memset_dev(cj_engine* e, void* d, int v, size_t n) {
 
 extern "C" uint64_t cj_debug_big_scratch_bytes(cj_engine* e) {
     if (!e) return 0;
-    std::lock_guard<std::mutex> lock(e->scratch_mu);
+    std::lock_guard<std::mutex> lock(e->scratch.mu);
     return (uint64_t)e->d_biglist.cap + e->d_bigrecs.cap + e->d_bigmisc.cap + e->d_bigslabtab.cap;
 }

@@ -213,11 +213,11 @@ int lz4_frame_linked_lds(cj_engine* e, const Lz4Frame& f, const uint8_t* d_in, s
     const size_t nb = f.blocks.size();
     const uint64_t B = 65536;
     hipStream_t s = e->stream;
-    std::lock_guard<std::mutex> lock(e->scratch_mu);
+    cj::ScratchTurn turn(e->scratch, s);       // (no done(): the call waits for its own kernels, the next turn has nobody to wait for)
+    if (turn.rc != 0 || (turn.rc = turn.wait_host()) != 0) return turn.rc;
     // rows: in_off | in_len | out_off | out_cap | result | hist(u32) | frames(uint2) | first(uint2 per block) | counter | done(u32 per block)
     const size_t hw = (nb * 4 + 7) / 8, r_first = 5 * nb + hw + 1, r_cnt = r_first + nb, r_done = r_cnt + 1, rows = r_done + hw;
     const size_t list_bytes = 16;
-    if (e->scratch_free) HIP_TRY(hipEventSynchronize(e->scratch_free), CJ_E_NO_DEVICE);
     if (!e->d_out.reserve(nb * B + 16) || !e->d_meta.reserve(rows * 8) || !e->d_sync.reserve(cj::lz4_lds_scratch_sync_bytes(nb)) ||
         !e->d_pmeta.reserve(cj::lz4_lds_scratch_meta_bytes(nb)) || !e->d_lanelist.reserve(list_bytes) ||
         !e->d_tab.reserve(cj::lz4_lds2_tab_bytes(1))) return CJ_E_OOM;

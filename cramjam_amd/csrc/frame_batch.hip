@@ -16,11 +16,14 @@ inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 
 int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    cj::FbTurn turn(e, s);
+    // One turn at the container batches' scratch (e->d_fb, e->h_fb: frame batches and Blosc chunk batches).  The lock is held across the
+    // call's one wait: such batches on one engine run one after another, and a call waits for everything its caller queued on `s` before
+    // it, so a second caller's batch also waits behind that (engines are cheap: one per thread or stream avoids it).
+    cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
     const size_t tab = up16(n * sizeof(cj::FbFrame));
-    int rc = cj::fb_reserve(e, std::max(16 * n, tab), tab + 16 * n);
-    if (rc != 0) return rc;
+    int rc;
+    if ((rc = turn.reserve(e->d_fb, std::max(16 * n, tab))) != 0 || (rc = turn.reserve(e->h_fb, tab + 16 * n)) != 0) return rc;
     uint64_t* cnt = (uint64_t*)e->h_fb.p;                                         // read back: [2i] blocks, [2i + 1] scratch bytes / in_len
     cj::FbFrame* h_fr = reinterpret_cast<cj::FbFrame*>(e->h_fb.p + 16 * n);
     const bool dec = op == CJ_OP_DECOMPRESS;
@@ -46,8 +49,7 @@ int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* 
     if (!dec) slot = nb * stride;
     // d_fb: frames | chain jobs (decompress) / content sums (compress) | block rows | scratch
     const size_t o_side = tab, o_rows = o_side + up16(n * sizeof(cj::ChainJob)), o_scr = o_rows + cj::kFbRowWords * 8 * nb;
-    rc = cj::fb_reserve(e, o_scr + slot + 16, tab + 16 * n);
-    if (rc != 0) return rc;
+    if ((rc = turn.reserve(e->d_fb, o_scr + slot + 16)) != 0) return rc;
     uint8_t* d = (uint8_t*)e->d_fb.p;
     cj::FbFrame* fr = reinterpret_cast<cj::FbFrame*>(d);
     const cj::FbRows r = cj::fb_rows(reinterpret_cast<uint64_t*>(d + o_rows), nb);

@@ -130,8 +130,7 @@ bool args_ok(int codec, uint32_t flags, const void* dict, size_t dict_len) {
     return codec == CJ_CODEC_LZ4_BLOCK && (flags & ~CJ_FLAG_LZ4_SIZE_PREFIX) == 0u && (dict_len == 0 || dict != nullptr);
 }
 
-// One turn at the engine's staging scratch (cj_stage.hpp: FbTurn's protocol): the previous user is waited for on the stream, or on
-// the host when the scratch has to grow.
+// One turn at the engine's staging scratch (cj::ScratchTurn)
 int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                     const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const uint8_t* dict_tail, uint32_t hist, hipStream_t s) {
     const uint64_t stride = ((uint64_t)hist + cj::kDictChunkMax + 255u) & ~(uint64_t)255u;
@@ -139,11 +138,8 @@ int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_ba
     const size_t per = (size_t)std::min<uint64_t>(n, std::max<uint64_t>(1, budget / stride));
     const size_t slots_bytes = per * stride + 256;                      // (the encoder's vector loads may pass a chunk's end by a granule)
     const size_t rows_bytes = per * (4 * 8 + 4) + 64;
-    std::lock_guard<std::mutex> lock(e->dict_mu);
-    if (slots_bytes + rows_bytes > e->d_dict_stage.cap && e->dict_free) HIP_TRY(hipEventSynchronize(e->dict_free), CJ_E_NO_DEVICE);
-    if (!e->d_dict_stage.reserve(slots_bytes + rows_bytes)) return CJ_E_OOM;
-    if (!e->dict_free) HIP_TRY(hipEventCreateWithFlags(&e->dict_free, hipEventDisableTiming), CJ_E_NO_DEVICE);
-    else HIP_TRY(hipStreamWaitEvent(s, e->dict_free, 0), CJ_E_NO_DEVICE);
+    cj::ScratchTurn turn(e->dict_stage, s);
+    if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_dict_stage, slots_bytes + rows_bytes)) != 0) return turn.rc;
     uint8_t* stage = (uint8_t*)e->d_dict_stage.p;
     uint64_t* rows = reinterpret_cast<uint64_t*>(stage + slots_bytes);
     const uint32_t prefix = (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1u : 0u;
@@ -162,9 +158,7 @@ int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_ba
         hipLaunchKernelGGL(cj::dict_finish_kernel, dim3((k + cj::kBlockThreads - 1) / cj::kBlockThreads), dim3(cj::kBlockThreads), 0, s, k, in_len + first, out_base,
                            out_off + first, result + first, prefix);
     }
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipEventRecord(e->dict_free, s), CJ_E_NO_DEVICE);
-    return 0;
+    return turn.done(s);
 }
 
 // enqueue only; dict = the whole dictionary on the device, dict_len > 0

@@ -24,6 +24,10 @@ def test_empty_batches_return_without_a_call():
     assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(0)) == []
     assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), []) == []
     assert M.batch_host(0, 0, 0, 0, (), (), 0, b"") == ([], [])                     # (a Blosc batch)
+    for d in (b"", b"dictionary", bytearray(b"dictionary"), memoryview(b"dictionary")):        # (LZ4 blocks against a dictionary)
+        assert M.batch_host(0, 0, 0, 0, [], [], 0, None, d) == ([], [])
+        assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), None, 0, None, d) == []
+    assert M.batch_host(0, 0, 0, 0, [], [], 0, None, None) == ([], [])
 
 
 @pytest.mark.parametrize("entry", ENTRIES)
@@ -41,6 +45,26 @@ def test_params_of_a_wrong_length(entry, params):
         entry([b"a"], [1], 0, params)
     with pytest.raises(ValueError):
         entry([], [], 0, params)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("dictionary", [5, "text", 1.5, [1, 2], memoryview(bytes(8))[::2]])
+def test_a_dictionary_that_is_no_contiguous_buffer(entry, dictionary):
+    with pytest.raises((TypeError, BufferError)) as ex:
+        entry([b"a"], [1], 0, None, dictionary)
+    assert ex.type is TypeError or isinstance(dictionary, memoryview)              # (the strided view: BufferError, as for an input)
+    with pytest.raises((TypeError, BufferError)):
+        entry([], [], 0, None, dictionary)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("params", [b"", bytes(20)])
+def test_a_dictionary_together_with_params(entry, params):
+    for inputs, caps in (([b"a"], [1]), ([], [])):
+        with pytest.raises(ValueError):
+            entry(inputs, caps, 0, params, b"dictionary")
+        with pytest.raises(ValueError):
+            entry(inputs, caps, 0, params, b"")
 
 
 @pytest.mark.parametrize("entry", ENTRIES)
@@ -74,17 +98,23 @@ def test_into_read_only_out():
             _into([b"a"], [1], out=out)
 
 
-def _failing(first):
-    """calls that fail on the entry BEHIND `first`, whose buffer has been borrowed by then"""
-    yield lambda: _host([first, 5], [1, 1])
-    yield lambda: _host([first, b"b"], [1, -1])
-    yield lambda: _into([first, 5], [1, 1])
-    yield lambda: _into([first, b"b"], [1, -1])
-    yield lambda: _into([first, b"b"], [8, 8], out=bytearray(12))
-    yield lambda: _into([first, b"b"], [1, 1], offsets=[0, "x"])
-    yield lambda: _into([first, b"b"], [1, 1], offsets=[0])
-    yield lambda: _host([first, b"b"], [1])
-    yield lambda: _host([first], [1], 0, b"xyz")
+def _failing(first, d=None):
+    """calls that fail on the entry BEHIND `first`, whose buffer has been borrowed by then (d: while a dictionary is borrowed too)"""
+    tail = () if d is None else (0, None, d)
+    yield lambda: _host([first, 5], [1, 1], *tail)
+    yield lambda: _host([first, b"b"], [1, -1], *tail)
+    yield lambda: _into([first, 5], [1, 1], *tail)
+    yield lambda: _into([first, b"b"], [1, -1], *tail)
+    yield lambda: _into([first, b"b"], [8, 8], *tail, out=bytearray(12))
+    yield lambda: _into([first, b"b"], [1, 1], *tail, offsets=[0, "x"])
+    yield lambda: _into([first, b"b"], [1, 1], *tail, offsets=[0])
+    yield lambda: _host([first, b"b"], [1], *tail)
+    if d is None:
+        yield lambda: _host([first], [1], 0, b"xyz")
+    else:
+        yield lambda: _host([first], [1], 0, b"", d)                # (params and a dictionary)
+        yield lambda: _into([first], [1], 0, bytes(20), d)
+        yield lambda: _into([first], [1], 0, None, d, out=bytes(8))       # (a read-only out)
 
 
 def test_a_failure_releases_the_inputs_it_borrowed():
@@ -95,6 +125,25 @@ def test_a_failure_releases_the_inputs_it_borrowed():
             call()
         first.extend(b"more")                # BufferError while a buffer export of the call is still alive
         del first[:]
+
+
+def test_a_failure_releases_the_dictionary_it_borrowed():
+    for k in range(11):
+        first, d = bytearray(b"0123456789"), bytearray(b"the dictionary")
+        call = list(_failing(first, d))[k]
+        with pytest.raises((TypeError, ValueError, OverflowError)):
+            call()
+        for b in (first, d):
+            b.extend(b"more")
+            del b[:]
+
+
+def test_a_call_that_returns_releases_the_dictionary():
+    d = bytearray(b"the dictionary")
+    assert M.batch_host(0, 0, 0, 0, [], [], 0, None, d) == ([], [])
+    assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), None, 0, None, d) == []
+    d.extend(b"more")
+    del d[:]
 
 
 def test_the_hip_error_text_is_always_appended():

@@ -1,11 +1,12 @@
-"""The one host staging (cj::host_batch) through its six host entries: the same small lists with and without a caller's buffer, on one
+"""The one host staging (cj::host_batch) through its eight host entries: the same small lists with and without a caller's buffer, on one
 engine, on two engines of device 0 and on one engine from two threads — equal results and bytes, the oracle's; a failed chunk keeps
 the code of the single-stream export, nothing is written outside a chunk's result, the size queries give the capacities used.
 
 The lists: b"", 1 byte, 100 bytes, 65 536, 65 537 (crosses a piece / stream boundary), a failed one, and a valid 3 000-byte one LAST,
 so that the span that is copied back is decided behind a failed chunk; the first two alone (n = 2); the fourth alone (n = 1,
 cj_batch_host's shortcut).  The failed one of a decoder is a stream of 2 000 bytes with the first byte flipped that the oracle
-rejects; the encoder (Blosc compress) cannot be failed by its input, there it is a capacity of 16 bytes: the header alone."""
+rejects; an encoder (Blosc compress, LZ4 compress against a dictionary) cannot be failed by its input, there it is a capacity of 16
+bytes: the header alone.  The dictionary's encoder also refuses the chunk of 65 537 bytes (CJ_E_INPUT_TOO_LARGE): a second failed chunk."""
 import ctypes as C
 import random
 import struct
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 import blosc_model as M
+import lz4_dict_model as D
 import oracle
 from cramjam_amd import _native as N
 from cramjam_amd import batch, blosc2
@@ -88,22 +90,23 @@ PARAMS = blosc2._params(4, 5, blosc2.Filter.Shuffle, blosc2.Codec.LZ4)
 
 
 class Entry:
-    """one host entry: its inputs, capacities, what the oracle expects of every chunk (bytes of a decoder; None = failed), and its exports"""
+    """one host entry: its inputs, capacities, what the oracle expects of every chunk (bytes of a decoder; None = failed), and its exports.
+    bad: the chunks that fail -> the code expected (None: the single-stream export's, whatever it is)"""
 
-    def __init__(self, name, kind, what, op, make, expect_len, single, sizes=None, size_of=None, params=None):
-        self.name, self.kind, self.what, self.op, self.single, self.sizes, self.params = name, kind, what, op, single, sizes, params
+    def __init__(self, name, kind, what, op, make, expect_len, single, sizes=None, size_of=None, params=None, bound=lambda n: n + 32, undo=lambda b, n: M.decode(b),
+                 also_bad={}):
+        self.name, self.kind, self.what, self.op, self.single, self.sizes, self.params, self.undo = name, kind, what, op, single, sizes, params, undo
+        self.bad = {BAD: None, **also_bad}
         if op == DEC:
             self.inputs = [make(r) for r in RAWS]
             self.inputs[BAD] = _flipped(self.inputs[BAD], lambda m: expect_len(m, len(RAWS[BAD])) < 0)
             # the capacities: what the single-stream size export says (a raw LZ4 block has none: the oracle's length)
             self.caps = [len(RAWS[i]) if size_of is None else max(size_of(b), 0) for i, b in enumerate(self.inputs)]
-            self.expect = list(RAWS)
         else:
             self.inputs = list(RAWS)
-            self.caps = [len(r) + 32 for r in RAWS]
+            self.caps = [bound(len(r)) for r in RAWS]
             self.caps[BAD] = 16                                                     # the header alone
-            self.expect = list(RAWS)
-        self.expect[BAD] = None
+        self.expect = [None if i in self.bad else r for i, r in enumerate(RAWS)]
 
     def run(self, pick, devices, out):
         ins, caps = [self.inputs[i] for i in pick], [self.caps[i] for i in pick]
@@ -118,6 +121,28 @@ def _info_nbytes(b):
     info = N.BloscInfo()
     rc = N.lib().cj_blosc_chunk_info(_ptr(b), len(b), C.byref(info))
     return rc if rc != 0 else info.nbytes
+
+
+DICT = D.dictionary(4096)
+
+
+def _dict_stream(raw):
+    """liblz4's block against DICT; the model certifies that it decodes to raw"""
+    s = D.lz4_compress_with_dict(D.liblz4(), raw, DICT)
+    assert D.decode(s, len(raw), DICT) == (len(raw), raw)
+    return s
+
+
+def _single_dict(op):
+    """the chunk alone through the C export itself (cj_dict_batch_host, n = 1, marshalled by ctypes) as (data, cap) -> (result, bytes)"""
+    def call(data, cap):
+        data = bytes(data)
+        buf = C.create_string_buffer(max(cap, 1))
+        ins, lens = (C.c_void_p * 1)(C.cast(C.c_char_p(data), C.c_void_p) if data else None), (C.c_size_t * 1)(len(data))
+        outs, caps, res = (C.c_void_p * 1)(C.cast(buf, C.c_void_p)), (C.c_size_t * 1)(cap), (C.c_int64 * 1)(0)
+        N.check(N.lib().cj_dict_batch_host(batch._engine(0).h, N.CODEC_LZ4_BLOCK, op, 0, 1, ins, lens, outs, caps, res, C.cast(C.c_char_p(DICT), C.c_void_p), len(DICT)))
+        return res[0], buf.raw[:max(res[0], 0)]
+    return call
 
 
 def _entries():
@@ -136,10 +161,14 @@ def _entries():
         Entry("blosc_decompress", N.BLOSC, 0, DEC, _blosc_chunk, lambda m, cap: 0 if M.verdict(m, cap)[0] == "ok" else -1,
               _single("cj_blosc_chunk_decompress"), batch.blosc_chunk_sizes, _info_nbytes, b""),
         Entry("blosc_compress", N.BLOSC, 0, ENC, None, None, _single("cj_blosc_chunk_compress", C.byref(PARAMS)), params=bytes(PARAMS)),
+        Entry("lz4_dict_decompress", N.DICT, N.CODEC_LZ4_BLOCK, DEC, _dict_stream, lambda m, cap: D.decode(m, cap, DICT)[0], _single_dict(DEC),
+              lambda blocks, devices: batch.lz4_block_sizes(blocks, devices=devices, dictionary=DICT), params=DICT),
+        Entry("lz4_dict_compress", N.DICT, N.CODEC_LZ4_BLOCK, ENC, None, None, _single_dict(ENC), params=DICT,
+              bound=lambda n: L.cj_lz4_block_compress_bound(n, 0), undo=lambda b, n: D.decode(b, n, DICT)[1], also_bad={4: D.INPUT_TOO_LARGE}),
     ]
 
 
-NAMES = ["lz4_blocks", "snappy_blocks", "lz4_frames", "snappy_framed", "blosc_decompress", "blosc_compress"]
+NAMES = ["lz4_blocks", "snappy_blocks", "lz4_frames", "snappy_framed", "blosc_decompress", "blosc_compress", "lz4_dict_decompress", "lz4_dict_compress"]
 _made = {}
 
 
@@ -195,14 +224,14 @@ def test_host_entry_every_way(name, pick, two_engines):
         r1, o1 = e.single(e.inputs[i], e.caps[i])
         assert res[k] == r1, (i, res[k], r1)             # above all the failed chunk: the single-stream export's code
         if e.expect[i] is None:
-            assert res[k] < 0 and outs[k] == b""
+            assert res[k] < 0 and outs[k] == b"" and e.bad[i] in (None, res[k]), (i, res[k])
         elif e.op == DEC:
             assert res[k] == len(e.expect[i]) and outs[k] == e.expect[i], i
         else:
-            assert res[k] == len(outs[k]) > 0 and M.decode(outs[k]) == e.expect[i], i
+            assert res[k] == len(outs[k]) > 0 and e.undo(outs[k], len(e.expect[i])) == e.expect[i], i
 
 
-@pytest.mark.parametrize("name", [n for n in NAMES if n != "blosc_compress"])
+@pytest.mark.parametrize("name", [n for n in NAMES if not n.endswith("_compress")])
 def test_size_queries_give_the_capacities_used(name, two_engines):
     e = _entry(name)
     one = e.sizes(e.inputs, devices=[0])
@@ -210,7 +239,7 @@ def test_size_queries_give_the_capacities_used(name, two_engines):
     for i, s in enumerate(one):
         if i != BAD:
             assert s == e.caps[i] == len(RAWS[i]), i
-        elif name != "lz4_blocks":           # (the failed raw LZ4 block's capacity is not from a size export)
+        elif name not in ("lz4_blocks", "lz4_dict_decompress"):      # (the failed raw LZ4 block's capacity is not from a size export)
             assert max(s, 0) == e.caps[i], s
     assert e.sizes(e.inputs[:2], devices=[0, "second"]) == one[:2] and e.sizes(e.inputs[3:4], devices=[0, "second"]) == one[3:4]
 
@@ -223,3 +252,10 @@ def test_a_refused_call_reports_code_text_and_hip_text():
         eng.batch_host(N.CODEC_LZ4_BLOCK, DEC, 1 << 20, [blob], [4096])
     L = N.lib()
     assert str(ex.value) == "cramjam_hip error %d: %s (%s)" % (-101, L.cj_strerror(-101).decode(), L.cj_last_hip_error().decode())
+    # ... and the same report from cj_dict_batch_host, into bytes and into a caller's buffer
+    for call in (lambda: eng.batch_host(N.CODEC_LZ4_BLOCK, DEC, 1 << 20, [blob], [4096], dictionary=DICT),
+                 lambda: eng.batch_host_into(N.CODEC_LZ4_BLOCK, DEC, 1 << 20, [blob], [4096], bytearray(4096), dictionary=DICT),
+                 lambda: batch._run(N.CODEC_SNAPPY_RAW, DEC, 0, [blob], [4096], [0], None, N.DICT, DICT)):        # (Snappy has no dictionaries)
+        with pytest.raises(N.EngineError) as ex:
+            call()
+        assert str(ex.value) == "cramjam_hip error %d: %s (%s)" % (-101, L.cj_strerror(-101).decode(), L.cj_last_hip_error().decode())

@@ -1,0 +1,187 @@
+"""One turn after another at each of an engine's three scratches (cj::ScratchTurn, csrc/cj_engine.hpp): a small batch A and, with no wait
+between them, a batch B that makes every buffer of the scratch grow while A may still be in flight — on a FRESH engine, so that the
+scratch starts empty.  Metadata and results are device-resident; the engine is waited for once.  The same two batches on a second fresh
+engine, each waited for, must give the same results and bytes; both are held to the oracle / the encoder's model, with guard bytes around
+every output slot.  Then B, A, B on the first engine: a turn that does not grow, and one that does not shrink.  Closing the engines runs
+their teardown.  Every input is a valid stream."""
+import numpy as np
+import pytest
+
+import lz4_dict_model as D
+import oracle
+from cramjam_amd import _native as N
+
+pytestmark = pytest.mark.gpu
+
+G = 64                  # guard bytes around every output slot
+FILL = 0xA5
+
+
+class Batch:
+    """a batch in HBM: the chunks 16 bytes apart, output slot i G bytes behind slot i - 1's end in a buffer filled with FILL, the four
+    metadata rows and the results on the device"""
+
+    def __init__(self, e, chunks, caps):
+        self.e, self.n, self.caps = e, len(chunks), caps
+        off, run = [], 0
+        for c in chunks:
+            off.append(run); run += (len(c) + 15) // 16 * 16 + 16
+        blob = np.zeros(run + 64, np.uint8)
+        for o, c in zip(off, chunks):
+            blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
+        self.ooff, run = [], G
+        for c in caps:
+            self.ooff.append(run); run += int(c) + G
+        self.total = run + 64
+        self.ptrs = []
+        self.d_in, self.d_out = self._alloc(blob.nbytes), self._alloc(self.total)
+        e.h2d(self.d_in, blob)
+        N.check(N.lib().cj_memset_dev(e.h, self.d_out, FILL, self.total))
+        self.meta = []
+        for row in (off, [len(c) for c in chunks], self.ooff, caps):
+            self.meta.append(self._alloc(8 * self.n))
+            e.h2d(self.meta[-1], np.array(row, np.uint64))
+        self.result = self._alloc(8 * self.n)
+        N.check(N.lib().cj_memset_dev(e.h, self.result, 0xEE, 8 * self.n))
+
+    def _alloc(self, nbytes):
+        self.ptrs.append(self.e.alloc(nbytes))
+        return self.ptrs[-1]
+
+    def args(self):
+        """in_base, in_off, in_len, out_base, out_off, out_cap, result"""
+        return (self.d_in, self.meta[0], self.meta[1], self.d_out, self.meta[2], self.meta[3], self.result)
+
+    def read(self):
+        return self.e.d2h(self.result, 8 * self.n, "int64"), self.e.d2h(self.d_out, self.total)
+
+    def free(self):
+        for p in self.ptrs:
+            self.e.free(p)
+        self.ptrs = []
+
+
+def _held_to(want, res, out, ooff):
+    """chunk i produced exactly want[i] at its slot, and nothing was written outside [slot, slot + result) of any chunk"""
+    assert [int(r) for r in res] == [len(w) for w in want]
+    keep = np.ones(out.size, bool)
+    for o, w in zip(ooff, want):
+        assert out[o:o + len(w)].tobytes() == w
+        keep[o:o + len(w)] = False
+    assert (out[keep] == FILL).all(), "a write outside a chunk's result"
+
+
+# A case: chunks(n) -> (inputs, capacities, expected outputs) of its first n chunks; enqueue(engine, batch) submits on the engine's own stream
+class Blocks:
+    """the workgroup decoders' scratch (cj_engine::scratch): cj_batch_device, LZ4 decompress, 256-byte word-like raws"""
+    A, B = 4, 4000
+
+    def __init__(self, flags):
+        self.flags = flags
+        self.raws = [D.words(256, 9000 + k) for k in range(self.B)]
+        self.comp = [oracle.lz4_compress_raw(r)[1] for r in self.raws]
+        assert all(oracle.lz4_decompress_raw(c, 256) == (256, r) for c, r in zip(self.comp[:8], self.raws))
+
+    def chunks(self, n):
+        return self.comp[:n], [256] * n, self.raws[:n]
+
+    def enqueue(self, e, b):
+        N.check(N.lib().cj_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, self.flags, b.n, *b.args(), None))
+
+
+class Frames:
+    """the container batches' scratch (cj_engine::fb): cj_frame_batch_device, LZ4 frames, decompress"""
+    A, B = 4, 400
+
+    def __init__(self):
+        self.raws = [D.words(3000 + 7 * (k % 5), 12000 + k) for k in range(self.B)]
+        self.comp = [oracle.lz4_frame_compress(r, 4, oracle.LZ4F_CONTENT_SIZE)[1] for r in self.raws]
+        assert all(oracle.lz4_frame_decompress(c, len(r)) == (len(r), r) for c, r in zip(self.comp[:8], self.raws))
+
+    def chunks(self, n):
+        return self.comp[:n], [len(r) for r in self.raws[:n]], self.raws[:n]
+
+    def enqueue(self, e, b):
+        N.check(N.lib().cj_frame_batch_device(e.h, N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, b.n, *b.args(), None))
+
+
+class Dict:
+    """the dictionary encoder's staging (cj_engine::dict_stage): cj_dict_batch_device, compress against a 4 096-byte dictionary, 300-byte chunks"""
+    A, B = 4, 64
+
+    def __init__(self):
+        from test_enc2_linked_model import linked_lib, model_linked
+        self.d = D.dictionary(4096)
+        self.raws = [D.words(300, 15000 + k) for k in range(self.B)]
+        M = linked_lib()
+        self.want = [model_linked(M, self.d, r) for r in self.raws]
+        assert all(D.decode(w, 300, self.d) == (300, r) for w, r in zip(self.want, self.raws))
+        self.bound = N.lib().cj_lz4_block_compress_bound(300, 0)
+        self.d_dict = {}
+
+    def chunks(self, n):
+        return self.raws[:n], [self.bound] * n, self.want[:n]
+
+    def enqueue(self, e, b):
+        if e not in self.d_dict:
+            self.d_dict[e] = e.alloc(len(self.d))
+            e.h2d(self.d_dict[e], np.frombuffer(self.d, np.uint8))
+        N.check(N.lib().cj_dict_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, 0, b.n, *b.args(), self.d_dict[e], len(self.d), None))
+
+    def free(self):
+        for e, p in self.d_dict.items():
+            e.free(p)
+
+
+CASES = {
+    "workgroup decoder, parse inside the decoder": lambda: Blocks(0),
+    "workgroup decoder, parse kernel": lambda: Blocks(N.FLAG_FORCE_PARSE_KERNEL),
+    "frame batches": Frames,
+    "dictionary staging": Dict,
+}
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_a_turn_that_grows_the_scratch_behind_one_in_flight(name):
+    case = CASES[name]()
+    a, b = case.chunks(case.A), case.chunks(case.B)
+    first, second = N.Engine(0), N.Engine(0)
+    made = []
+
+    def batch(e, chunks):
+        made.append(Batch(e, chunks[0], chunks[1]))
+        return made[-1]
+
+    try:
+        # A and B back to back, one wait
+        a1, b1 = batch(first, a), batch(first, b)
+        case.enqueue(first, a1)
+        case.enqueue(first, b1)
+        first.sync()
+        # ... and each waited for, on an engine of its own
+        a2, b2 = batch(second, a), batch(second, b)
+        case.enqueue(second, a2)
+        second.sync()
+        case.enqueue(second, b2)
+        second.sync()
+        ref = {}
+        for key, x, y, chunks in (("a", a1, a2, a), ("b", b1, b2, b)):
+            (rx, ox), (ry, oy) = x.read(), y.read()
+            assert (rx == ry).all() and (ox == oy).all(), key
+            _held_to(chunks[2], rx, ox, x.ooff)
+            ref[key] = (rx, ox)
+        # a turn that does not grow, then one that does not shrink
+        again = [("b", batch(first, b)), ("a", batch(first, a)), ("b", batch(first, b))]
+        for _, x in again:
+            case.enqueue(first, x)
+        first.sync()
+        for key, x in again:
+            r, o = x.read()
+            assert (r == ref[key][0]).all() and (o == ref[key][1]).all(), key
+    finally:
+        for x in made:
+            x.free()
+        if hasattr(case, "free"):
+            case.free()
+        first.close()
+        second.close()
