@@ -196,7 +196,9 @@ __device__ __forceinline__ int64_t lz4_lane_walk(const uint8_t* in, uint32_t ien
             op += (uint32_t)lit;
             break;
         }
-        if (kCopy) lane_copy(out + op, in + ip, (uint32_t)lit, rem_out, rem_in);
+        // (a wide copy may run past the literals only over bytes the chunk is certain to produce: the match behind them is at least 4 long.
+        //  out_cap is a capacity, not the decoded size: an accepted chunk leaves [result, out_cap) as it found it)
+        if (kCopy) lane_copy(out + op, in + ip, (uint32_t)lit, (uint32_t)lit + 4u, rem_in);
         ip += (uint32_t)lit; op += (uint32_t)lit;
 
         const uint32_t o4 = ld_le_tail(in, ip, iend);       // >= 8 input bytes remain here
@@ -216,7 +218,7 @@ __device__ __forceinline__ int64_t lz4_lane_walk(const uint8_t* in, uint32_t ien
         mlen += 4u;
         if (offset == 0u || offset > op) return CJ_E_CORRUPT;
         if ((uint64_t)(cap - op) < mlen + 5u) return CJ_E_CORRUPT;
-        if (kCopy) lane_match(out + op, offset, (uint32_t)mlen, cap - op);
+        if (kCopy) lane_match(out + op, offset, (uint32_t)mlen, (uint32_t)mlen);      // exact: the final literals behind the last match may be none
         op += (uint32_t)mlen;
     }
     if (nseq_out) *nseq_out = nseq;

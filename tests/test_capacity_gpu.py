@@ -1,0 +1,200 @@
+"""The capacity sweep on the GPU (tests/capacity_cases.py: ~6 000 - 8 000 (stream, capacity) chunks per body, expected values from the CPU
+oracle) through every LZ4 and Snappy decoder path of a device-resident batch: one wavefront / one lane per chunk, the workgroup decoder
+behind the parse kernel and with the parse inside it, the default pipeline below and above CJ_FUSED_MAX_CHUNKS, the 32 KiB and 16 KiB
+windows with each placement of the parse, big chunks, the LZ4 size prefix, the shared dictionary.
+
+Slots as in tests/test_lz4_dict_gpu.py: inputs packed at every misalignment, 64 guard bytes of 0xA5 on both sides of every output slot, the
+whole output filled before the call.  For every chunk: the oracle's result (LZ4: any refusal is CJ_E_CORRUPT; Snappy and the size prefix:
+the oracle's code), the oracle's bytes in [0, result), both guards intact — accepted or refused —, and [result, cap) untouched where the
+chunk was accepted (a refused chunk may have written inside its own slot)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import capacity_cases as K
+import lz4_dict_model as D
+import test_spec_parse_model as M
+from cramjam_amd import _native as N
+
+pytestmark = pytest.mark.gpu
+LZ4, SN, DEC = N.CODEC_LZ4_BLOCK, N.CODEC_SNAPPY_RAW, N.OP_DECOMPRESS
+G = 64                                            # guard bytes around every output slot
+PROFILE = 0x1000                                  # CJ_FLAG_DEBUG_PROFILE: the debug counters count
+WAVE, LANE, LDS = N.FLAG_FORCE_WAVE_PER_CHUNK, N.FLAG_FORCE_LANE_PER_CHUNK, N.FLAG_FORCE_LDS_PER_CHUNK
+PK, FUSED = N.FLAG_FORCE_PARSE_KERNEL, N.FLAG_FORCE_FUSED_PARSE
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = N.Engine(0)
+    yield e
+    e.close()
+
+
+_layouts = {}
+
+
+def _layout(key, cases):
+    """the host side of one batch, built once per case list: packed input, the four descriptor rows, the offsets, and the mask of the
+    output bytes that must still be 0xA5 after the call (everything but [0, result) of an accepted and [0, cap) of a refused chunk)"""
+    if key not in _layouts:
+        n = len(cases)
+        off, run = np.zeros(n, np.uint64), 0
+        for i, c in enumerate(cases):
+            m = (5 * i) % 16
+            off[i] = run + m; run += (m + len(c["bytes"]) + 15) // 16 * 16 + 16
+        blob = np.zeros(run + 64, np.uint8)
+        for o, c in zip(off, cases):
+            blob[int(o):int(o) + len(c["bytes"])] = np.frombuffer(c["bytes"], np.uint8)
+        caps = np.array([c["cap"] for c in cases], np.uint64)
+        ooff = (G + np.concatenate([[0], np.cumsum(caps + np.uint64(G))[:-1]])).astype(np.uint64)
+        total = int(ooff[-1] + caps[-1]) + G + 64
+        keep = np.ones(total, bool)
+        for lo, c in zip(ooff, cases):
+            keep[int(lo):int(lo) + (c["result"] if c["result"] >= 0 else c["cap"])] = False
+        lens = np.array([len(c["bytes"]) for c in cases], np.uint64)
+        _layouts[key] = (blob, [off, lens, ooff, caps], total, keep, np.array([c["result"] for c in cases], np.int64))
+    return _layouts[key]
+
+
+def _run_and_check(eng, codec, flags, key, cases, dictionary=None):
+    blob, rows, total, keep, want = _layout(key, cases)
+    n = len(cases)
+    d_in, d_out, d_meta = eng.alloc(blob.nbytes), eng.alloc(total), eng.alloc(5 * 8 * n)
+    d_dict = eng.alloc(len(dictionary) + 32) if dictionary is not None else None
+    try:
+        eng.h2d(d_in, blob)
+        eng.h2d(d_meta, np.concatenate(rows + [np.zeros(n, np.uint64)]))
+        N.check(N.lib().cj_memset_dev(eng.h, d_out, 0xA5, total))
+        m = [d_meta + 8 * n * k for k in range(5)]
+        if dictionary is None:
+            eng.batch_device(codec, DEC, flags, n, d_in, m[0], m[1], d_out, m[2], m[3], m[4])
+        else:
+            eng.h2d(d_dict + 3, np.frombuffer(dictionary, np.uint8))             # (3 bytes off a granule)
+            N.check(N.lib().cj_dict_batch_device(eng.h, codec, DEC, flags, n, d_in, m[0], m[1], d_out, m[2], m[3], m[4], d_dict + 3, len(dictionary), None))
+        eng.sync()
+        res, out = eng.d2h(m[4], 8 * n, "int64"), eng.d2h(d_out, total)
+    finally:
+        for p in (d_in, d_out, d_meta, d_dict):
+            if p is not None: eng.free(p)
+    _check(key, flags, cases, res, out)
+    return res
+
+
+def _check(key, flags, cases, res, out):
+    _, rows, total, keep, want = _layout(key, cases)
+    tag = lambda i: (key, hex(flags), cases[i]["stream"], "cap", cases[i]["cap"], "U", cases[i]["U"], "got", int(res[i]), "want", int(want[i]))
+    bad = np.nonzero(res != want)[0]
+    assert len(bad) == 0, (len(bad), [tag(i) for i in bad[:6]])
+    ooff = rows[2]
+    dirty = np.nonzero(out[keep] != 0xA5)[0]
+    if len(dirty):                                 # which chunk's neighbourhood: the first byte that changed
+        at = int(np.nonzero(keep)[0][dirty[0]])
+        i = max(int(np.searchsorted(ooff, at, side="right")) - 1, 0)
+        assert False, ("a byte outside [0, result) changed", at - int(ooff[i]), len(dirty), tag(i))
+    for i in np.nonzero(want > 0)[0]:
+        lo = int(ooff[i])
+        assert out[lo:lo + int(want[i])].tobytes() == cases[i]["out"], ("bytes", tag(i))
+
+
+def _lz4_bodies(win):
+    return K.LZ4_BODIES if win >= 65536 else K.LZ4_BODIES[:2]          # (the body with the 300-byte runs: 64 KiB window only)
+
+
+LE32, LE16 = N.FLAG_CHUNKS_LE_32K, N.FLAG_CHUNKS_LE_16K
+PATHS = [pytest.param(WAVE, 65536, id="wave-per-chunk"), pytest.param(LANE, 65536, id="lane-per-chunk"),
+         pytest.param(LDS | PK, 65536, id="lds+parse-kernel"), pytest.param(LDS | FUSED, 65536, id="lds+fused-parse"), pytest.param(0, 65536, id="default"),
+         pytest.param(LE32, 32768, id="le32k"), pytest.param(LE32 | PK, 32768, id="le32k+parse-kernel"), pytest.param(LE32 | FUSED, 32768, id="le32k+fused-parse"),
+         pytest.param(LE16, 16384, id="le16k"), pytest.param(LE16 | PK, 16384, id="le16k+parse-kernel"), pytest.param(LE16 | FUSED, 16384, id="le16k+fused-parse")]
+
+
+@pytest.mark.parametrize("flags,win", PATHS)
+def test_lz4_capacity_sweep(eng, flags, win):
+    for body in _lz4_bodies(win):
+        _run_and_check(eng, LZ4, flags, ("lz4", body), K.lz4_cases(body))
+
+
+@pytest.mark.parametrize("flags,win", PATHS)
+def test_snappy_declared_length_and_capacity_sweep(eng, flags, win):
+    for body in K.SNAPPY_BODIES:
+        _run_and_check(eng, SN, flags, ("snappy", body), K.snappy_cases(body))
+
+
+@pytest.mark.parametrize("codec", [LZ4, SN])
+def test_default_pipeline_above_the_one_kernel_limit(eng, codec):
+    """16 384 + 41 chunks: the parse kernel in front of the workgroup decoder, chosen by the engine"""
+    cs = K.lz4_cases("b") if codec == LZ4 else K.snappy_cases("b")
+    n = 16384 + 41
+    assert len(cs) < n
+    _run_and_check(eng, codec, 0, ("above", codec), [cs[i % len(cs)] for i in range(n)])
+
+
+@pytest.mark.parametrize("codec", [LZ4, SN])
+def test_big_chunks_capacity_sweep(eng, codec):
+    """the ~100 KiB streams under CJ_FLAG_BIG_CHUNKS: around U and around 32 768, 65 536 (below it the chunk takes the small-chunk path: intended)
+    and 98 304 (the slabs' boundaries)"""
+    _run_and_check(eng, codec, N.FLAG_BIG_CHUNKS, ("big", codec), K.big_cases("lz4" if codec == LZ4 else "snappy"))
+
+
+@pytest.mark.parametrize("flags", [pytest.param(WAVE, id="wave-per-chunk"), pytest.param(LDS | FUSED, id="lds+fused-parse")])
+def test_lz4_size_prefix_sweep(eng, flags):
+    """the PREFIX takes the capacity's place (out_cap = U + 64): the prologue's codes for a prefix above out_cap, negative or too big"""
+    for body in K.LZ4_BODIES[:2]:
+        cs = K.lz4_prefix_cases(body)
+        assert {-4, -5, -6, -7} <= {c["result"] for c in cs}
+        _run_and_check(eng, LZ4, flags | N.FLAG_LZ4_SIZE_PREFIX, ("prefix", body), cs)
+
+
+def test_lz4_dictionary_capacity_sweep(eng):
+    """bodies whose first twenty matches reach into the dictionary (tests/lz4_dict_model.py decides)"""
+    for body in K.LZ4_BODIES:
+        cs = K.lz4_dict_cases(body)
+        assert sum(c["result"] >= 0 for c in cs) >= 150
+        _run_and_check(eng, LZ4, 0, ("dict", body), cs, dictionary=D.dictionary(4096))
+
+
+@functools.lru_cache(maxsize=None)
+def _elements(at, b):
+    """elements a walk of the true path reads before it ends or meets a malformed one (what the in-kernel parse counts)"""
+    n = ip = 0
+    while True:
+        ok, _, _, _, nxt, last = at(b, ip, len(b))
+        if not ok: return n
+        n += 1
+        if last or nxt == M.END: return n
+        ip = nxt
+
+
+def _reaches_the_in_kernel_checks(codec, c):
+    """lz4_decode_lds.hip (kFused prologue) + lds_shared.hpp fused_parse: a chunk is counted in cj_debug_fused_parse_paths when the prologue
+    does not hand it to the wave kernel (no room / a declared length of 0, above out_cap or above the window; no input) and its walk
+    finds 256 .. 16 384 elements — BEFORE the capacity rules give their verdict, so refused chunks count as well"""
+    blob, cap = c["bytes"], c["cap"]
+    if codec == LZ4:
+        return cap > 0 and cap <= 65536 and 0 < len(blob) <= 65504 and 256 <= _elements(M.seq_at, blob) <= 16384
+    hdr = next(i for i, x in enumerate(blob) if x < 0x80) + 1
+    dn = sum((x & 0x7f) << (7 * i) for i, x in enumerate(blob[:hdr]))
+    return 0 < dn <= min(cap, 65536) and 0 < len(blob) - hdr <= 65504 and 256 <= _elements(M.snappy_at, blob[hdr:]) <= 16384
+
+
+@pytest.mark.parametrize("codec", [LZ4, SN])
+def test_accepted_chunks_are_decoded_by_the_workgroup_decoder(eng, codec):
+    """On FORCE_LDS | FORCE_FUSED_PARSE with the debug counters on: the workgroup decoder completes exactly as many chunks as the oracle
+    accepts (cj_debug_lds_phase_cycles, word 5: one per chunk streamed out of the window) — none of them was quietly left to the wave
+    kernel.  cj_debug_fused_parse_paths counts at the ENTRY of the parse's capacity checks, so its sum is not the accepted count: it is
+    the number of chunks that reach those checks, accepted or refused (the rule: _reaches_the_in_kernel_checks) — every refusal of the
+    sweep beyond the prologue's was therefore made by Lz4Grammar / SnappyGrammar::check inside the decoder kernel."""
+    L = N.lib()
+    paths, cyc = (C.c_ulonglong * 3)(), (C.c_ulonglong * 16)()
+    for body in (K.LZ4_BODIES if codec == LZ4 else K.SNAPPY_BODIES):
+        cs = K.lz4_cases(body) if codec == LZ4 else K.snappy_cases(body)
+        accepted = sum(c["result"] >= 0 for c in cs)
+        reached = sum(_reaches_the_in_kernel_checks(codec, c) for c in cs)
+        assert accepted >= 150 and reached >= accepted + 3000
+        assert L.cj_debug_fused_parse_paths(paths, 1) == 0 and L.cj_debug_lds_phase_cycles(cyc, 1) == 0
+        _run_and_check(eng, codec, LDS | FUSED | PROFILE, ("lz4" if codec == LZ4 else "snappy", body), cs)
+        assert L.cj_debug_fused_parse_paths(paths, 0) == 0 and L.cj_debug_lds_phase_cycles(cyc, 0) == 0
+        assert sum(paths) == reached, (body, list(paths), reached)
+        assert cyc[5] == accepted, (body, cyc[5], accepted)

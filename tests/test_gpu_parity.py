@@ -600,44 +600,7 @@ def test_chunks_of_up_to_16384_sequences_take_the_workgroup_decoder(eng):
             assert all(bytes(o) == c for o, c in zip(outs, chunks)), (codec, flags)
 
 
-def _lz4_block(seqs, tail):
-    """an LZ4 block from (literal bytes, offset, match length) triples + the final literals — written by hand so that the
-    test chooses every length and alignment itself"""
-    out = bytearray()
-    def ext(v):
-        while v >= 255: out.append(255); v -= 255
-        out.append(v)
-    for lit, off, m in seqs:
-        out.append((min(len(lit), 15) << 4) | min(m - 4, 15))
-        if len(lit) >= 15: ext(len(lit) - 15)
-        out += lit
-        out += bytes((off & 255, off >> 8))
-        if m - 4 >= 15: ext(m - 4 - 15)
-    out.append(min(len(tail), 15) << 4)
-    if len(tail) >= 15: ext(len(tail) - 15)
-    out += tail
-    return bytes(out)
-
-
-def _snappy_raw(n, seqs, tail):
-    out = bytearray()
-    v = n
-    while v >= 128: out.append((v & 127) | 128); v >>= 7
-    out.append(v)
-    def lit(b):
-        if not b: return
-        k = len(b) - 1
-        if k < 60: out.append(k << 2)
-        else: out.append(61 << 2); out.extend((k & 255, k >> 8))
-        out.extend(b)
-    for l, off, m in seqs:
-        lit(l)
-        while m > 0:                                  # copies of at most 64 bytes, 2-byte offsets
-            k = min(m, 64) if m - min(m, 64) == 0 or m - min(m, 64) >= 4 else m - 4
-            out.append(((k - 1) << 2) | 2); out.extend((off & 255, off >> 8))
-            m -= k
-    lit(tail)
-    return bytes(out)
+from capacity_cases import _lz4_block, _snappy_raw  # noqa: E402  (the hand-written stream builders, shared with the capacity sweep)
 
 
 @pytest.mark.parametrize("codec", [LZ4, SNAPPY])

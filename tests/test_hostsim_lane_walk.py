@@ -27,11 +27,12 @@ g = json.load(open(%(golden)r))
 bad = 0
 def chk(blob, cap, tag):
     global bad
-    out = C.create_string_buffer(max(cap, 1)); ns1 = C.c_uint32(0); ns2 = C.c_uint32(0)
+    out = C.create_string_buffer(b"\xa5" * max(cap, 1), max(cap, 1)); ns1 = C.c_uint32(0); ns2 = C.c_uint32(0)
     r = S.sim_walk(blob, len(blob), out, cap, 1, C.byref(ns1))
     rp = S.sim_walk(blob, len(blob), None, cap, 0, C.byref(ns2))            # parse-only walk: same verdict, size, count
     er, eo = oracle.lz4_decompress_raw(blob, cap)
     ok = (r < 0) == (er < 0) and (r < 0 or (r == er and out.raw[:r] == eo)) and rp == r and (r < 0 or ns1.value == ns2.value)
+    ok = ok and (r < 0 or out.raw[r:cap] == b"\xa5" * (cap - r))          # the capacity is not the size: nothing behind the bytes produced
     if not ok:
         bad += 1; print("MISMATCH", tag, cap, r, rp, er)
 for v in g["vectors"]:
