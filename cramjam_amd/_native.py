@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("CJ_HIP_LIB") or os.path.join(_HERE, "libcramjam_hip.s
 CODEC_LZ4_BLOCK, CODEC_SNAPPY_RAW = 0, 1
 FORMAT_LZ4_FRAME, FORMAT_SNAPPY_FRAMED = 0, 1      # cj_frame_batch_*
 OP_DECOMPRESS, OP_COMPRESS = 0, 1
+DEFLATE_RAW, DEFLATE_ZLIB, DEFLATE_GZIP = 0, 1, 2  # cj_deflate_wrap (cj_deflate_batch_*)
 FLAG_LZ4_SIZE_PREFIX = 1
 FLAG_FORCE_WAVE_PER_CHUNK = 0x100
 FLAG_FORCE_LANE_PER_CHUNK = 0x200
@@ -20,6 +21,7 @@ FLAG_CHUNKS_LE_16K = 0x80
 FLAG_BIG_CHUNKS = 0x800            # decompress: reserve record areas for chunks of 64 KiB .. 256 KiB (cramjam_hip.h)
 E_NO_DEVICE = -100
 E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
+E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
 
 
@@ -77,6 +79,10 @@ SYMBOLS = {
     "cj_dict_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "cj_dict_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cj_dict_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _sz]),
+    "cj_deflate_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_deflate_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_deflate_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_deflate_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_blosc_chunk_max_compressed_len": (_sz, [_sz]),
     "cj_blosc_chunk_info": (_i64, [_vp, _sz, _vp]),
@@ -178,6 +184,7 @@ class Kind:
 BLOCKS = Kind("cj_batch_host", "cj_batch_device", "cj_batch_sizes_host", "cj_batch_sizes_device")
 FRAMES = Kind("cj_frame_batch_host", "cj_frame_batch_device", "cj_frame_batch_sizes_host", "cj_frame_batch_sizes_device")
 DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_host", "cj_dict_batch_sizes_device", dictionary=True)
+DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_batch_sizes_host", "cj_deflate_batch_sizes_device")   # what = a DEFLATE_*
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
 
 

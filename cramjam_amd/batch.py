@@ -533,3 +533,54 @@ def blosc_chunk_sizes_device(inp, in_off, in_len, result=None, device=None, stre
     """nbytes of every chunk of a device-resident batch after the header checks, or their error; enqueue-only like lz4_block_sizes_device.
     blosclz: as in blosc_decompress_chunks."""
     return _device_sizes(N.BLOSC, 0, N.BLOSC.read_flags(blosclz), inp, in_off, in_len, result, device, stream, sync)
+
+
+# ---- DEFLATE streams (cj_deflate_batch_* / cj_deflate_batch_sizes_*): raw DEFLATE, zlib streams, gzip members; decode only -----------
+# One stream per entry (ORC's zlib codec writes raw DEFLATE, Parquet GZIP pages are gzip members, numcodecs Zlib / GZip chunks are zlib
+# / gzip streams).  result[i] = the decoded length or a negative CJ_E_* code: -40 invalid DEFLATE data, -41 a zlib / gzip header zlib
+# refuses, -42 Adler-32 / CRC-32 / ISIZE mismatch, -43 the input ends inside the stream, -44 bytes behind the stream (a second gzip
+# member included), -6 a capacity too small.  The size query does not verify checksums.
+_DEFLATE_WRAP = {"raw": N.DEFLATE_RAW, "zlib": N.DEFLATE_ZLIB, "gzip": N.DEFLATE_GZIP}
+
+
+def _deflate_wrap(wrapper):
+    try:
+        return _DEFLATE_WRAP[wrapper]
+    except (KeyError, TypeError):
+        raise ValueError("wrapper must be 'raw', 'zlib' or 'gzip', not %r" % (wrapper,)) from None
+
+
+def deflate_sizes(streams, wrapper="raw", devices=None):
+    """decoded sizes of many DEFLATE streams held on the host (list of ints; negative = CJ_E_* code): the decoder's walk without its
+    stores — exact for a stream that is valid to its end; checksums are NOT verified here, gzip's ISIZE is not read"""
+    return _host_sizes(N.DEFLATE, _deflate_wrap(wrapper), 0, streams, devices)
+
+
+def deflate_decompress_many(streams, output_lens=None, wrapper="raw", devices=None, out=None):
+    """decode many DEFLATE streams; returns (results, outputs) as lz4_decompress_blocks.  wrapper: "raw" (RFC 1951), "zlib" (RFC 1950) or
+    "gzip" (RFC 1952, one member per stream).  output_lens=None: the sizes are asked for first (deflate_sizes; the input then crosses
+    the link twice): a stream the query rejects gets the query's code as its result and an empty output."""
+    wrap = _deflate_wrap(wrapper)
+    run = lambda caps: _run(wrap, N.OP_DECOMPRESS, 0, streams, caps, devices, out, N.DEFLATE)
+    if output_lens is not None:
+        return run(output_lens)
+    sizes = deflate_sizes(streams, wrapper, devices)
+    res, outs = run([max(s, 0) for s in sizes])
+    bad = [i for i, s in enumerate(sizes) if s < 0]
+    if bad:
+        res = list(res)
+        outs = list(outs)
+        for i in bad:
+            res[i], outs[i] = sizes[i], outs[i][:0]
+    return res, outs
+
+
+def deflate_decompress_many_device(inp, in_off, in_len, out, out_off, out_cap, wrapper="raw", result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of DEFLATE streams (arguments as lz4_decompress_blocks_device); enqueue-only with device-resident
+    metadata, a result tensor and sync=False."""
+    return _device_batch(N.DEFLATE, _deflate_wrap(wrapper), N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def deflate_sizes_device(inp, in_off, in_len, wrapper="raw", result=None, device=None, stream=None, sync=True):
+    """Decoded sizes of a device-resident batch of DEFLATE streams, as deflate_sizes; enqueue-only like lz4_block_sizes_device."""
+    return _device_sizes(N.DEFLATE, _deflate_wrap(wrapper), 0, inp, in_off, in_len, result, device, stream, sync)

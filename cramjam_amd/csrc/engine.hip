@@ -446,6 +446,11 @@ const char* cj_strerror(int64_t code) {
     case CJ_E_LZ4F_DECOMPRESS: return "LZ4 error: ERROR_decompressionFailed";
     case CJ_E_BLOSC_HEADER: return "blosc: corrupt chunk (invalid header, block table or stream length)";
     case CJ_E_BLOSC_UNSUPPORTED: return "blosc: unsupported chunk (only format version 2 with LZ4 streams; shuffle, bitshuffle or no filter)";
+    case CJ_E_DEFLATE_CORRUPT: return "deflate: invalid data (zlib: invalid block type / stored block lengths / code lengths set / bit length repeat / literal/length code / distance code / distance too far back)";
+    case CJ_E_DEFLATE_HEADER: return "deflate: invalid zlib or gzip header (zlib: incorrect header check / unknown compression method / invalid window size / unknown header flags set / header crc mismatch; preset dictionaries are not supported)";
+    case CJ_E_DEFLATE_CHECKSUM: return "deflate: checksum mismatch (zlib: incorrect data check / incorrect length check)";
+    case CJ_E_DEFLATE_EOF: return "deflate: the input ends inside the stream (zlib: incomplete or truncated stream)";
+    case CJ_E_DEFLATE_TRAILING: return "deflate: bytes behind the end of the stream (zlib: unused data); one chunk is exactly one stream";
     case CJ_E_NO_DEVICE: return "cramjam_hip: no usable HIP device (no CPU fallback exists)";
     case CJ_E_BAD_ARG: return "cramjam_hip: bad argument";
     case CJ_E_OOM: return "cramjam_hip: out of memory";

@@ -64,6 +64,15 @@ extern "C" {
 #define CJ_E_LZ4F_DECOMPRESS    (-27) /* LZ4F ERROR_decompressionFailed (malformed block) */
 #define CJ_E_BLOSC_HEADER       (-30) /* Blosc chunk: malformed header, block table or stream word (c-blosc returns -1) */
 #define CJ_E_BLOSC_UNSUPPORTED  (-31) /* Blosc chunk this library does not read or write: see "Blosc chunks" below */
+#define CJ_E_DEFLATE_CORRUPT    (-40) /* zlib: "invalid block type" / "invalid stored block lengths" / "too many length or distance symbols" /
+                                         "invalid code lengths set" / "invalid bit length repeat" / "invalid code -- missing end-of-block" /
+                                         "invalid literal/lengths set" / "invalid distances set" / "invalid literal/length code" /
+                                         "invalid distance code" / "invalid distance too far back" */
+#define CJ_E_DEFLATE_HEADER     (-41) /* zlib: "incorrect header check" / "unknown compression method" / "invalid window size" /
+                                         "unknown header flags set" / "header crc mismatch"; a zlib stream that asks for a preset dictionary */
+#define CJ_E_DEFLATE_CHECKSUM   (-42) /* zlib: "incorrect data check" (Adler-32, CRC-32) / "incorrect length check" (gzip ISIZE) */
+#define CJ_E_DEFLATE_EOF        (-43) /* zlib: "incomplete or truncated stream" (Z_BUF_ERROR): the input ends inside the stream or its trailer */
+#define CJ_E_DEFLATE_TRAILING   (-44) /* bytes behind the stream (zlib leaves them as unused data; one chunk is exactly one stream here) */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -336,6 +345,48 @@ CJ_API int cj_dict_batch_sizes_device(cj_engine* e, cj_codec codec, uint32_t fla
                                       int64_t* result, size_t dict_len, void* hip_stream);
 CJ_API int cj_dict_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks,
                                     const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result, size_t dict_len);
+
+/* Batches of DEFLATE streams — decode only: raw DEFLATE (RFC 1951: ORC's zlib codec), zlib streams (RFC 1950: Zarr / numcodecs Zlib)
+ * and gzip members (RFC 1952: Parquet GZIP pages, numcodecs GZip).  One chunk is exactly ONE stream, one wavefront decodes it
+ * (DESIGN.md 5.12); the accept / reject rules are zlib's inflate.  Addressing, the 16-byte-granule rule, stream rules, e == NULL,
+ * n_chunks == 0 and the null-pointer rules are cj_batch_device's / cj_batch_host's / cj_batch_sizes_*'s.
+ *   wrap        a cj_deflate_wrap; anything else is CJ_E_BAD_ARG.
+ *   op          CJ_OP_DECOMPRESS.  CJ_OP_COMPRESS (kept for a later encoder) and any other value: CJ_E_BAD_ARG.
+ *   flags       0.  Any bit set is CJ_E_BAD_ARG.
+ *   result[i]   the decoded length (>= 0) or CJ_E_*; one bad chunk never affects another; nothing is written outside
+ *               out_base + out_off[i] .. + out_cap[i], and what lies behind result[i] bytes (or anywhere in the slot of a chunk with an
+ *               error) is unspecified.  in_len[i] > 0x7FFFFFF0 is CJ_E_CORRUPT, out_cap[i] > 0x7E000000 is CJ_E_PREFIX_TOO_BIG, in that
+ *               chunk's own result[i], as elsewhere in this library.
+ *   errors      the FIRST one in stream order.  CJ_E_DEFLATE_HEADER: zlib — CM != 8, CINFO > 7, a bad FCHECK, FDICT (preset dictionaries
+ *               are not supported); gzip — a bad magic, CM != 8, a reserved FLG bit, a bad FHCRC (FEXTRA, FNAME, FCOMMENT and FHCRC are
+ *               walked).  CJ_E_DEFLATE_CORRUPT: block type 3, stored LEN / ~LEN mismatch, more than 286 length or 30 distance symbols, a
+ *               bad code-length repeat, an over-subscribed code, an incomplete code where zlib refuses it (all but a single code of
+ *               length 1 in a data alphabet), no end-of-block code, literal/length symbols 286 / 287, distance symbols 30 / 31, a
+ *               distance beyond the bytes produced so far.  A symbol's own validity comes before its fit: a match with a bad distance
+ *               that would also overrun the capacity is CJ_E_DEFLATE_CORRUPT.  CJ_E_OUT_TOO_SMALL: raised before the first byte that
+ *               would not fit is written.  CJ_E_DEFLATE_EOF: the input ends before the final block's end-of-block code or inside the
+ *               trailer.  CJ_E_DEFLATE_CHECKSUM: Adler-32 (zlib), CRC-32 or ISIZE (gzip), compared only after the stream has ended well.
+ *               CJ_E_DEFLATE_TRAILING: raw — whole bytes behind the byte that holds the final block's last bit; zlib / gzip — anything
+ *               behind the trailer.  A second gzip member IS trailing data: multi-member gzip files are split by the caller.
+ *   sizes       the same decoder with its stores and checksums compiled out: result[i] = the exact decoded length of a stream that is
+ *               valid up to its end, with the decoder's header, data, EOF and trailing errors; a total above 0x7E000000 is
+ *               CJ_E_PREFIX_TOO_BIG.  The checksums are NOT verified by the size query (it writes no output to sum), and gzip's ISIZE is
+ *               neither trusted nor read for the size: a stream the query sizes can still be CJ_E_DEFLATE_CHECKSUM in the decode.
+ * The _device calls only enqueue: no wait, no read-back, no engine scratch, no lock.  The _host calls are cj_batch_host's one-shot
+ * staging, synchronous. */
+typedef enum { CJ_DEFLATE_RAW = 0, CJ_DEFLATE_ZLIB = 1, CJ_DEFLATE_GZIP = 2 } cj_deflate_wrap;
+CJ_API int cj_deflate_batch_device(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n_chunks,
+                                   const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                   uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                   int64_t* result, void* hip_stream);
+CJ_API int cj_deflate_batch_host(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n_chunks,
+                                 const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                 uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API int cj_deflate_batch_sizes_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks,
+                                         const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                         int64_t* result, void* hip_stream);
+CJ_API int cj_deflate_batch_sizes_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks,
+                                       const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
 
 /* =====================================================================================
  * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706
