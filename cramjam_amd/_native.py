@@ -83,6 +83,9 @@ SYMBOLS = {
     "cj_deflate_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_deflate_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_deflate_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_deflate_compress_bound": (_sz, [_sz, _int]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_blosc_chunk_max_compressed_len": (_sz, [_sz]),
     "cj_blosc_chunk_info": (_i64, [_vp, _sz, _vp]),
@@ -112,6 +115,7 @@ BENCH_SYMBOLS = {
     "cj_debug_xxh32_device": (_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
 }
 
 _lib = None
@@ -161,8 +165,9 @@ class Kind:
     """One kind of batch: its four C symbols, and how `what` (a CODEC_* / FORMAT_*; Blosc chunks have none) and `params` (a BloscParams
     or None) enter their argument lists.  i = (in_base, in_off, in_len) / (in_ptrs, in_lens); o = (out_base, out_off, out_cap)."""
 
-    def __init__(self, host, device, sizes_host, sizes_device, blosc=False, dictionary=False):
+    def __init__(self, host, device, sizes_host, sizes_device, blosc=False, dictionary=False, one_op=False):
         self.host, self.device, self.sizes_host, self.sizes_device, self.blosc = host, device, sizes_host, sizes_device, blosc
+        self.one_op = one_op                        # the calls have one direction: their argument lists carry no `op`
         self.dictionary = dictionary                # the calls take (dict, dict_len) / (dict_len,) behind result: `params` = that tuple
 
     def read_flags(self, blosclz=False):
@@ -174,7 +179,8 @@ class Kind:
     def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
         if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)
             return (h, op) + i + o + (result, n, C.byref(params) if params is not None else None, flags, stream)
-        return (h, what, op, flags, n) + i + o + (result,) + (tuple(params) if self.dictionary else ()) + (stream,)
+        head = (h, what, flags, n) if self.one_op else (h, what, op, flags, n)
+        return head + i + o + (result,) + (tuple(params) if self.dictionary else ()) + (stream,)
 
     def sizes_args(self, h, what, flags, n, body, tail=(), dict_len=0):
         """body = i + (result,); tail = (stream,) for the device form; dict_len (dictionary batches only) goes between them"""
@@ -185,6 +191,7 @@ BLOCKS = Kind("cj_batch_host", "cj_batch_device", "cj_batch_sizes_host", "cj_bat
 FRAMES = Kind("cj_frame_batch_host", "cj_frame_batch_device", "cj_frame_batch_sizes_host", "cj_frame_batch_sizes_device")
 DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_host", "cj_dict_batch_sizes_device", dictionary=True)
 DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_batch_sizes_host", "cj_deflate_batch_sizes_device")   # what = a DEFLATE_*
+DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_batch_device", None, None, one_op=True)      # what = a DEFLATE_*; no size query
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
 
 

@@ -584,3 +584,52 @@ def deflate_decompress_many_device(inp, in_off, in_len, out, out_off, out_cap, w
 def deflate_sizes_device(inp, in_off, in_len, wrapper="raw", result=None, device=None, stream=None, sync=True):
     """Decoded sizes of a device-resident batch of DEFLATE streams, as deflate_sizes; enqueue-only like lz4_block_sizes_device."""
     return _device_sizes(N.DEFLATE, _deflate_wrap(wrapper), 0, inp, in_off, in_len, result, device, stream, sync)
+
+
+# ---- ... and into them (cj_deflate_compress_batch_* / cj_deflate_compress_bound; DESIGN.md 5.13) --------------------------------------
+# One stream per buffer: independent pieces of at most 64 KiB, each one stored, fixed or dynamic block.  result[i] = the stream's length
+# or a negative CJ_E_* code (-6: the capacity is too small; -1: a buffer above 0x7E000000 bytes).
+def deflate_compress_bound(n, wrapper="raw"):
+    """the capacity that always suffices for a buffer of n bytes (exact worst case of the layout; 0 above 0x7E000000).  No device."""
+    return N.lib().cj_deflate_compress_bound(n, _deflate_wrap(wrapper))
+
+
+def deflate_compress_many(buffers, wrapper="raw", devices=None, out=None):
+    """one DEFLATE stream per buffer; returns (results, outputs) as lz4_compress_blocks.  wrapper: "raw", "zlib" or "gzip" — what
+    deflate_decompress_many, zlib.decompress and gzip.decompress read.  out: as in lz4_decompress_blocks; it has to hold
+    sum(deflate_compress_bound(len(buffer), wrapper)) bytes."""
+    import numpy as np
+    wrap, L = _deflate_wrap(wrapper), N.lib()
+    views = [np.frombuffer(b, dtype=np.uint8) for b in buffers]          # borrowed, not copied
+    caps = [L.cj_deflate_compress_bound(a.size, wrap) for a in views]
+    offsets, total = [], 0
+    for c in caps:
+        offsets.append(total); total += c
+    if out is not None and memoryview(out).readonly:
+        raise ValueError("cramjam_amd.batch: out must be a writable buffer")
+    dst = np.empty(max(total, 1), np.uint8) if out is None else np.frombuffer(out, dtype=np.uint8)
+    if dst.size < total:
+        raise ValueError("cramjam_amd.batch: out holds %d bytes, the batch needs %d" % (dst.size, total))
+    base = dst.ctypes.data
+
+    def work(dev, idx):
+        k = len(idx)
+        ins = (_C.c_void_p * max(k, 1))(*[views[i].ctypes.data if views[i].size else None for i in idx])
+        lens = (_C.c_size_t * max(k, 1))(*[views[i].size for i in idx])
+        outs = (_C.c_void_p * max(k, 1))(*[base + offsets[i] for i in idx])
+        ocaps = (_C.c_size_t * max(k, 1))(*[caps[i] for i in idx])
+        res = np.empty(k, np.int64)
+        N.check(L.cj_deflate_compress_batch_host(_engine(dev).h, wrap, 0, k, ins, lens, outs, ocaps, res.ctypes.data))
+        return ([int(x) for x in res],)
+    res = _shard(devices, len(views), work)[0]
+    if out is None:
+        return res, [dst[o:o + max(r, 0)].tobytes() for o, r in zip(offsets, res)]
+    mv = memoryview(out).cast("B")
+    return res, [mv[o:o + max(r, 0)] for o, r in zip(offsets, res)]
+
+
+def deflate_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, wrapper="raw", result=None, device=None, stream=None, sync=True):
+    """Compress a device-resident batch into DEFLATE streams (arguments as lz4_compress_blocks_device); out_cap[i] >=
+    deflate_compress_bound(in_len[i], wrapper) always suffices.  Enqueue-only with device-resident metadata, a result tensor and
+    sync=False (a call that has to grow the engine's record slots waits for their previous user)."""
+    return _device_batch(N.DEFLATE_COMPRESS, _deflate_wrap(wrapper), N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)

@@ -115,6 +115,8 @@ __device__ __forceinline__ void lane_copy(gptr out, uint32_t o, gcptr in, uint32
 //   Fmt::emit_lane(in, out, o, lit0, lit, code, off) -> where its literals go   one lane writes one queued sequence at output offset o
 //                                               (the literal bytes themselves only below kLaneLit)
 //   Fmt::emit_wave(in, out, op, lit0, lit, off, mlen) -> new op   the whole wavefront writes one sequence of any size
+//   Fmt::kMaxDist                               the largest distance a candidate may have (65535: the table's lap, no condition compiled)
+//   Fmt::kStreamLiterals                        the literal bytes go into the stream (false: a format that keeps them in the input)
 // kW = wavefronts per chunk (1 or 2).  With two, a round is 512 positions and wavefront w owns its group w of 256: wavefront 0 probes and
 // inserts its two blocks, then wavefront 1 its two (one meeting in between); both measure their heads side by side, then select in position
 // order — wavefront 0's heads, then wavefront 1's (`cur`, the queue count and the output position travel through LDS).  A wavefront issues
@@ -171,9 +173,11 @@ struct Walk {
         const uint32_t before = wave_excl_add(on ? Fmt::seq_size(lit, code, off) : 0u, total);
         uint32_t lit_at = 0;
         if (on) lit_at = Fmt::emit_lane(in, out, op + before, lit0, lit, code, off);        // (copies its literals itself below kLaneLit)
-        for (uint64_t lm = bal(on && lit >= kLaneLit); lm != 0ull; lm &= lm - 1ull) {      // long literal runs: by the whole wavefront
-            const uint32_t i = ctz64(lm);
-            wave_copy((uint8_t*)out + rdlane(lit_at, i), (const uint8_t*)in + rdlane(lit0, i), rdlane(lit, i));
+        if constexpr (Fmt::kStreamLiterals) {
+            for (uint64_t lm = bal(on && lit >= kLaneLit); lm != 0ull; lm &= lm - 1ull) {      // long literal runs: by the whole wavefront
+                const uint32_t i = ctz64(lm);
+                wave_copy((uint8_t*)out + rdlane(lit_at, i), (const uint8_t*)in + rdlane(lit0, i), rdlane(lit, i));
+            }
         }
         op = uni(op + total);
         q_n = 0u;
@@ -218,7 +222,9 @@ struct Walk {
             for (int k = 0; k < 4; k++) {
                 const uint32_t p = p0 + k;
                 const uint32_t d = (p - t[k]) & 0xffffu;
-                if (mine) h.dd[k] = (d != 0u && d <= p && p <= round_last) ? d : 0u;
+                bool cand = d != 0u && d <= p && p <= round_last;
+                if constexpr (Fmt::kMaxDist < 0xffffu) cand = cand && d <= Fmt::kMaxDist;      // (a position without a candidate enters the table)
+                if (mine) h.dd[k] = cand ? d : 0u;
             }
             // A FOLLOWER — same candidate distance as its left neighbour — lies inside that neighbour's match if it is one: it is neither
             // verified (probe_verify) nor inserted.  (The DPP move runs with every lane: lane 32's left neighbour belongs to block 0.)

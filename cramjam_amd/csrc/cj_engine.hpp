@@ -160,6 +160,8 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     cj::Scratch dict_stage;        // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows
     cj::DevBuf d_dict_stage;
     cj::DevBuf d_dict;             // ... the dictionary of a host batch (under `mu`)
+    cj::Scratch deflate_slots;     // deflate_encode.hip: the workgroups' sequence-record slots of a compress batch
+    cj::DevBuf d_deflate_slots;
 };
 
 namespace cj {

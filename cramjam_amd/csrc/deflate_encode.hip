@@ -1,0 +1,249 @@
+// deflate_encode.hip — batches of inputs into DEFLATE streams (cj_deflate_compress_batch_device / _host, cj_deflate_compress_bound;
+// DESIGN.md §5.13): raw DEFLATE, zlib streams and gzip members, one stream per chunk.  One workgroup of two wavefronts owns a stream
+// and walks its independent pieces of at most 64 KiB in order:
+//   stage 1   enc2::Walk<DeflateFmt, 2> (cj_enc2.hpp: the matcher of the LZ4 and Snappy encoders, candidates limited to 32 768 back)
+//             leaves fixed-size sequence records in the workgroup's scratch slot; the literals stay in the input
+//   stage 2   deflate_enc_wave.hpp on the first wavefront: histograms, length-limited codes, the exact costs of a stored, a fixed and
+//             a dynamic block, the block behind the bit position the previous one left.  The second wavefront sums the input meanwhile
+//             (Adler-32 / CRC-32, once per stream)
+// The bytes are those of tests/hostsim/deflate_enc_model.c.  The slots are engine scratch within a fixed budget: a batch goes through
+// in slices of as many streams as there are slots (cj::ScratchTurn).  The device call only enqueues (a call that grows the scratch
+// waits for its previous user while it reallocates).
+#include "cj_stage.hpp"
+#include "cj_enc2.hpp"
+
+#include <atomic>
+
+namespace cj {
+
+#define CJ_LANES(lane) for (uint32_t lane = lane_id(); lane < 64u; lane += 64u)
+
+__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) { return uni(*p); }
+__device__ __forceinline__ uint32_t lds_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
+__device__ __forceinline__ uint32_t out_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
+__device__ __forceinline__ void lds_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
+__device__ __forceinline__ void lds_xor(uint32_t* p, uint32_t v) { atomicXor(p, v); }
+__device__ __forceinline__ void lds_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
+struct LaneBytes {      // (deflate_wave.hpp's decoder, not instantiated here, names it)
+    uint32_t v;
+    __device__ __forceinline__ void put(uint32_t k, uint32_t byte) { if (lane_id() == k) v = byte; }
+    __device__ __forceinline__ void flush(uint8_t* dst, uint32_t n) { if (lane_id() < n) dst[lane_id()] = (uint8_t)v; }
+};
+
+// a value per lane: the lane's own register
+struct LaneU32 { uint32_t v; __device__ __forceinline__ uint32_t& operator[](uint32_t) { return v; } };
+struct LaneU64 { uint64_t v; __device__ __forceinline__ uint64_t& operator[](uint32_t) { return v; } };
+__device__ __forceinline__ uint32_t lane_excl_add(LaneU32& x, LaneU32& before) {
+    uint32_t total;
+    before.v = wave_excl_add(x.v, total);
+    return total;
+}
+__device__ __forceinline__ uint32_t in_ld8(const uint8_t* p) { return *p; }
+__device__ __forceinline__ void out_st8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
+__device__ __forceinline__ void out_st32(uint8_t* p, uint32_t v) { *reinterpret_cast<enc2::u32_unaligned*>(p) = v; }
+struct DfeRec;
+__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i);
+
+}  // namespace cj
+
+#include "deflate_wave.hpp"          // adler32_lane, crc32_lane (the decoder's; neither file changes)
+#include "deflate_enc_wave.hpp"
+
+namespace cj {
+
+__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i) {
+    const uint4 v = *reinterpret_cast<const uint4*>(slot + i);
+    return DfeRec{v.x, v.y, v.z, v.w};
+}
+
+__device__ const Crc32Tables d_crc32_enc_tables = make_crc32_tables();
+
+// The matcher's format: a sequence is one record in the scratch slot (`out`), counted in records
+struct DeflateFmt {
+    static constexpr uint32_t kMaxDist = 32768u;
+    static constexpr bool kStreamLiterals = false;
+    static __device__ __forceinline__ uint32_t last_start(uint32_t n) { return n - 8u; }      // Snappy's: the position lanes read 8 bytes at a time
+    static __device__ __forceinline__ uint32_t limit(uint32_t n) { return n; }
+    static __device__ __forceinline__ uint32_t seq_size(uint32_t, uint32_t, uint32_t) { return 1u; }
+    static __device__ __forceinline__ void put(enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
+        if (o + 1u < kDfeSlotRecs) enc2::s128(out, 16u * o, make_uint4(lit0, lit, off, mlen));      // (the last record is the final literals')
+    }
+    static __device__ __forceinline__ uint32_t emit_lane(enc2::gcptr, enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t code, uint32_t off) {
+        put(out, o, lit0, lit, off, code + 4u);
+        return 0u;
+    }
+    static __device__ __forceinline__ uint32_t emit_wave(enc2::gcptr, enc2::gptr out, uint32_t op, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
+        if (lane_id() == 0u) put(out, op, lit0, lit, off, mlen);
+        return op + 1u;
+    }
+};
+
+constexpr uint32_t kDfeSlotBytes = (kDfeSlotRecs * 16u + 255u) & ~255u;
+constexpr int kDfeThreads = 128;
+
+// One workgroup per stream of the slice; slot blockIdx.x of `slots` is its own
+template <int WRAP>
+__global__ __launch_bounds__(kDfeThreads) void deflate_encode_kernel(BatchArgs a, uint8_t* slots) {
+    typedef enc2::Walk<DeflateFmt, 2> Matcher;
+    __shared__ uint16_t ht_lds[kHashSize];
+    __shared__ uint32_t scr[Matcher::kWords];
+    __shared__ DfeLds lds;
+    __shared__ uint32_t crc_adv[WRAP == kDfeGzip ? 1024 : 1];
+    __shared__ uint32_t sh[8];                     // 0 / 1 Adler-32's two sums, 2 the CRC register, 3 the stream still fits
+    const uint32_t chunk = blockIdx.x;
+    if (chunk >= a.n_chunks) return;
+    const uint32_t wave = uni(threadIdx.x >> 6), lane = lane_id();
+    const uint64_t n64 = a.in_len[chunk], cap64 = a.out_cap[chunk];
+    if (n64 > kDfeInMax) { if (threadIdx.x == 0) a.result[chunk] = CJ_E_INPUT_TOO_LARGE; return; }      // (the whole workgroup leaves)
+    const uint32_t n = (uint32_t)n64, cap = (uint32_t)(cap64 < 0xFFFFFFF0ull ? cap64 : 0xFFFFFFF0ull);
+    const uint8_t* in = a.in_base + a.in_off[chunk];
+    uint8_t* out = a.out_base + a.out_off[chunk];
+    DfeRec* slot = reinterpret_cast<DfeRec*>(slots + (uint64_t)blockIdx.x * kDfeSlotBytes);
+    if (WRAP == kDfeGzip)
+        for (uint32_t i = threadIdx.x; i < 1024u; i += kDfeThreads) crc_adv[i] = (&d_crc32_enc_tables.adv256[0][0])[i];
+    if (threadIdx.x < 8) sh[threadIdx.x] = 0u;
+    __syncthreads();
+
+    DfeOut W = {out, cap, 0u, 0u};
+    bool ok = true;
+    if (wave == 0u) ok = dfe_begin(&lds, W, WRAP, out, cap);
+    const uint32_t np = n == 0u ? 1u : (n + kDfePiece - 1u) / kDfePiece;
+    const HashTab ht{ht_lds};
+    for (uint32_t p = 0; p < np; p++) {
+        const uint8_t* pin = in + (uint64_t)p * kDfePiece;
+        const uint32_t pn = n - p * kDfePiece < kDfePiece ? n - p * kDfePiece : kDfePiece;
+        // ---- stage 1: both wavefronts
+        uint32_t nrec = 0, anchor = 0;
+        if (pn >= 8u) {
+            ht.clear(threadIdx.x, kDfeThreads);
+            ht.settle();
+            Matcher w{enc2::uniform_gptr(pin), (enc2::gptr)enc2::uniform_gptr(reinterpret_cast<const uint8_t*>(slot)), pn, DeflateFmt::last_start(pn),
+                      DeflateFmt::limit(pn), scr, ht, 0u, 0u, wave};
+            anchor = w.run(0u);
+            nrec = w.op;                                         // (the first wavefront's: it flushed the queue last)
+        }
+        if (wave == 0u) {
+            nrec = nrec + 1u < kDfeSlotRecs ? nrec : kDfeSlotRecs - 2u;
+            if (lane == 0u) slot[nrec] = DfeRec{anchor, pn - anchor, 0u, 0u};
+            nrec += 1u;
+        }
+        __syncthreads();                                         // the records, whoever wrote them, are the first wavefront's to read
+        // ---- stage 2: the first wavefront codes the piece, the second sums the input (once)
+        if (wave == 0u) {
+            if (ok) ok = dfe_piece(&lds, W, pin, pn, slot, nrec, p + 1u == np, dfe_tail_bytes(WRAP), nullptr);
+            if (lane == 0u) sh[3] = ok ? 1u : 0u;
+        } else if (p == 0u) {
+            const auto ld32 = [](const uint8_t* q) { uint32_t x; __builtin_memcpy(&x, q, 4); return x; };
+            if (WRAP == kDfeZlib) {
+                uint32_t s1, s2;
+                adler32_lane(in, n, lane, ld32, s1, s2);
+                lds_add(&sh[0], s1);
+                lds_add(&sh[1], s2);
+            }
+            if (WRAP == kDfeGzip) lds_xor(&sh[2], crc32_lane(in, n, lane, crc_adv, d_crc32_enc_tables.xpow8, ld32));
+        }
+        __syncthreads();
+        if (sh[3] == 0u) break;                                  // (the same word in both wavefronts: they leave together)
+    }
+    if (wave != 0u) return;
+    int64_t r = CJ_E_OUT_TOO_SMALL;
+    if (ok) {
+        uint32_t sum = 0;
+        if (WRAP == kDfeZlib) {
+            const uint32_t s1 = (1u + lds_ld(&sh[0])) % 65521u, s2 = (n % 65521u + lds_ld(&sh[1])) % 65521u;
+            sum = (s2 << 16) | s1;
+        }
+        if (WRAP == kDfeGzip) sum = ~lds_ld(&sh[2]);
+        r = dfe_end(&lds, W, WRAP, sum, n);
+    }
+    if (lane == 0u) a.result[chunk] = r;
+}
+
+}  // namespace cj
+
+namespace {
+
+// bytes of record slots per slice at most: 1280 slots, the workgroups of the raw / zlib kernel that 256 CUs hold at
+// once (five per CU by LDS) — more slots would only be memory the engine keeps
+constexpr uint64_t kSlotBudgetDefault = 1280ull * cj::kDfeSlotBytes;
+std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
+
+bool wrap_ok(int wrap) { return wrap == CJ_DEFLATE_RAW || wrap == CJ_DEFLATE_ZLIB || wrap == CJ_DEFLATE_GZIP; }
+
+// the workgroups of a wrapper's kernel that one CU holds at once (asked once; 0: not known)
+int resident_per_cu(int wrap) {
+    static std::atomic<int> known[3] = {{-1}, {-1}, {-1}};
+    int v = known[wrap].load();
+    if (v < 0) {
+        v = 0;
+        hipError_t err;
+        if (wrap == CJ_DEFLATE_RAW) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeRaw>, cj::kDfeThreads, 0);
+        else if (wrap == CJ_DEFLATE_ZLIB) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeZlib>, cj::kDfeThreads, 0);
+        else err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeGzip>, cj::kDfeThreads, 0);
+        if (err != hipSuccess) { (void)hipGetLastError(); v = 0; }
+        known[wrap].store(v);
+    }
+    return v;
+}
+
+// One turn at the engine's record slots (cj::ScratchTurn); enqueue only.  A slice is what the device holds at once — a launch of more
+// workgroups than that ends in a tail of a few of them (gzip, four per CU, on synth-v1: 25.7 GB/s in slices of 1280, 37.8 in slices of 1024) —
+// within the budget.
+int compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+                    const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
+    if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
+    uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kDfeSlotBytes);
+    const uint64_t resident = (uint64_t)resident_per_cu(wrap) * (uint64_t)e->n_cu;
+    if (resident != 0) slots_max = std::min(slots_max, resident);
+    const size_t per = (size_t)std::min<uint64_t>(n, slots_max);
+    cj::ScratchTurn turn(e->deflate_slots, s);
+    if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_deflate_slots, per * (size_t)cj::kDfeSlotBytes)) != 0) return turn.rc;
+    uint8_t* slots = (uint8_t*)e->d_deflate_slots.p;
+    for (size_t first = 0; first < n; first += per) {
+        cj::BatchArgs a;
+        cj::fill_args(a, 0u, std::min(per, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
+        const dim3 grid(a.n_chunks), block(cj::kDfeThreads);
+        if (wrap == CJ_DEFLATE_RAW) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeRaw>), grid, block, 0, s, a, slots);
+        else if (wrap == CJ_DEFLATE_ZLIB) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeZlib>), grid, block, 0, s, a, slots);
+        else hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeGzip>), grid, block, 0, s, a, slots);
+    }
+    return turn.done(s);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap) {
+    if (!wrap_ok((int)wrap) || n > cj::kDfeInMax) return 0;
+    return (size_t)cj::dfe_bound(n, (int)wrap);
+}
+
+int cj_deflate_compress_batch_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
+                                     const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result,
+                                     void* hip_stream) {
+    if (!wrap_ok((int)wrap) || flags != 0u || n_chunks > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    if (n_chunks && (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !result)) return CJ_E_BAD_ARG;
+    if (n_chunks == 0) return 0;
+    if (!e) e = cj::default_engine();
+    if (!e) return CJ_E_NO_DEVICE;
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    return compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
+}
+
+int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                   uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result) {
+    if (!wrap_ok((int)wrap) || flags != 0u || n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    if (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result)) return CJ_E_BAD_ARG;
+    if (n == 0) return 0;
+    if (!e) e = cj::default_engine();
+    if (!e) return CJ_E_NO_DEVICE;
+    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+        return compress_device(e, (int)wrap, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+    });
+}
+
+// tests: the bytes of record slots per slice of a DEFLATE compress batch (0 = the default); returns the previous value
+uint64_t cj_debug_deflate_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes ? bytes : kSlotBudgetDefault); }
+
+}  // extern "C"

@@ -22,6 +22,8 @@ __device__ __forceinline__ uint32_t emit_len_ext(uint8_t* out, uint32_t op, uint
 
 // ---- round-based matcher (cj_enc2.hpp): the encoder of every batch and of the split pieces of large buffers ----
 struct Lz4Fmt {
+    static constexpr uint32_t kMaxDist = 65535u;       // the lap of the matcher's 16-bit table
+    static constexpr bool kStreamLiterals = true;
     static __device__ __forceinline__ uint32_t last_start(uint32_t n) { return n - 12u; }      // a match may start here at the latest
     static __device__ __forceinline__ uint32_t limit(uint32_t n) { return n - 5u; }            // and must end here at the latest
     static __device__ __forceinline__ uint32_t seq_size(uint32_t lit, uint32_t code, uint32_t) {

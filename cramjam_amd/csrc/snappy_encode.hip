@@ -71,6 +71,8 @@ __device__ __forceinline__ uint32_t snappy_copy_size(uint32_t off, uint32_t len)
 
 // ---- round-based matcher (cj_enc2.hpp): the encoder of every batch and of the split pieces of large buffers ----
 struct SnappyFmt {
+    static constexpr uint32_t kMaxDist = 65535u;       // the lap of the matcher's 16-bit table
+    static constexpr bool kStreamLiterals = true;
     // a copy may start in the last 8 bytes of the input neither here nor (for its last 15) in the CPU encoders: the matcher's
     // position lanes read 8 bytes at a time
     static __device__ __forceinline__ uint32_t last_start(uint32_t n) { return n - 8u; }

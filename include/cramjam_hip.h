@@ -351,7 +351,8 @@ CJ_API int cj_dict_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags
  * (DESIGN.md 5.12); the accept / reject rules are zlib's inflate.  Addressing, the 16-byte-granule rule, stream rules, e == NULL,
  * n_chunks == 0 and the null-pointer rules are cj_batch_device's / cj_batch_host's / cj_batch_sizes_*'s.
  *   wrap        a cj_deflate_wrap; anything else is CJ_E_BAD_ARG.
- *   op          CJ_OP_DECOMPRESS.  CJ_OP_COMPRESS (kept for a later encoder) and any other value: CJ_E_BAD_ARG.
+ *   op          CJ_OP_DECOMPRESS.  CJ_OP_COMPRESS and any other value: CJ_E_BAD_ARG — the encoder has entry points of its own
+ *               (cj_deflate_compress_batch_*, below).
  *   flags       0.  Any bit set is CJ_E_BAD_ARG.
  *   result[i]   the decoded length (>= 0) or CJ_E_*; one bad chunk never affects another; nothing is written outside
  *               out_base + out_off[i] .. + out_cap[i], and what lies behind result[i] bytes (or anywhere in the slot of a chunk with an
@@ -387,6 +388,32 @@ CJ_API int cj_deflate_batch_sizes_device(cj_engine* e, cj_deflate_wrap wrap, uin
                                          int64_t* result, void* hip_stream);
 CJ_API int cj_deflate_batch_sizes_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks,
                                        const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+
+/* Batches of inputs INTO DEFLATE streams: one chunk in gives exactly one stream out — raw: RFC 1951 blocks, BFINAL on
+ * the last one only, the unused bits of the last byte 0; zlib: 78 01, the blocks, Adler-32 big-endian; gzip: a fixed 10-byte header (no
+ * flags, MTIME 0, XFL 0, OS 255), the blocks, CRC-32 and ISIZE.  The bytes depend on nothing but the input and the wrapper; an empty
+ * input gives a valid stream of one final block.  The input is cut into independent pieces of at most 64 KiB (no match crosses a
+ * piece, distances up to 32 768), each piece one block — stored, fixed or dynamic, whichever is smallest — behind the bit position the
+ * previous block left.  What cj_deflate_batch_* (zlib's inflate) accepts is the contract.  Addressing, the 16-byte-granule rule,
+ * stream rules, e == NULL, n_chunks == 0 and the null-pointer rules are cj_deflate_batch_*'s.
+ *   wrap        a cj_deflate_wrap; anything else is CJ_E_BAD_ARG.      flags   0; any bit set is CJ_E_BAD_ARG.
+ *   result[i]   the stream's length or CJ_E_*: in_len[i] > 0x7E000000 is CJ_E_INPUT_TOO_LARGE in that chunk's own result;
+ *               CJ_E_OUT_TOO_SMALL when the stream does not fit out_cap[i] (checked per block from its exact cost, before its first
+ *               store: nothing is written at or behind out_cap[i]; what lies in the slot of such a chunk is unspecified).
+ *   bound       cj_deflate_compress_bound(n, wrap): the exact worst case of this layout (every piece stored, two stored blocks for a
+ *               full piece, each header spilling into a byte of its own) = n + 10 * (n / 65536) + 5 * (n % 65536 != 0 || n == 0) +
+ *               0 / 6 / 18 for raw / zlib / gzip; a capacity of that many bytes never gives CJ_E_OUT_TOO_SMALL.  0 for a bad wrap or
+ *               n > 0x7E000000.  Pure arithmetic, no device.
+ * The _device call only enqueues (like every call, one that has to GROW the engine's scratch — the workgroups' record slots, within a
+ * fixed budget — waits for its previous user while it reallocates).  The _host call is cj_batch_host's one-shot staging, synchronous. */
+CJ_API int cj_deflate_compress_batch_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks,
+                                            const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                            uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                            int64_t* result, void* hip_stream);
+CJ_API int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks,
+                                          const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                          uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap);
 
 /* =====================================================================================
  * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706

@@ -41,6 +41,10 @@ CJ_API int cj_debug_blosc_filter(cj_engine* e, int forward, uint32_t filter, uin
  * previous value.  Tests force more than one slice with it. */
 CJ_API uint64_t cj_debug_dict_stage_budget(uint64_t bytes);
 
+/* DEFLATE compress (cj_deflate_compress_batch_*): the bytes of sequence-record slots per slice, one slot of 256.25 KiB per stream in flight
+ * (0 = the default, 1280 slots = 320 MiB); returns the previous value.  Tests force more than one slice with it. */
+CJ_API uint64_t cj_debug_deflate_slot_budget(uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

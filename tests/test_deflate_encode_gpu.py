@@ -1,0 +1,260 @@
+"""DEFLATE compress batches on the GPU (cj_deflate_compress_batch_* / cramjam_amd.batch.deflate_compress_*): per wrapper
+the kernel's bytes against the scalar model's (tests/hostsim/deflate_enc_model.c) on every case of tests/deflate_enc_cases.py, through
+the device and the C host entry, 64 guard bytes of 0xA5 around every output slot of both, inputs and outputs at every misalignment; the same
+streams decoded on the device behind the encoder on the same stream without a wait in between, and inflated by zlib; capacities exact,
+exact - 1 and 0 and batches of 1, 3 and 5 through both entries; a batch of 20 through several turns at a shrunken slot budget; the argument checks; torch
+tensors on a side stream; two engines on one device."""
+import os
+import subprocess
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+import deflate_enc_cases as E
+
+pytestmark = pytest.mark.gpu
+G = 64          # guard bytes around every output slot
+_want = {}
+
+
+def want(name, wrap):
+    """(result, stream) of the model, computed once"""
+    if (name, wrap) not in _want:
+        _want[(name, wrap)] = E.model(E.cases()[name], wrap)[:2]
+    return _want[(name, wrap)]
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from cramjam_amd import _native as N
+    from cramjam_amd.batch import _engine
+    return _engine(0), N
+
+
+def _device_call(e, N, wrap, chunks, caps, decode=False, in_lens=None):
+    """cj_deflate_compress_batch_device over chunks packed in HBM at every misalignment; slot i lies at least G bytes behind slot i - 1's
+    end, at every misalignment too, and the whole output is filled with 0xA5 first: (results, output, offsets).  decode: the streams
+    are then decoded by cj_deflate_batch_device on the same stream, with the encoder's device results as its in_len and no wait in
+    between: (.., decoded results, decoded output, its offsets) are appended"""
+    n = len(chunks)
+    off, run = [], 0
+    for i, c in enumerate(chunks):
+        m = (5 * i) % 16
+        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
+    blob = np.zeros(run + 64, np.uint8)
+    for o, c in zip(off, chunks):
+        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
+    ooff, run = [], G
+    for i, c in enumerate(caps):
+        run += (7 * i) % 16
+        ooff.append(run); run += int(c) + G
+    total = run + 64
+    lens = [len(c) for c in chunks] if in_lens is None else in_lens
+    doff, drun = [], G
+    for c in chunks:
+        doff.append(drun); drun += len(c) + G
+    metas = [np.array(a, np.uint64) for a in (off, lens, ooff, caps, doff, [len(c) for c in chunks])]
+    d_in, d_out, d_dec = e.alloc(blob.nbytes), e.alloc(total), e.alloc(drun + 64)
+    d_meta = [e.alloc(8 * n) for _ in range(8)]
+    L = N.lib()
+    try:
+        e.h2d(d_in, blob)
+        N.check(L.cj_memset_dev(e.h, d_out, 0xA5, total))
+        N.check(L.cj_memset_dev(e.h, d_dec, 0xA5, drun + 64))
+        for p, a in zip(d_meta, metas):
+            e.h2d(p, a)
+        e.sync()
+        N.check(L.cj_deflate_compress_batch_device(e.h, wrap, 0, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[6], None))
+        if decode:          # in_len = the encoder's results, still on the device
+            N.check(L.cj_deflate_batch_device(e.h, wrap, N.OP_DECOMPRESS, 0, n, d_out, d_meta[2], d_meta[6], d_dec, d_meta[4], d_meta[5], d_meta[7], None))
+        e.sync()
+        got = (e.d2h(d_meta[6], 8 * n, "int64"), e.d2h(d_out, total), ooff)
+        if decode:
+            got += (e.d2h(d_meta[7], 8 * n, "int64"), e.d2h(d_dec, drun + 64), doff)
+        return got
+    finally:
+        for p in [d_in, d_out, d_dec] + d_meta:
+            e.free(p)
+
+
+def _guards_intact(out, ooff, caps):
+    for i, (lo, cap) in enumerate(zip(ooff, caps)):
+        if not ((out[lo - G:lo] == 0xA5).all() and (out[lo + int(cap):lo + int(cap) + G] == 0xA5).all()):
+            return i
+    return None
+
+
+@pytest.mark.parametrize("wrap", E.WRAPS)
+def test_device_batch_emits_the_models_bytes_and_the_decoder_reads_them(eng, wrap):
+    e, N = eng
+    names = list(E.cases())
+    chunks = [E.cases()[k] for k in names]
+    caps = [E.bound(len(c), wrap) for c in chunks]
+    res, out, ooff, dres, dout, doff = _device_call(e, N, wrap, chunks, caps, decode=True)
+    for i, k in enumerate(names):
+        r, s = want(k, wrap)
+        assert res[i] == r, (k, int(res[i]), r)
+        got = out[ooff[i]:ooff[i] + r].tobytes()
+        assert got == s, (k, next(j for j in range(r) if got[j] != s[j]))
+        assert zlib.decompress(got, E.WBITS[wrap]) == chunks[i], k
+        assert dres[i] == len(chunks[i]) and dout[doff[i]:doff[i] + len(chunks[i])].tobytes() == chunks[i], (k, int(dres[i]))
+    assert _guards_intact(out, ooff, caps) is None and _guards_intact(dout, doff, [len(c) for c in chunks]) is None
+
+
+@pytest.mark.parametrize("wrap", E.WRAPS)
+def test_capacities_exact_one_less_and_zero(eng, wrap):
+    e, N = eng
+    names = list(E.cases())
+    chunks = [E.cases()[k] for k in names]
+    exact = [want(k, wrap)[0] for k in names]
+    mixed = [x - (i % 2) for i, x in enumerate(exact)]                 # a chunk that fits beside one that does not
+    for caps in (exact, [x - 1 for x in exact], [0] * len(names), mixed):
+        res, out, ooff = _device_call(e, N, wrap, chunks, caps)
+        for i, k in enumerate(names):
+            if caps[i] >= exact[i]:
+                assert res[i] == exact[i] and out[ooff[i]:ooff[i] + exact[i]].tobytes() == want(k, wrap)[1], (k, caps[i], int(res[i]))
+            else:
+                assert res[i] == E.OUT_TOO_SMALL, (k, caps[i], int(res[i]))
+        assert _guards_intact(out, ooff, caps) is None
+
+
+def test_batches_of_one_three_and_five_with_mixed_lengths(eng):
+    e, N = eng
+    pick = ["text_random_text", "len0", "text4k", "random65537", "len7", "zeros64k", "fixed300", "one40", "mlen517"]
+    for wrap in E.WRAPS:
+        for part in (pick[:1], pick[1:4], pick[4:9]):
+            chunks = [E.cases()[k] for k in part]
+            caps = [E.bound(len(c), wrap) for c in chunks]
+            res, out, ooff = _device_call(e, N, wrap, chunks, caps)
+            for i, k in enumerate(part):
+                assert (int(res[i]), out[ooff[i]:ooff[i] + max(int(res[i]), 0)].tobytes()) == want(k, wrap), (k, wrap)
+            assert _guards_intact(out, ooff, caps) is None
+
+
+def _host_call(e, N, wrap, chunks, caps):
+    """cj_deflate_compress_batch_host with out_ptrs / out_caps of its own: the inputs at every misalignment, slot i at least G bytes
+    behind slot i - 1's end at every misalignment too, the whole output filled with 0xA5 first: (results, output, offsets)"""
+    import ctypes as C
+    n = len(chunks)
+    off, run = [], 0
+    for i, c in enumerate(chunks):
+        m = (5 * i) % 16
+        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
+    blob = np.zeros(run + 64, np.uint8)
+    for o, c in zip(off, chunks):
+        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
+    ooff, run = [], G
+    for i, c in enumerate(caps):
+        run += (7 * i) % 16
+        ooff.append(run); run += int(c) + G
+    out = np.full(run + 64, 0xA5, np.uint8)
+    ins = (C.c_void_p * n)(*[blob.ctypes.data + o for o in off])
+    lens = (C.c_size_t * n)(*[len(c) for c in chunks])
+    outs = (C.c_void_p * n)(*[out.ctypes.data + o for o in ooff])
+    ocaps = (C.c_size_t * n)(*[int(c) for c in caps])
+    res = np.zeros(n, np.int64)
+    N.check(N.lib().cj_deflate_compress_batch_host(e.h, wrap, 0, n, ins, lens, outs, ocaps, res.ctypes.data))
+    return res, out, ooff
+
+
+@pytest.mark.parametrize("wrap", E.WRAPS)
+def test_host_entry_emits_the_models_bytes_at_every_capacity(eng, wrap):
+    """the C host entry itself, 64 guard bytes around every slot: capacities the bound, exact, exact - 1, 0 and mixed"""
+    e, N = eng
+    names = list(E.cases())
+    chunks = [E.cases()[k] for k in names]
+    exact = [want(k, wrap)[0] for k in names]
+    mixed = [x - (i % 2) for i, x in enumerate(exact)]
+    for caps in ([E.bound(len(c), wrap) for c in chunks], exact, [x - 1 for x in exact], [0] * len(names), mixed):
+        res, out, ooff = _host_call(e, N, wrap, chunks, caps)
+        for i, k in enumerate(names):
+            if caps[i] >= exact[i]:
+                assert res[i] == exact[i] and out[ooff[i]:ooff[i] + exact[i]].tobytes() == want(k, wrap)[1], (k, caps[i], int(res[i]))
+            else:
+                assert res[i] == E.OUT_TOO_SMALL, (k, caps[i], int(res[i]))
+        assert _guards_intact(out, ooff, caps) is None
+
+
+def test_host_batches_of_one_three_and_five_with_mixed_lengths(eng):
+    e, N = eng
+    pick = ["text_random_text", "len0", "text4k", "random65537", "len7", "zeros64k", "fixed300", "one40", "mlen517"]
+    for wrap in E.WRAPS:
+        for part in (pick[:1], pick[1:4], pick[4:9]):
+            chunks = [E.cases()[k] for k in part]
+            caps = [E.bound(len(c), wrap) for c in chunks]
+            res, out, ooff = _host_call(e, N, wrap, chunks, caps)
+            for i, k in enumerate(part):
+                assert (int(res[i]), out[ooff[i]:ooff[i] + max(int(res[i]), 0)].tobytes()) == want(k, wrap), (k, wrap)
+            assert _guards_intact(out, ooff, caps) is None
+
+
+@pytest.mark.parametrize("wrap", E.WRAPS)
+def test_host_batch_through_python(wrap):
+    from cramjam_amd import batch
+    names = list(E.cases())
+    chunks = [E.cases()[k] for k in names]
+    name = E.WRAP_NAME[wrap]
+    res, outs = batch.deflate_compress_many(chunks, wrapper=name)
+    for k, r, o in zip(names, res, outs):
+        assert (r, bytes(o)) == want(k, wrap), k
+    sub = chunks[:40]
+    need = sum(batch.deflate_compress_bound(len(c), name) for c in sub)
+    buf = bytearray(b"\xa5" * (need + 16))
+    res2, views = batch.deflate_compress_many(sub, wrapper=name, out=buf)
+    assert list(res2) == list(res[:40]) and [bytes(v) for v in views] == [bytes(o) for o in outs[:40]] and bytes(buf[need:]) == b"\xa5" * 16
+    back, raw = batch.deflate_decompress_many(outs, output_lens=[len(c) for c in chunks], wrapper=name)
+    assert list(back) == [len(c) for c in chunks] and [bytes(x) for x in raw] == [bytes(c) for c in chunks]
+    res3, outs3 = batch.deflate_compress_many(chunks, wrapper=name, devices=[0, 0])       # two host engines on device 0 equal one
+    assert list(res3) == list(res) and [bytes(o) for o in outs3] == [bytes(o) for o in outs]
+    with pytest.raises((TypeError, ValueError, BufferError)):                             # a buffer that cannot be written is refused, not written
+        batch.deflate_compress_many(sub[:2], wrapper=name, out=bytes(need))
+
+
+def test_twenty_chunks_through_several_turns_of_a_shrunken_slot_budget(eng):
+    e, N = eng
+    L = N.lib()
+    names = [k for k in E.cases() if len(E.cases()[k]) < 5000][:20]
+    assert len(names) == 20
+    chunks = [E.cases()[k] for k in names]
+    caps = [E.bound(len(c), E.GZIP) for c in chunks]
+    prev = L.cj_debug_deflate_slot_budget(3 * 262400)                 # three slots: seven turns
+    try:
+        res, out, ooff = _device_call(e, N, E.GZIP, chunks, caps)
+    finally:
+        assert L.cj_debug_deflate_slot_budget(prev) == 3 * 262400
+    for i, k in enumerate(names):
+        assert (int(res[i]), out[ooff[i]:ooff[i] + int(res[i])].tobytes()) == want(k, E.GZIP), k
+    assert _guards_intact(out, ooff, caps) is None
+
+
+def test_empty_batches_and_bad_arguments(eng):
+    e, N = eng
+    L = N.lib()
+    from cramjam_amd import batch
+    p = e.alloc(64)
+    try:
+        for wrap in E.WRAPS:
+            assert L.cj_deflate_compress_batch_device(e.h, wrap, 0, 0, None, None, None, None, None, None, None, None) == 0
+            assert L.cj_deflate_compress_batch_host(e.h, wrap, 0, 0, None, None, None, None, None) == 0
+            assert L.cj_deflate_compress_batch_device(e.h, wrap, 1, 1, p, p, p, p, p, p, p, None) == E.BAD_ARG
+            assert L.cj_deflate_compress_batch_device(e.h, wrap, 0, 1, p, p, p, None, p, p, p, None) == E.BAD_ARG
+            assert L.cj_deflate_batch_device(e.h, wrap, N.OP_COMPRESS, 0, 1, p, p, p, p, p, p, p, None) == E.BAD_ARG      # still refused there
+            assert batch.deflate_compress_many([], wrapper=E.WRAP_NAME[wrap]) == ([], [])
+        assert L.cj_deflate_compress_batch_device(e.h, 3, 0, 1, p, p, p, p, p, p, p, None) == E.BAD_ARG
+        assert L.cj_deflate_compress_batch_host(e.h, 3, 0, 0, None, None, None, None, None) == E.BAD_ARG
+    finally:
+        e.free(p)
+    # a limit that belongs to a chunk lands in that chunk's result: an announced length above 0x7E000000 beside a good chunk
+    t = E.cases()["text4k"]
+    res, out, ooff = _device_call(e, N, E.RAW, [t, t, t], [E.bound(len(t), E.RAW)] * 3, in_lens=[len(t), 0x7E000001, len(t)])
+    assert [int(r) for r in res] == [want("text4k", E.RAW)[0], E.INPUT_TOO_LARGE, want("text4k", E.RAW)[0]]
+    assert out[ooff[2]:ooff[2] + int(res[2])].tobytes() == want("text4k", E.RAW)[1]
+
+
+def test_device_entries_on_torch_tensors_on_a_side_stream():
+    """deflate_compress_many_device on torch tensors with sync=False, then the decode, in a child that imports torch BEFORE cramjam_amd"""
+    r = subprocess.run([sys.executable, os.path.join(E.ROOT, "tests", "deflate_encode_torch_child.py")], capture_output=True, text=True, timeout=600)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0 and "deflate encode: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
