@@ -193,6 +193,7 @@ DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_h
 DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_batch_sizes_host", "cj_deflate_batch_sizes_device")   # what = a DEFLATE_*
 DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_batch_device", None, None, one_op=True)      # what = a DEFLATE_*; no size query
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, BLOSC)}
 
 
 class Engine:
@@ -255,26 +256,28 @@ class Engine:
 
     def _host(self, entry, codec, op, flags, args, fn, params, dictionary):
         """entry: batch_host or batch_host_into of the CPython host layer (the engine scatters straight into the bytes objects / the buffer).
-        The call's signature follows from what is given: params, the bytes of a cj_blosc_params (b"" = decompress) — a batch of Blosc
-        chunks, codec is not used; dictionary, bytes-like (borrowed) — LZ4 blocks against it; neither — fn, one of the two entries of
-        cj_batch_host's signature.  Both: ValueError."""
+        fn: a Kind, or the name of its host entry — the call's signature is the Kind's: BLOSC takes params, the bytes of a cj_blosc_params
+        (b"" = decompress; codec is not used), DICT a dictionary, bytes-like (borrowed), DEFLATE_COMPRESS has no op.  None: DICT with a
+        dictionary, BLOSC with params, else BLOCKS.  An argument the Kind does not take: ValueError."""
         from . import _cramjam
-        if dictionary is not None:
-            fn = DICT.host
-        elif params is not None:
-            fn, codec = BLOSC.host, 0
+        if fn is None:
+            fn = DICT if dictionary is not None else BLOSC if params is not None else BLOCKS
+        kind = fn if isinstance(fn, Kind) else _HOST_KINDS[fn]
+        if (params is not None and not kind.blosc) or (dictionary is not None and not kind.dictionary):
+            raise ValueError("cramjam_amd: %s takes no %s" % (kind.host, "params" if params is not None and not kind.blosc else "dictionary"))
         try:
-            return getattr(_cramjam, entry)(self.h.value or 0, int(codec), int(op), int(flags), *args, _batch_host_addr(fn), params, dictionary)
+            return getattr(_cramjam, entry)(self.h.value or 0, 0 if kind.blosc else int(codec), int(op), int(flags), *args, _batch_host_addr(kind.host),
+                                            params, dictionary, kind.one_op)
         except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
             raise EngineError(_with_hip_error(str(ex))) from None
 
-    def batch_host(self, codec, op, flags, inputs, out_caps, fn="cj_batch_host", params=None, dictionary=None):
+    def batch_host(self, codec, op, flags, inputs, out_caps, fn=None, params=None, dictionary=None):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
         Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
-        fn: "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
+        fn: the Kind of the batch or the name of its host entry, "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
         return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params, dictionary)
 
-    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn="cj_batch_host", params=None, dictionary=None):
+    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn=None, params=None, dictionary=None):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
         return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params, dictionary)

@@ -36,20 +36,33 @@ def _pick(seq, idx):
 
 
 def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None):
-    """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress) or
-    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed).
+    """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress),
+    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*).
     out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
     tail = {"dictionary": params} if kind is N.DICT else {"params": params}
     if out is None:
-        return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind.host, **tail))
+        return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind, **tail))
     offsets, run = [], 0
     for c in out_caps:
         offsets.append(run); run += int(c)
     mv = memoryview(out).cast("B")
     res, = _shard(devices, n, lambda dev, idx: (_engine(dev).batch_host_into(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), out,
-                                                                             _pick(offsets, idx), kind.host, **tail),))
+                                                                             _pick(offsets, idx), kind, **tail),))
     return res, [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
+
+
+def _sizes_first(sizes, run):
+    """a decode without capacities: `sizes` are the size query's answers — a chunk it accepts gets exactly its size as capacity, a chunk it
+    rejects the query's code as its result and an empty output"""
+    res, outs = run([max(s, 0) for s in sizes])
+    bad = [i for i, s in enumerate(sizes) if s < 0]
+    if bad:
+        res = list(res)
+        outs = list(outs)
+        for i in bad:
+            res[i], outs[i] = sizes[i], outs[i][:0]
+    return res, outs
 
 
 def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=None, out=None, dictionary=None):
@@ -67,15 +80,7 @@ def lz4_decompress_blocks(blocks, output_lens=None, store_size=False, devices=No
     run = lambda caps: _run(N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, flags, blocks, caps, devices, out, kind, dictionary)
     if output_lens is not None:
         return run(output_lens)
-    sizes = lz4_block_sizes(blocks, store_size, devices, dictionary)
-    res, outs = run([max(s, 0) for s in sizes])
-    bad = [i for i, s in enumerate(sizes) if s < 0]
-    if bad:
-        res = list(res)
-        outs = list(outs)
-        for i in bad:
-            res[i], outs[i] = sizes[i], outs[i][:0]
-    return res, outs
+    return _sizes_first(lz4_block_sizes(blocks, store_size, devices, dictionary), run)
 
 
 def lz4_compress_blocks(chunks, store_size=True, devices=None, out=None, dictionary=None):
@@ -564,15 +569,7 @@ def deflate_decompress_many(streams, output_lens=None, wrapper="raw", devices=No
     run = lambda caps: _run(wrap, N.OP_DECOMPRESS, 0, streams, caps, devices, out, N.DEFLATE)
     if output_lens is not None:
         return run(output_lens)
-    sizes = deflate_sizes(streams, wrapper, devices)
-    res, outs = run([max(s, 0) for s in sizes])
-    bad = [i for i, s in enumerate(sizes) if s < 0]
-    if bad:
-        res = list(res)
-        outs = list(outs)
-        for i in bad:
-            res[i], outs[i] = sizes[i], outs[i][:0]
-    return res, outs
+    return _sizes_first(deflate_sizes(streams, wrapper, devices), run)
 
 
 def deflate_decompress_many_device(inp, in_off, in_len, out, out_off, out_cap, wrapper="raw", result=None, device=None, stream=None, sync=True):
@@ -598,34 +595,9 @@ def deflate_compress_many(buffers, wrapper="raw", devices=None, out=None):
     """one DEFLATE stream per buffer; returns (results, outputs) as lz4_compress_blocks.  wrapper: "raw", "zlib" or "gzip" — what
     deflate_decompress_many, zlib.decompress and gzip.decompress read.  out: as in lz4_decompress_blocks; it has to hold
     sum(deflate_compress_bound(len(buffer), wrapper)) bytes."""
-    import numpy as np
     wrap, L = _deflate_wrap(wrapper), N.lib()
-    views = [np.frombuffer(b, dtype=np.uint8) for b in buffers]          # borrowed, not copied
-    caps = [L.cj_deflate_compress_bound(a.size, wrap) for a in views]
-    offsets, total = [], 0
-    for c in caps:
-        offsets.append(total); total += c
-    if out is not None and memoryview(out).readonly:
-        raise ValueError("cramjam_amd.batch: out must be a writable buffer")
-    dst = np.empty(max(total, 1), np.uint8) if out is None else np.frombuffer(out, dtype=np.uint8)
-    if dst.size < total:
-        raise ValueError("cramjam_amd.batch: out holds %d bytes, the batch needs %d" % (dst.size, total))
-    base = dst.ctypes.data
-
-    def work(dev, idx):
-        k = len(idx)
-        ins = (_C.c_void_p * max(k, 1))(*[views[i].ctypes.data if views[i].size else None for i in idx])
-        lens = (_C.c_size_t * max(k, 1))(*[views[i].size for i in idx])
-        outs = (_C.c_void_p * max(k, 1))(*[base + offsets[i] for i in idx])
-        ocaps = (_C.c_size_t * max(k, 1))(*[caps[i] for i in idx])
-        res = np.empty(k, np.int64)
-        N.check(L.cj_deflate_compress_batch_host(_engine(dev).h, wrap, 0, k, ins, lens, outs, ocaps, res.ctypes.data))
-        return ([int(x) for x in res],)
-    res = _shard(devices, len(views), work)[0]
-    if out is None:
-        return res, [dst[o:o + max(r, 0)].tobytes() for o, r in zip(offsets, res)]
-    mv = memoryview(out).cast("B")
-    return res, [mv[o:o + max(r, 0)] for o, r in zip(offsets, res)]
+    caps = [L.cj_deflate_compress_bound(memoryview(b).nbytes, wrap) for b in buffers]
+    return _run(wrap, N.OP_COMPRESS, 0, buffers, caps, devices, out, N.DEFLATE_COMPRESS)
 
 
 def deflate_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, wrapper="raw", result=None, device=None, stream=None, sync=True):

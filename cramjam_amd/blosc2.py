@@ -82,9 +82,9 @@ def _one(op, data, cap, out, params, exc, blosclz=False):
     try:
         eng = _engine(0)
         if out is None:
-            res, outs = eng.batch_host(0, op, flags, [data], [cap], params=params)
+            res, outs = eng.batch_host(0, op, flags, [data], [cap], _N.BLOSC, params)
         else:
-            res, outs = eng.batch_host_into(0, op, flags, [data], [cap], out, None, params=params), None
+            res, outs = eng.batch_host_into(0, op, flags, [data], [cap], out, None, _N.BLOSC, params), None
     except _N.EngineError as ex:
         raise RuntimeError(str(ex)) from None
     if res[0] < 0:

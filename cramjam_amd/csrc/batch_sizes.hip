@@ -204,23 +204,15 @@ int sizes_launch(Query q, int what, uint32_t flags, size_t n, const uint8_t* in_
 
 int sizes_device(Query q, cj_engine* e, int what, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off,
                  const uint64_t* in_len, int64_t* result, void* hip_stream) {
-    if (!known(q, what) || !flags_ok(q, flags) || n > 0xFFFFFFF0ull || (n && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return sizes_launch(q, what, flags, n, in_base, in_off, in_len, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!known(q, what) || !flags_ok(q, flags)) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        return sizes_launch(q, what, flags, n, in_base, in_off, in_len, result, s);
+    });
 }
 
-// the host batch's staging (cj::host_batch) as a size query: no output
 int sizes_host(Query q, cj_engine* e, int what, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
-    if (!known(q, what) || !flags_ok(q, flags) || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    for (size_t i = 0; i < n; i++)
-        if (in_lens[i] && !in_ptrs[i]) return CJ_E_BAD_ARG;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, nullptr, nullptr, result, -1, [&](const uint8_t* d_in, uint8_t*, const cj::BatchRows& d, hipStream_t s) {
+    if (!known(q, what) || !flags_ok(q, flags)) return CJ_E_BAD_ARG;
+    return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine*, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
         return sizes_launch(q, what, flags, n, d_in, d.in_off, d.in_len, d.result, s);
     });
 }

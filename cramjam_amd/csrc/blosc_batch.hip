@@ -357,14 +357,11 @@ int cj_blosc_batch_device(cj_engine* e, cj_op op, const uint8_t* in_base, const 
                           const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, size_t n, const cj_blosc_params* params, uint32_t flags,
                           void* hip_stream) {
     if (!flags_ok(flags, op == CJ_OP_DECOMPRESS) || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
-    const int pc = params_check(op, params);
+    const int pc = params_check(op, params);           // (before n == 0)
     if (pc != 0) return pc;
-    if (n == 0) return 0;
-    if (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !result) return CJ_E_BAD_ARG;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return blosc_batch(e, op, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, params, flags, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    return cj::device_call(e, n, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
+        return blosc_batch(e, op, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, params, flags, s);
+    });
 }
 
 int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
@@ -372,13 +369,8 @@ int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n, const 
     if (!flags_ok(flags, op == CJ_OP_DECOMPRESS) || n > 0xFFFFFFF0ull || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
     const int pc = params_check(op, params);
     if (pc != 0) return pc;
-    if (n == 0) return 0;
-    if (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result) return CJ_E_BAD_ARG;
-    for (size_t i = 0; i < n; i++)
-        if ((in_lens[i] && !in_ptrs[i]) || (out_caps[i] && !out_ptrs[i])) return CJ_E_BAD_ARG;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+    return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, true,
+                         [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         return blosc_batch(e, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, params, flags, s);
     });
 }
@@ -399,15 +391,12 @@ int64_t cj_blosc_chunk_compress(const uint8_t* in, size_t n, uint8_t* out, size_
 
 int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                                 int64_t* result, void* hip_stream) {
-    if (!flags_ok(flags, true) || n > 0xFFFFFFF0ull || (n && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, hip_stream ? (hipStream_t)hip_stream : e->stream, (uint32_t)n,
-                       in_base, in_off, in_len, result, flags);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    return 0;
+    if (!flags_ok(flags, true)) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, result, flags);
+        HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+        return 0;
+    });
 }
 
 int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {

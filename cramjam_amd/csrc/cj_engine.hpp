@@ -165,6 +165,7 @@ struct cj_engine {                 // (members are destroyed last to first: the 
 };
 
 namespace cj {
+constexpr size_t kGridChunks = (size_t)1 << 22;      // chunks per launch of a wavefront-per-chunk kernel: a grid stays below 2^32 threads
 cj_engine* default_engine();     // lazily created on device 0 (tuning builds: $CJ_DEVICE); nullptr when no device is usable
 // submit one batch on stream s (slices very large decode batches); 0 or CJ_E_*
 int launch(cj_engine* e, cj_codec codec, cj_op op, const BatchArgs& a, hipStream_t s);

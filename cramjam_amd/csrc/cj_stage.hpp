@@ -118,6 +118,52 @@ using HostRun = std::function<int(const uint8_t* d_in, uint8_t* d_out, const Bat
 int host_batch(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, uint8_t* const* out_ptrs, const size_t* out_caps,
                int64_t* result, int lz4_room, const HostRun& run);
 
+// ---- what the C-ABI batch entries do behind their own checks of kind, op, flags, params and dictionary -----------------------------
+// The gate: the limit, every row pointer of `rows` present when n > 0, n == 0 -> 0.  kBatchGo: the call goes on.
+constexpr int kBatchGo = 1;
+inline int batch_gate(size_t n, std::initializer_list<const void*> rows) {
+    if (n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
+    for (const void* r : rows)
+        if (n && !r) return CJ_E_BAD_ARG;
+    return n == 0 ? 0 : kBatchGo;
+}
+// the scan of the entries that scan: no chunk with a length (a capacity) and no address
+inline bool chunk_ptrs_ok(size_t n, const uint8_t* const* ptrs, const size_t* lens) {
+    for (size_t i = 0; i < n; i++)
+        if (lens[i] && !ptrs[i]) return false;
+    return true;
+}
+// A device call: the gate, the engine (nullptr: the default one) and its device; launch(e, s) enqueues on the caller's stream or the engine's
+template <class F>
+int device_call(cj_engine* e, size_t n, std::initializer_list<const void*> rows, void* hip_stream, F&& launch) {
+    const int g = batch_gate(n, rows);
+    if (g != kBatchGo) return g;
+    if (!e && !(e = default_engine())) return CJ_E_NO_DEVICE;
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    return launch(e, hip_stream ? (hipStream_t)hip_stream : e->stream);
+}
+// A host call: the gate (scan: then the per-chunk pointers), the engine, host_batch around launch(e, d_in, d_out, d, s)
+template <class F>
+int host_call(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, uint8_t* const* out_ptrs, const size_t* out_caps,
+              int64_t* result, int lz4_room, bool scan, F&& launch) {
+    const int g = batch_gate(n, {in_ptrs, in_lens, out_ptrs, out_caps, result});
+    if (g != kBatchGo) return g;
+    if (scan && !(chunk_ptrs_ok(n, in_ptrs, in_lens) && chunk_ptrs_ok(n, out_ptrs, out_caps))) return CJ_E_BAD_ARG;
+    if (!e && !(e = default_engine())) return CJ_E_NO_DEVICE;
+    return host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, lz4_room,
+                      [&](const uint8_t* d_in, uint8_t* d_out, const BatchRows& d, hipStream_t s) { return launch(e, d_in, d_out, d, s); });
+}
+// A host size query: the gate, the scan, the engine, host_batch without an output around launch(e, d_in, d, s)
+template <class F>
+int host_sizes_call(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result, F&& launch) {
+    const int g = batch_gate(n, {in_ptrs, in_lens, result});
+    if (g != kBatchGo) return g;
+    if (!chunk_ptrs_ok(n, in_ptrs, in_lens)) return CJ_E_BAD_ARG;
+    if (!e && !(e = default_engine())) return CJ_E_NO_DEVICE;
+    return host_batch(e, n, in_ptrs, in_lens, nullptr, nullptr, result, -1,
+                      [&](const uint8_t* d_in, uint8_t*, const BatchRows& d, hipStream_t s) { return launch(e, d_in, d, s); });
+}
+
 // The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
 int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);
 

@@ -1,4 +1,5 @@
-// crc32_lanes.hpp — CRC-32 (IEEE 802.3, reflected 0xEDB88320: gzip's) of one piece by 64 lanes, the sibling of crc32c_lanes.hpp.
+// crc32_lanes.hpp — CRC-32 (IEEE 802.3, reflected 0xEDB88320: gzip's) of one piece by 64 lanes, the sibling of crc32c_lanes.hpp;
+// behind it Adler-32 (zlib's) by the same lanes: the two checksums of the DEFLATE decoder and encoder.
 //
 // The same linearity argument and the same lane mapping as there: lane l owns dwords l, l + 64, l + 128, ... of the piece (one
 // coalesced 256 B wave load per step), advances its register over the 256 bytes of the others with four table lookups and its last
@@ -64,6 +65,30 @@ CJ_HD32 inline uint32_t crc32_lane(const uint8_t* p, uint32_t len, uint32_t lane
         return gf_mul_ieee(s ^ d, xpow8[len - pos]);
     }
     return s;   // the lane owns nothing behind its last full step: s is 0 (or, for lane 0 of an empty piece, the init value)
+}
+
+// ---- Adler-32, lane-parallel ----------------------------------------------------------------------------------------------------------
+// adler = 1 + sum(x_i), sum2 = n + sum((n - i) * x_i), both mod 65521.  Lane l owns dwords l, l + 64, ... as above and
+// adds its bytes with their weights (n - i) mod 65521; the lanes' sums are added in LDS.  a, s2: this lane's two sums, below 65521.
+template <class Ld32>
+CJ_HD32 inline void adler32_lane(const uint8_t* p, uint32_t n, uint32_t lane, Ld32 ld32, uint32_t& a, uint32_t& s2) {
+    constexpr uint32_t M = 65521u;
+    uint64_t sa = 0, sb = 0;
+    uint32_t pos = 4u * lane;
+    uint32_t w = pos < n ? (n - pos) % M : 0u;           // weight of the byte at pos
+    while (pos < n && n - pos >= 4u) {
+        const uint32_t v = ld32(p + pos);
+        const uint32_t b0 = v & 0xffu, b1 = (v >> 8) & 0xffu, b2 = (v >> 16) & 0xffu, b3 = v >> 24;
+        sa += b0 + b1 + b2 + b3;
+        sb += (uint64_t)(b0 + b1 + b2 + b3) * (w + M) - (b1 + 2u * b2 + 3u * b3);      // weights w, w - 1, w - 2, w - 3 (mod M)
+        pos += 256u;
+        w = w >= 256u ? w - 256u : w + M - 256u;
+    }
+    if (pos < n) {
+        for (uint32_t k = 0; k < n - pos; k++) { sa += p[pos + k]; sb += (uint64_t)p[pos + k] * (n - pos - k); }
+    }
+    a = (uint32_t)(sa % M);
+    s2 = (uint32_t)(sb % M);
 }
 
 }  // namespace cj

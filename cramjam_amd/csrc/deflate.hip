@@ -1,20 +1,12 @@
 // deflate.hip — batches of DEFLATE streams, decode only (cj_deflate_batch_device / _host, cj_deflate_batch_sizes_device / _host;
 // DESIGN.md §5.12): raw DEFLATE, zlib streams and gzip members, one stream per chunk, one wavefront per stream, workgroups of four
 // wavefronts.  The decoder is deflate_wave.hpp (the same text tests/hostsim compiles for the host); this file gives it the wavefront:
-// the LDS accessors, the lanes, each wavefront's private tables in static LDS (9.6 KiB each; the gzip decode adds the workgroup's 4 KiB
+// the LDS accessors and the lanes (deflate_lanes.hpp, shared with the encoder), each wavefront's private tables in static LDS (9.6 KiB each; the gzip decode adds the workgroup's 4 KiB
 // of CRC-32 tables), and the launches.  The size query is the same decoder with stores and checksums compiled out.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock.
-#include "cj_stage.hpp"
+#include "deflate_lanes.hpp"
 
 namespace cj {
-
-#define CJ_LANES(lane) for (uint32_t lane = lane_id(); lane < 64u; lane += 64u)
-
-__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) { return uni(*p); }
-__device__ __forceinline__ uint32_t lds_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
-__device__ __forceinline__ uint32_t out_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
-__device__ __forceinline__ void lds_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-__device__ __forceinline__ void lds_xor(uint32_t* p, uint32_t v) { atomicXor(p, v); }
 
 // the round's literals: lane k keeps literal k in a register, one store puts the run out
 struct LaneBytes {
@@ -35,8 +27,8 @@ __device__ const Crc32Tables d_crc32_tables = make_crc32_tables();
 template <int WRAP, bool SIZE>
 __global__ __launch_bounds__(kBlockThreads) void deflate_kernel(BatchArgs a) {
     __shared__ DeflateLds lds[kWavesPerBlock];
-    __shared__ uint32_t crc_adv[(WRAP == kDfGzip && !SIZE) ? 1024 : 1];
-    if (WRAP == kDfGzip && !SIZE) {                    // (before any wavefront leaves: every thread reaches this barrier)
+    __shared__ uint32_t crc_adv[(WRAP == CJ_DEFLATE_GZIP && !SIZE) ? 1024 : 1];
+    if (WRAP == CJ_DEFLATE_GZIP && !SIZE) {                    // (before any wavefront leaves: every thread reaches this barrier)
         for (uint32_t i = threadIdx.x; i < 1024u; i += kBlockThreads) crc_adv[i] = (&d_crc32_tables.adv256[0][0])[i];
         __syncthreads();
     }
@@ -57,8 +49,6 @@ __global__ __launch_bounds__(kBlockThreads) void deflate_kernel(BatchArgs a) {
 
 namespace {
 
-constexpr size_t kGridChunks = (size_t)1 << 22;           // chunks per launch: a grid stays below 2^32 threads
-
 template <int WRAP, bool SIZE>
 void launch_one(const cj::BatchArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((cj::deflate_kernel<WRAP, SIZE>), dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a);
@@ -67,24 +57,22 @@ void launch_one(const cj::BatchArgs& a, hipStream_t s) {
 // enqueue only; size: the size query (the output rows are null)
 int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                    const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    for (size_t first = 0; first < n; first += kGridChunks) {
+    for (size_t first = 0; first < n; first += cj::kGridChunks) {
         cj::BatchArgs a;
-        cj::fill_args(a, 0u, std::min(kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, size ? nullptr : out_off + first,
+        cj::fill_args(a, 0u, std::min(cj::kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, size ? nullptr : out_off + first,
                       size ? nullptr : out_cap + first, result + first);
         switch (wrap * 2 + (size ? 1 : 0)) {
-        case 0: launch_one<cj::kDfRaw, false>(a, s); break;
-        case 1: launch_one<cj::kDfRaw, true>(a, s); break;
-        case 2: launch_one<cj::kDfZlib, false>(a, s); break;
-        case 3: launch_one<cj::kDfZlib, true>(a, s); break;
-        case 4: launch_one<cj::kDfGzip, false>(a, s); break;
-        default: launch_one<cj::kDfGzip, true>(a, s); break;
+        case 0: launch_one<CJ_DEFLATE_RAW, false>(a, s); break;
+        case 1: launch_one<CJ_DEFLATE_RAW, true>(a, s); break;
+        case 2: launch_one<CJ_DEFLATE_ZLIB, false>(a, s); break;
+        case 3: launch_one<CJ_DEFLATE_ZLIB, true>(a, s); break;
+        case 4: launch_one<CJ_DEFLATE_GZIP, false>(a, s); break;
+        default: launch_one<CJ_DEFLATE_GZIP, true>(a, s); break;
         }
     }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
-
-bool wrap_ok(int wrap) { return wrap == CJ_DEFLATE_RAW || wrap == CJ_DEFLATE_ZLIB || wrap == CJ_DEFLATE_GZIP; }
 
 }  // namespace
 
@@ -92,45 +80,32 @@ extern "C" {
 
 int cj_deflate_batch_device(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                             const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, void* hip_stream) {
-    if (!wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u || n_chunks > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n_chunks && (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !result)) return CJ_E_BAD_ARG;
-    if (n_chunks == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return deflate_launch((int)wrap, false, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!cj::deflate_wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        return deflate_launch((int)wrap, false, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+    });
 }
 
 int cj_deflate_batch_host(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
                           uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result) {
-    if (!wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u || n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result)) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+    if (!cj::deflate_wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
+                         [&](cj_engine*, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         return deflate_launch((int)wrap, false, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }
 
 int cj_deflate_batch_sizes_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                                   const uint64_t* in_len, int64_t* result, void* hip_stream) {
-    if (!wrap_ok((int)wrap) || flags != 0u || n_chunks > 0xFFFFFFF0ull || (n_chunks && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
-    if (n_chunks == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return deflate_launch((int)wrap, true, n_chunks, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_chunks, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        return deflate_launch((int)wrap, true, n_chunks, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
+    });
 }
 
 int cj_deflate_batch_sizes_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
-    if (!wrap_ok((int)wrap) || flags != 0u || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    for (size_t i = 0; i < n; i++)
-        if (in_lens[i] && !in_ptrs[i]) return CJ_E_BAD_ARG;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, nullptr, nullptr, result, -1, [&](const uint8_t* d_in, uint8_t*, const cj::BatchRows& d, hipStream_t s) {
+    if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine*, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
         return deflate_launch((int)wrap, true, n, d_in, d.in_off, d.in_len, nullptr, nullptr, nullptr, d.result, s);
     });
 }

@@ -439,7 +439,7 @@ __device__ __forceinline__ bool dfe_piece(DfeLds* L, DfeOut& W, const uint8_t* i
     return true;
 }
 
-constexpr int kDfeRaw = 0, kDfeZlib = 1, kDfeGzip = 2;      // cj_deflate_wrap
+constexpr int kDfeRaw = 0, kDfeZlib = 1, kDfeGzip = 2;      // cj_deflate_wrap (the one set of names: the decoder compares with the C-ABI's enum)
 __device__ __forceinline__ uint32_t dfe_head_bytes(int wrap) { return wrap == kDfeZlib ? 2u : wrap == kDfeGzip ? 10u : 0u; }
 __device__ __forceinline__ uint32_t dfe_tail_bytes(int wrap) { return wrap == kDfeZlib ? 4u : wrap == kDfeGzip ? 8u : 0u; }
 

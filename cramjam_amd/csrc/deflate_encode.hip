@@ -9,26 +9,13 @@
 // The bytes are those of tests/hostsim/deflate_enc_model.c.  The slots are engine scratch within a fixed budget: a batch goes through
 // in slices of as many streams as there are slots (cj::ScratchTurn).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
-#include "cj_stage.hpp"
+#include "deflate_lanes.hpp"
 #include "cj_enc2.hpp"
+#include "crc32_lanes.hpp"
 
 #include <atomic>
 
 namespace cj {
-
-#define CJ_LANES(lane) for (uint32_t lane = lane_id(); lane < 64u; lane += 64u)
-
-__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) { return uni(*p); }
-__device__ __forceinline__ uint32_t lds_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
-__device__ __forceinline__ uint32_t out_ld8(const uint8_t* p) { return uni((uint32_t)*p); }
-__device__ __forceinline__ void lds_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-__device__ __forceinline__ void lds_xor(uint32_t* p, uint32_t v) { atomicXor(p, v); }
-__device__ __forceinline__ void lds_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
-struct LaneBytes {      // (deflate_wave.hpp's decoder, not instantiated here, names it)
-    uint32_t v;
-    __device__ __forceinline__ void put(uint32_t k, uint32_t byte) { if (lane_id() == k) v = byte; }
-    __device__ __forceinline__ void flush(uint8_t* dst, uint32_t n) { if (lane_id() < n) dst[lane_id()] = (uint8_t)v; }
-};
 
 // a value per lane: the lane's own register
 struct LaneU32 { uint32_t v; __device__ __forceinline__ uint32_t& operator[](uint32_t) { return v; } };
@@ -46,7 +33,6 @@ __device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i);
 
 }  // namespace cj
 
-#include "deflate_wave.hpp"          // adler32_lane, crc32_lane (the decoder's; neither file changes)
 #include "deflate_enc_wave.hpp"
 
 namespace cj {
@@ -168,8 +154,6 @@ namespace {
 constexpr uint64_t kSlotBudgetDefault = 1280ull * cj::kDfeSlotBytes;
 std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
 
-bool wrap_ok(int wrap) { return wrap == CJ_DEFLATE_RAW || wrap == CJ_DEFLATE_ZLIB || wrap == CJ_DEFLATE_GZIP; }
-
 // the workgroups of a wrapper's kernel that one CU holds at once (asked once; 0: not known)
 int resident_per_cu(int wrap) {
     static std::atomic<int> known[3] = {{-1}, {-1}, {-1}};
@@ -215,30 +199,24 @@ int compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, co
 extern "C" {
 
 size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap) {
-    if (!wrap_ok((int)wrap) || n > cj::kDfeInMax) return 0;
+    if (!cj::deflate_wrap_ok((int)wrap) || n > cj::kDfeInMax) return 0;
     return (size_t)cj::dfe_bound(n, (int)wrap);
 }
 
 int cj_deflate_compress_batch_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                                      const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result,
                                      void* hip_stream) {
-    if (!wrap_ok((int)wrap) || flags != 0u || n_chunks > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n_chunks && (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !result)) return CJ_E_BAD_ARG;
-    if (n_chunks == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
+        return compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+    });
 }
 
 int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
                                    uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result) {
-    if (!wrap_ok((int)wrap) || flags != 0u || n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result)) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+    if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
+    return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
+                         [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         return compress_device(e, (int)wrap, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }

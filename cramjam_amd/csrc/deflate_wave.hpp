@@ -14,7 +14,7 @@
 // Mapping.  All stream state (bit buffer, positions, the symbol being decoded) is wave-uniform; the lanes build the Huffman tables
 // and move the bytes.  A round is a run of up to 64 literals, lane k keeping literal k, stored in ONE step when a match, the
 // end of the block or the 64th literal ends it; the match that ended it is then one wave_match_copy between two wave_order().  Stored
-// blocks are a wave_copy.  Checksums are one lane-parallel pass over the finished output (crc32_lanes.hpp; adler32_lane below).
+// blocks are a wave_copy.  Checksums are one lane-parallel pass over the finished output (crc32_lanes.hpp).
 #pragma once
 #include "crc32_lanes.hpp"
 
@@ -248,32 +248,6 @@ __device__ __forceinline__ int32_t df_symbol(DfBits& b, const uint32_t* tab, uin
     return 0;
 }
 
-// ---- Adler-32, lane-parallel ---------------------------------------------------------------------------------------------------------
-// adler = 1 + sum(x_i), sum2 = n + sum((n - i) * x_i), both mod 65521.  Lane l owns dwords l, l + 64, ... as in crc32_lanes.hpp and
-// adds its bytes with their weights (n - i) mod 65521; the lanes' sums are added in LDS.  a, s2: this lane's two sums, below 65521.
-template <class Ld32>
-__device__ __forceinline__ void adler32_lane(const uint8_t* p, uint32_t n, uint32_t lane, Ld32 ld32, uint32_t& a, uint32_t& s2) {
-    constexpr uint32_t M = 65521u;
-    uint64_t sa = 0, sb = 0;
-    uint32_t pos = 4u * lane;
-    uint32_t w = pos < n ? (n - pos) % M : 0u;           // weight of the byte at pos
-    while (pos < n && n - pos >= 4u) {
-        const uint32_t v = ld32(p + pos);
-        const uint32_t b0 = v & 0xffu, b1 = (v >> 8) & 0xffu, b2 = (v >> 16) & 0xffu, b3 = v >> 24;
-        sa += b0 + b1 + b2 + b3;
-        sb += (uint64_t)(b0 + b1 + b2 + b3) * (w + M) - (b1 + 2u * b2 + 3u * b3);      // weights w, w - 1, w - 2, w - 3 (mod M)
-        pos += 256u;
-        w = w >= 256u ? w - 256u : w + M - 256u;
-    }
-    if (pos < n) {
-        for (uint32_t k = 0; k < n - pos; k++) { sa += p[pos + k]; sb += (uint64_t)p[pos + k] * (n - pos - k); }
-    }
-    a = (uint32_t)(sa % M);
-    s2 = (uint32_t)(sb % M);
-}
-
-constexpr int kDfRaw = 0, kDfZlib = 1, kDfGzip = 2;      // cj_deflate_wrap
-
 // The walk of one stream (deflate_wave_decode below).  The capacity's rule is inflate's with ONE byte of room behind the capacity, the
 // rule the verdicts of the tests are computed by: the first byte that does not fit is not written but kept (`over`, its value in
 // over_byte: a later match may copy it, and the checksums cover it), the walk goes on without output, and whatever needs a SECOND
@@ -289,7 +263,7 @@ __device__ __forceinline__ int64_t deflate_wave_walk(const uint8_t* in, uint32_t
     uint32_t v = 0;
 
     // ---- the wrapper's header -------------------------------------------------------------------------------------------------
-    if (WRAP == kDfZlib) {
+    if (WRAP == CJ_DEFLATE_ZLIB) {
         uint32_t cmf, flg;
         if (!b.get(8, cmf) || !b.get(8, flg)) return CJ_E_DEFLATE_EOF;
         if (((cmf << 8) | flg) % 31u != 0u || (cmf & 15u) != 8u || (cmf >> 4) > 7u) return CJ_E_DEFLATE_HEADER;
@@ -298,7 +272,7 @@ __device__ __forceinline__ int64_t deflate_wave_walk(const uint8_t* in, uint32_t
             return CJ_E_DEFLATE_HEADER;
         }
     }
-    if (WRAP == kDfGzip) {
+    if (WRAP == CJ_DEFLATE_GZIP) {
         // every header byte enters the header's CRC-32 (bytewise; used only with FHCRC)
         uint32_t hcrc = 0xFFFFFFFFu, flg = 0;
         bool eof = false;
@@ -503,7 +477,7 @@ __device__ __forceinline__ int64_t deflate_wave_walk(const uint8_t* in, uint32_t
 
     // ---- the end of the stream --------------------------------------------------------------------------------------------------
     b.align();
-    if (WRAP == kDfZlib) {
+    if (WRAP == CJ_DEFLATE_ZLIB) {
         uint32_t sum;                                                        // big-endian in the stream
         if (!b.get(32, sum)) return CJ_E_DEFLATE_EOF;
         if (!SIZE) {
@@ -522,7 +496,7 @@ __device__ __forceinline__ int64_t deflate_wave_walk(const uint8_t* in, uint32_t
             if (__builtin_bswap32(sum) != ((s2 << 16) | a)) return CJ_E_DEFLATE_CHECKSUM;
         }
     }
-    if (WRAP == kDfGzip) {
+    if (WRAP == CJ_DEFLATE_GZIP) {
         uint32_t crc, isize;
         if (!b.get(32, crc)) return CJ_E_DEFLATE_EOF;
         if (!SIZE) {

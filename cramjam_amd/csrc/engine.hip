@@ -516,12 +516,12 @@ int cj_batch_device(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size
                     const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                     uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
                     int64_t* result, void* hip_stream) {
-    if (!e || n_chunks > 0xFFFFFFF0ull || (flags & ~kPublicFlags)) return CJ_E_BAD_ARG;
-    if (n_chunks == 0) return 0;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    cj::BatchArgs a;
-    fill_args(a, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
-    return launch(e, codec, op, a, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!e || (flags & ~kPublicFlags)) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_chunks, {}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        cj::BatchArgs a;
+        fill_args(a, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
+        return launch(e, codec, op, a, s);
+    });
 }
 
 int cj_engine_sync(cj_engine* e) {

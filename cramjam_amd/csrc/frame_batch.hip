@@ -100,20 +100,18 @@ int cj_frame_batch_device(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags,
                           const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                           uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
                           int64_t* result, void* hip_stream) {
-    if (!fb_args_ok(e, fmt, op, flags) || n_frames > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n_frames == 0) return 0;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return frame_batch(e, fmt, op, n_frames, in_base, in_off, in_len, out_base, out_off, out_cap, result,
-                       hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!fb_args_ok(e, fmt, op, flags)) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_frames, {}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        return frame_batch(e, fmt, op, n_frames, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+    });
 }
 
 int cj_frame_batch_host(cj_engine* e, cj_format fmt, cj_op op, uint32_t flags, size_t n,
                         const uint8_t* const* in_ptrs, const size_t* in_lens,
                         uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result) {
-    if (!fb_args_ok(e, fmt, op, flags) || (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result))) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
+    if (!fb_args_ok(e, fmt, op, flags)) return CJ_E_BAD_ARG;
+    return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
+                         [&](cj_engine*, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         return frame_batch(e, fmt, op, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }

@@ -124,8 +124,6 @@ namespace {
 constexpr uint64_t kStageBudgetDefault = 1ull << 30;      // bytes of staged slots per slice
 std::atomic<uint64_t> g_stage_budget{kStageBudgetDefault};
 
-constexpr size_t kGridChunks = (size_t)1 << 22;           // chunks per launch of the wavefront-per-chunk kernels: a grid stays below 2^32 threads
-
 bool args_ok(int codec, uint32_t flags, const void* dict, size_t dict_len) {
     return codec == CJ_CODEC_LZ4_BLOCK && (flags & ~CJ_FLAG_LZ4_SIZE_PREFIX) == 0u && (dict_len == 0 || dict != nullptr);
 }
@@ -153,8 +151,8 @@ int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_ba
         a.hist = g.r_hist;
         HIP_TRY(cj::launch_lz4_encode(a, s), CJ_E_NO_DEVICE);
     }
-    for (size_t first = 0; first < n; first += kGridChunks << 6) {
-        const uint32_t k = (uint32_t)std::min(kGridChunks << 6, n - first);
+    for (size_t first = 0; first < n; first += cj::kGridChunks << 6) {
+        const uint32_t k = (uint32_t)std::min(cj::kGridChunks << 6, n - first);
         hipLaunchKernelGGL(cj::dict_finish_kernel, dim3((k + cj::kBlockThreads - 1) / cj::kBlockThreads), dim3(cj::kBlockThreads), 0, s, k, in_len + first, out_base,
                            out_off + first, result + first, prefix);
     }
@@ -168,9 +166,9 @@ int batch_launch(cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t
     const uint8_t* dict_end = dict + dict_len;
     if (op == CJ_OP_COMPRESS)
         return compress_device(e, flags, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, dict_end - hist, hist, s);
-    for (size_t first = 0; first < n; first += kGridChunks) {
+    for (size_t first = 0; first < n; first += cj::kGridChunks) {
         cj::BatchArgs a;
-        cj::fill_args(a, flags, std::min(kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
+        cj::fill_args(a, flags, std::min(cj::kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
         hipLaunchKernelGGL(cj::lz4_dict_decode_kernel, dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a, dict_end, hist);
     }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
@@ -179,8 +177,8 @@ int batch_launch(cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t
 
 int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, size_t dict_len, hipStream_t s) {
     const uint32_t hist = (uint32_t)std::min<size_t>(dict_len, cj::kDictWindow);
-    for (size_t first = 0; first < n; first += kGridChunks) {
-        const uint32_t k = (uint32_t)std::min(kGridChunks, n - first);
+    for (size_t first = 0; first < n; first += cj::kGridChunks) {
+        const uint32_t k = (uint32_t)std::min(cj::kGridChunks, n - first);
         hipLaunchKernelGGL(cj::lz4_dict_size_kernel, dim3((k + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, k, in_base, in_off + first,
                            in_len + first, result + first, hist);
     }
@@ -205,24 +203,20 @@ extern "C" {
 int cj_dict_batch_device(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                          const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result,
                          const uint8_t* dict_dev, size_t dict_len, void* hip_stream) {
-    if (!args_ok((int)codec, flags, dict_dev, dict_len) || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS) || n_chunks > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n_chunks && (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !result)) return CJ_E_BAD_ARG;
-    if (n_chunks == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    if (dict_len == 0) return cj_batch_device(e, codec, op, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, hip_stream);
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return batch_launch(e, op, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, dict_dev, dict_len,
-                        hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (!args_ok((int)codec, flags, dict_dev, dict_len) || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
+    return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
+        if (dict_len == 0) return cj_batch_device(e, codec, op, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, hip_stream);
+        return batch_launch(e, op, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, dict_dev, dict_len, s);
+    });
 }
 
 int cj_dict_batch_host(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens,
                        uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, const uint8_t* dict_host, size_t dict_len) {
-    if (!args_ok((int)codec, flags, dict_host, dict_len) || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS) || n > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    if (n && (!in_ptrs || !in_lens || !out_ptrs || !out_caps || !result)) return CJ_E_BAD_ARG;
-    if (n == 0) return 0;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
+    if (!args_ok((int)codec, flags, dict_host, dict_len) || (op != CJ_OP_DECOMPRESS && op != CJ_OP_COMPRESS)) return CJ_E_BAD_ARG;
+    // (a dictionary of length 0 is the plain batch, which stages for itself: the gate and the engine stay here)
+    const int g = cj::batch_gate(n, {in_ptrs, in_lens, out_ptrs, out_caps, result});
+    if (g != cj::kBatchGo) return g;
+    if (!e && !(e = cj::default_engine())) return CJ_E_NO_DEVICE;
     if (dict_len == 0) return cj_batch_host(e, codec, op, flags, n, in_ptrs, in_lens, out_ptrs, out_caps, result);
     const int lz4_room = op == CJ_OP_COMPRESS ? ((flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1 : 0) : -1;
     return cj::host_batch(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, lz4_room, [&](const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
@@ -236,25 +230,19 @@ int cj_dict_batch_host(cj_engine* e, cj_codec codec, cj_op op, uint32_t flags, s
 
 int cj_dict_batch_sizes_device(cj_engine* e, cj_codec codec, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                                const uint64_t* in_len, int64_t* result, size_t dict_len, void* hip_stream) {
-    if (!args_ok((int)codec, flags, "", dict_len) || n_chunks > 0xFFFFFFF0ull || (n_chunks && (!in_base || !in_off || !in_len || !result))) return CJ_E_BAD_ARG;
+    if (!args_ok((int)codec, flags, "", dict_len)) return CJ_E_BAD_ARG;
     // the prefix answers without the stream, a dictionary of length 0 is the plain query
-    if (n_chunks == 0 || dict_len == 0 || (flags & CJ_FLAG_LZ4_SIZE_PREFIX))
-        return cj_batch_sizes_device(e, codec, flags, n_chunks, in_base, in_off, in_len, result, hip_stream);
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
-    return sizes_launch(n_chunks, in_base, in_off, in_len, result, dict_len, hip_stream ? (hipStream_t)hip_stream : e->stream);
+    if (dict_len == 0 || (flags & CJ_FLAG_LZ4_SIZE_PREFIX)) return cj_batch_sizes_device(e, codec, flags, n_chunks, in_base, in_off, in_len, result, hip_stream);
+    return cj::device_call(e, n_chunks, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
+        return sizes_launch(n_chunks, in_base, in_off, in_len, result, dict_len, s);
+    });
 }
 
 int cj_dict_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result,
                              size_t dict_len) {
-    if (!args_ok((int)codec, flags, "", dict_len) || n > 0xFFFFFFF0ull || (n && (!in_ptrs || !in_lens || !result))) return CJ_E_BAD_ARG;
-    if (n == 0 || dict_len == 0 || (flags & CJ_FLAG_LZ4_SIZE_PREFIX)) return cj_batch_sizes_host(e, codec, flags, n, in_ptrs, in_lens, result);
-    for (size_t i = 0; i < n; i++)
-        if (in_lens[i] && !in_ptrs[i]) return CJ_E_BAD_ARG;
-    if (!e) e = cj::default_engine();
-    if (!e) return CJ_E_NO_DEVICE;
-    return cj::host_batch(e, n, in_ptrs, in_lens, nullptr, nullptr, result, -1, [&](const uint8_t* d_in, uint8_t*, const cj::BatchRows& d, hipStream_t s) {
+    if (!args_ok((int)codec, flags, "", dict_len)) return CJ_E_BAD_ARG;
+    if (dict_len == 0 || (flags & CJ_FLAG_LZ4_SIZE_PREFIX)) return cj_batch_sizes_host(e, codec, flags, n, in_ptrs, in_lens, result);
+    return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine*, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
         return sizes_launch(n, d_in, d.in_off, d.in_len, d.result, dict_len, s);
     });
 }

@@ -1,6 +1,7 @@
 """Rates and ratios of the DEFLATE batch encoder on one MI355X.  Device-resident, HIP events, a warm-up and the median
 of RUNS runs with min .. max.  torch is imported first (one HIP runtime per process).  Prints one JSON line per figure.
   python tests/perf/deflate_enc_rates.py [--quick]      (--quick: one pass of every batch at a tenth of the size)
+  python tests/perf/deflate_enc_rates.py --python-host  (only the last figure: batch.deflate_compress_many host to host, wall time)
 Batches: the corpus's full 64 KiB chunks (bench.py --data corpus64k) tiled to 20 000, bench.py's synth-v1 chunks tiled to 20 000, and
 100 000 word-like records of 4 KiB; each as raw DEFLATE and as gzip (the difference is the checksum's cost).
 Yardsticks in the same session: zlib levels 1 and 6 on 16 threads over the same payloads (it releases the GIL), and this library's
@@ -116,16 +117,36 @@ def shape(side, eng, label, uniq, n):
         deflate_raw_over_it=round(rates[D.RAW] / lz, 2), **stats(ev))
 
 
+def python_host(uniq, n):
+    """batch.deflate_compress_many from host buffers to new `bytes` objects and into one buffer: wall time of the whole Python call"""
+    chunks = [uniq[i % len(uniq)] for i in range(n)]
+    total = sum(len(c) for c in chunks)
+    out = bytearray(sum(batch.deflate_compress_bound(len(c), "gzip") for c in chunks))
+    for label, kw in (("new bytes objects", {}), ("into one buffer", {"out": out})):
+        ms = []
+        for k in range(RUNS + 1):
+            t = time.perf_counter()
+            res, outs = batch.deflate_compress_many(chunks, wrapper="gzip", **kw)
+            if k or QUICK:
+                ms.append((time.perf_counter() - t) * 1e3)
+        assert min(res) > 0 and all(zlib.decompress(bytes(outs[i]), D.WBITS[D.GZIP]) == chunks[i] for i in range(0, n, max(n // 16, 1)))
+        say(what="batch.deflate_compress_many, host to host, gzip, %s: %d x %d B" % (label, n, len(chunks[0])),
+            GBps=round(total / statistics.median(ms) / 1e6, 2), **stats(ms))
+
+
 def main():
     import bench
     import oracle
+    corpus, _ = bench.corpus_chunks(65536)
+    if "--python-host" in sys.argv:
+        return python_host(corpus, 4096 // (10 if QUICK else 1))
     side = torch.cuda.Stream()
     eng = batch._engine(0)
     scale = 10 if QUICK else 1
-    corpus, _ = bench.corpus_chunks(65536)
     shape(side, eng, "corpus64k", corpus, 20000 // scale)
     shape(side, eng, "synth-v1", [oracle.synth_v1(65536, i) for i in range(256)], 20000 // scale)
     shape(side, eng, "text records", [D.words(4096, 9000 + k) for k in range(256)], 100000 // scale)
+    python_host(corpus, 4096 // scale)
 
 
 if __name__ == "__main__":

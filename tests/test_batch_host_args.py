@@ -28,6 +28,9 @@ def test_empty_batches_return_without_a_call():
         assert M.batch_host(0, 0, 0, 0, [], [], 0, None, d) == ([], [])
         assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), None, 0, None, d) == []
     assert M.batch_host(0, 0, 0, 0, [], [], 0, None, None) == ([], [])
+    for one_op in (True, False, 1, 0):                                              # (the signature without `op`: DEFLATE compress)
+        assert M.batch_host(0, 0, 0, 0, [], [], 0, None, None, one_op) == ([], [])
+        assert M.batch_host_into(0, 0, 0, 0, [], [], bytearray(4), None, 0, None, None, one_op) == []
 
 
 @pytest.mark.parametrize("entry", ENTRIES)
@@ -65,6 +68,14 @@ def test_a_dictionary_together_with_params(entry, params):
             entry(inputs, caps, 0, params, b"dictionary")
         with pytest.raises(ValueError):
             entry(inputs, caps, 0, params, b"")
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("params, dictionary", [(b"", None), (bytes(20), None), (None, b"dictionary"), (None, b""), (bytes(20), b"dictionary")])
+def test_one_op_together_with_params_or_a_dictionary(entry, params, dictionary):
+    for inputs, caps in (([b"a"], [1]), ([], [])):
+        with pytest.raises(ValueError):
+            entry(inputs, caps, 0, params, dictionary, True)
 
 
 @pytest.mark.parametrize("entry", ENTRIES)

@@ -119,6 +119,10 @@ def test_batch_argument_checks_need_no_device():
     assert L.cj_blosc_batch_host(None, 0, 0, 0, None, None, None, None, None, None) == 0
     assert L.cj_blosc_batch_host(None, 7, 0, 0, None, None, None, None, None, None) == -101         # unknown op
     assert L.cj_blosc_batch_host(None, 1, 0, 0, None, None, None, None, None, None) == -101         # compress without params
+    assert L.cj_blosc_batch_host(None, 0, 0, 3, None, None, None, None, None, None) == -101         # null pointers with n > 0
+    assert L.cj_blosc_batch_device(None, 0, None, None, None, None, None, None, None, 0, None, 0, None) == 0
+    assert L.cj_blosc_batch_device(None, 7, None, None, None, None, None, None, None, 0, None, 0, None) == -101
+    assert L.cj_blosc_batch_device(None, 0, None, None, None, None, None, None, None, 3, None, 0, None) == -101
     for bad, want in ((N.BloscParams(0, 1, 5, 1, 0), -101), (N.BloscParams(256, 1, 5, 1, 0), -101), (N.BloscParams(4, 1, 10, 1, 0), -101),
                       (N.BloscParams(4, 3, 5, 1, 0), N.E_BLOSC_UNSUPPORTED), (N.BloscParams(4, 4, 5, 1, 0), N.E_BLOSC_UNSUPPORTED),
                       (N.BloscParams(4, 1, 5, 0, 0), N.E_BLOSC_UNSUPPORTED), (N.BloscParams(4, 1, 5, 3, 0), N.E_BLOSC_UNSUPPORTED),

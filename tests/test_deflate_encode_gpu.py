@@ -208,6 +208,12 @@ def test_host_batch_through_python(wrap):
     assert list(back) == [len(c) for c in chunks] and [bytes(x) for x in raw] == [bytes(c) for c in chunks]
     res3, outs3 = batch.deflate_compress_many(chunks, wrapper=name, devices=[0, 0])       # two host engines on device 0 equal one
     assert list(res3) == list(res) and [bytes(o) for o in outs3] == [bytes(o) for o in outs]
+    buf4 = bytearray(b"\xa5" * (need + 16))                                               # the sharded scatter into one buffer through offsets
+    res4, views4 = batch.deflate_compress_many(sub, wrapper=name, devices=[0, 0], out=buf4)
+    assert [(r, bytes(v)) for r, v in zip(res4, views4)] == [want(k, wrap) for k in names[:40]] and bytes(buf4[need:]) == b"\xa5" * 16
+    for borrowed in ([bytearray(c) for c in sub], [memoryview(c) for c in sub], [np.frombuffer(c, np.uint8).copy() for c in sub]):
+        res5, outs5 = batch.deflate_compress_many(borrowed, wrapper=name)                 # any buffer is borrowed, not copied or converted
+        assert [(r, bytes(o)) for r, o in zip(res5, outs5)] == [want(k, wrap) for k in names[:40]]
     with pytest.raises((TypeError, ValueError, BufferError)):                             # a buffer that cannot be written is refused, not written
         batch.deflate_compress_many(sub[:2], wrapper=name, out=bytes(need))
 

@@ -197,6 +197,10 @@ def test_argument_refusals_that_need_no_device():
     # a batch without its pointers
     assert L.cj_dict_batch_device(None, 0, 0, 0, 3, None, None, None, None, None, None, None, d, 10, None) == D.BAD_ARG
     assert L.cj_dict_batch_host(None, 0, 0, 0, 3, None, None, None, None, None, d, 10) == D.BAD_ARG
+    for flags in (0, N.FLAG_LZ4_SIZE_PREFIX):
+        for dict_len in (10, 0):
+            assert L.cj_dict_batch_sizes_device(None, 0, flags, 3, None, None, None, None, dict_len, None) == D.BAD_ARG
+            assert L.cj_dict_batch_sizes_host(None, 0, flags, 3, None, None, None, dict_len) == D.BAD_ARG
     assert L.cj_debug_dict_stage_budget(0) == 1 << 30
     # the Python keyword: a Snappy call has none
     from cramjam_amd import batch
