@@ -1,7 +1,7 @@
 """DEFLATE test material shared by tests/test_deflate_model.py, tests/test_deflate_gpu.py and tests/golden/make_golden_deflate.py:
 the payloads and their matrix, the hand-written streams (a bit writer, no compressor), zlib's verdict at a capacity computed live
-(Python's zlib module), the size query's expectation derived from it, the loader of tests/golden/golden_deflate.json + .bin and the
-host build of the kernel's decoder (tests/hostsim/sim_deflate_decode.cpp).  Data and helpers only; nothing here needs a GPU."""
+(Python's zlib module), the size query's expectation derived from it, the loaders of tests/golden/golden_deflate.json + .bin and of
+golden_deflate_others.json + .bin (libdeflate's and zopfli's streams) and the host build of the kernel's decoder (tests/hostsim/sim_deflate_decode.cpp).  Data and helpers only; nothing here needs a GPU."""
 import bz2
 import ctypes as C
 import hashlib
@@ -65,7 +65,9 @@ def corpus_chunk():
 
 
 def payloads():
-    """name -> bytes, in the order of the issue's list (the 300 000-byte text is flush_text, written apart)"""
+    """name -> bytes, in the order of the issue's list (the 300 000-byte text is flush_text, written apart).  dist32768 repeats at
+    distance 32 768, but zlib's own streams of it stop at distance 32 506 (w_size - MIN_LOOKAHEAD): distances 32 767 and 32 768 are
+    written by tests/deflate_synth.py (family `matches`) and by the other encoders of tests/golden/golden_deflate_others.*"""
     half = words(32768, 11)
     return {"empty": b"", "one": b"Q", "text300": words(300, 1), "text4k": words(4096, 2), "corpus64k": corpus_chunk(), "zeros64k": bytes(65536),
             "random64k": random_bytes(65536, 3), "dist32768": half + half}
@@ -220,13 +222,15 @@ CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 CL_LENS = [4] * 13 + [5] * 6                       # a complete code-length code over all 19 symbols (13/16 + 6/32)
 
 
-def dyn_header(w, litlens, distlens, final=1, cl_syms=None, nlen=None, ndist=None):
-    """a dynamic block's header: every code length sent as itself (no repeats) unless cl_syms = [(symbol, extra bits value)] is given"""
+def dyn_header(w, litlens, distlens, final=1, cl_syms=None, nlen=None, ndist=None, cl_lens=None, ncode=19):
+    """a dynamic block's header: every code length sent as itself (no repeats) unless cl_syms = [(symbol, extra bits value)] is given;
+    cl_lens: the code-length code's own 19 lengths (CL_LENS when None), of which the first ncode in CL_ORDER are sent (HCLEN = ncode - 4)"""
     nlen, ndist = nlen or len(litlens), ndist or len(distlens)
-    w.put(final, 1).put(2, 2).put(nlen - 257, 5).put(ndist - 1, 5).put(19 - 4, 4)
-    for s in CL_ORDER:
-        w.put(CL_LENS[s], 3)
-    cl = canon(CL_LENS)
+    cl_lens = CL_LENS if cl_lens is None else cl_lens
+    w.put(final, 1).put(2, 2).put(nlen - 257, 5).put(ndist - 1, 5).put(ncode - 4, 4)
+    for s in CL_ORDER[:ncode]:
+        w.put(cl_lens[s], 3)
+    cl = canon(cl_lens)
     if cl_syms is None:
         cl_syms = [(l, 0) for l in list(litlens) + list(distlens)]
     for s, x in cl_syms:
@@ -410,6 +414,45 @@ def hand():
         assert [h[0] for h in hs] == [m["name"] for m in meta["hand"]], "tests/golden/golden_deflate.json is stale: run tests/golden/make_golden_deflate.py"
         _cache["hand"] = [dict(m, wrap=h[1], bytes=h[2]) for h, m in zip(hs, meta["hand"])]
     return _cache["hand"]
+
+
+def _load_others():
+    if "ometa" not in _cache:
+        with open(os.path.join(GOLDEN, "golden_deflate_others.json")) as f:
+            _cache["ometa"] = json.load(f)
+        with open(os.path.join(GOLDEN, "golden_deflate_others.bin"), "rb") as f:
+            _cache["obin"] = f.read()
+    return _cache["ometa"], _cache["obin"]
+
+
+def others():
+    """the streams libdeflate and zopfli wrote (tests/golden/make_golden_deflate_others.py): name = payload_encoder_wrapper, wrap, bytes,
+    result = n = cap (zlib's verdict at capacity n), sha256"""
+    if "others" not in _cache:
+        meta, blob = _load_others()
+        out, off = [], 0
+        for name, ln, n, h in meta["valid"]:
+            payload, enc, wr = name.split("_")
+            out.append(dict(name=name, wrap=("raw", "zlib", "gzip").index(wr), bytes=blob[off:off + ln], len=ln, result=n, n=n, cap=n, sha256=h, payload=payload, encoder=enc))
+            off += ln
+        assert off == len(blob)
+        _cache["others"] = out
+    return _cache["others"]
+
+
+def other_mutations():
+    """single-bit flips and cuts of four of them with zlib's verdict at cap"""
+    if "omut" not in _cache:
+        meta, _ = _load_others()
+        vs, empty = others(), sha(b"")
+        ms = []
+        for k, (b, bit, cut, r, n, h) in enumerate(meta["mutations"]):
+            base = vs[b]
+            s = flip(base["bytes"], bit) if cut is None else base["bytes"][:cut]
+            ms.append(dict(name="omut%03d_%s" % (k, base["name"]), base=base["name"], wrap=base["wrap"], bytes=s, bit=bit, cut=cut, cap=base["n"] + meta["mutation_slack"],
+                           result=r, n=n, sha256=h or empty))
+        _cache["omut"] = ms
+    return _cache["omut"]
 
 
 def cases(wrap=None):

@@ -1,9 +1,10 @@
 // deflate_wave.hpp compiled for the host: the kernel's own DEFLATE decoder with stand-ins for the wavefront's window, copies, lanes and
 // LDS, for tests/test_deflate_model.py (and, with SIM_MAIN, a stand-alone program that runs a file of cases: the form a sanitizer
-// build takes).  The stand-ins move the same bytes and abort on any read outside the stream, any write outside the capacity and any
-// LDS access outside the wavefront's DeflateLds; bytes that the window would load from beyond the stream read as 0xEE, so that a
+// build takes).  The stand-ins move the same bytes and end the decode with SIM_BOUNDS (-9999, no CJ_E_* code) on any read outside the
+// stream, any write outside the capacity and any LDS access outside the wavefront's DeflateLds, so that a test fails by name; bytes that the window would load from beyond the stream read as 0xEE, so that a
 // decision taken on them shows.  A CJ_LANES body runs for lanes 0..63 one after another: the header's rule (no body reads what
 // another lane wrote in the same body) is what makes that the wavefront's result.
+#include <setjmp.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +19,8 @@ namespace cj {
 static const uint8_t *g_in, *g_in_end;
 static uint8_t *g_out, *g_out_end;
 static const uint8_t *g_lds, *g_lds_end;
+static jmp_buf g_fail;                                                   // back into sim_deflate_decode (no frame between holds a destructor)
+[[noreturn]] static void sim_fail() { longjmp(g_fail, 1); }
 
 struct InWindow {
     const uint8_t* base;
@@ -28,7 +31,7 @@ struct InWindow {
         if (q >= 256u) { if (q < 504u) wpos += 256u; else anchor(pos); }
     }
     uint32_t fetch32(uint32_t pos) const {
-        if (pos - wpos > 507u) abort();                              // the register window's precondition
+        if (pos - wpos > 507u) sim_fail();                              // the register window's precondition
         uint32_t v = 0;
         for (uint32_t k = 0; k < 4; k++) v |= (uint32_t)(base + pos + k >= g_in && pos + k < iend ? base[pos + k] : 0xEE) << (8 * k);
         return v;
@@ -36,29 +39,29 @@ struct InWindow {
 };
 
 static void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n) {
-    if (n && (src < g_in || src + n > g_in_end || dst < g_out || dst + n > g_out_end)) abort();
+    if (n && (src < g_in || src + n > g_in_end || dst < g_out || dst + n > g_out_end)) sim_fail();
     memcpy(dst, src, n);
 }
 static void wave_match_copy(uint8_t* dst, uint32_t d, uint32_t m) {
-    if (d == 0 || dst - d < g_out || dst + m > g_out_end) abort();
+    if (d == 0 || dst - d < g_out || dst + m > g_out_end) sim_fail();
     for (uint32_t j = 0; j < m; j++) dst[j] = dst[(int64_t)j - d];
 }
 static void wave_order() {}
 
 static void lds_check(const void* p, size_t n) {
-    if ((const uint8_t*)p < g_lds || (const uint8_t*)p + n > g_lds_end) abort();
+    if ((const uint8_t*)p < g_lds || (const uint8_t*)p + n > g_lds_end) sim_fail();
 }
 static uint32_t lds_ld(const uint32_t* p) { lds_check(p, 4); return *p; }
 static uint32_t lds_ld8(const uint8_t* p) { lds_check(p, 1); return *p; }
-static uint32_t out_ld8(const uint8_t* p) { if (p < g_out || p >= g_out_end) abort(); return *p; }
+static uint32_t out_ld8(const uint8_t* p) { if (p < g_out || p >= g_out_end) sim_fail(); return *p; }
 static void lds_add(uint32_t* p, uint32_t v) { lds_check(p, 4); *p += v; }
 static void lds_xor(uint32_t* p, uint32_t v) { lds_check(p, 4); *p ^= v; }
 
 struct LaneBytes {
     uint8_t v[64];
-    void put(uint32_t k, uint32_t byte) { if (k >= 64u) abort(); v[k] = (uint8_t)byte; }
+    void put(uint32_t k, uint32_t byte) { if (k >= 64u) sim_fail(); v[k] = (uint8_t)byte; }
     void flush(uint8_t* dst, uint32_t n) {
-        if (n > 64u || dst < g_out || dst + n > g_out_end) abort();
+        if (n > 64u || dst < g_out || dst + n > g_out_end) sim_fail();
         memcpy(dst, v, n);
     }
 };
@@ -77,6 +80,7 @@ extern "C" long long sim_deflate_decode(int wrap, int size, const unsigned char*
     cj::g_in = in; cj::g_in_end = in + n; cj::g_out = out; cj::g_out_end = out + (size ? 0 : cap);
     cj::g_lds = (const uint8_t*)L; cj::g_lds_end = cj::g_lds + sizeof *L;
     const uint32_t* adv = &g_crc.adv256[0][0];
+    if (setjmp(cj::g_fail)) { free(L); return -9999; }                   // SIM_BOUNDS: a stand-in's check fired
     long long r = CJ_E_BAD_ARG;
     if (!size) {
         if (wrap == 0) r = cj::deflate_wave_decode<0, false>(in, n, out, cap, L, adv, g_crc.xpow8);
