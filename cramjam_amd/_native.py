@@ -22,6 +22,8 @@ FLAG_BIG_CHUNKS = 0x800            # decompress: reserve record areas for chunks
 E_NO_DEVICE = -100
 E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
 E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
+E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -50, -51, -52, -53, -54
+ZSTD_FRAMES = 0                    # cj_zstd_format (cj_zstd_batch_*)
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
 
 
@@ -83,6 +85,10 @@ SYMBOLS = {
     "cj_deflate_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_zstd_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_zstd_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_zstd_batch_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_zstd_batch_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_deflate_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_bound": (_sz, [_sz, _int]),
@@ -116,6 +122,7 @@ BENCH_SYMBOLS = {
     "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
 }
 
 _lib = None
@@ -192,8 +199,9 @@ FRAMES = Kind("cj_frame_batch_host", "cj_frame_batch_device", "cj_frame_batch_si
 DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_host", "cj_dict_batch_sizes_device", dictionary=True)
 DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_batch_sizes_host", "cj_deflate_batch_sizes_device")   # what = a DEFLATE_*
 DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_batch_device", None, None, one_op=True)      # what = a DEFLATE_*; no size query
+ZSTD = Kind("cj_zstd_batch_host", "cj_zstd_batch_device", "cj_zstd_batch_sizes_host", "cj_zstd_batch_sizes_device")   # what = ZSTD_FRAMES
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
-_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, BLOSC)}
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, BLOSC)}
 
 
 class Engine:

@@ -583,6 +583,35 @@ def deflate_sizes_device(inp, in_off, in_len, wrapper="raw", result=None, device
     return _device_sizes(N.DEFLATE, _deflate_wrap(wrapper), 0, inp, in_off, in_len, result, device, stream, sync)
 
 
+# ---- Zstandard frames (cj_zstd_batch_* / cj_zstd_batch_sizes_*): decode only --------------------------------------------
+# One entry is what one ZSTD_decompress call reads: one or more frames, skippable frames skipped, b"" decoding to b"".  result[i] = the
+# decoded length or a negative CJ_E_* code: -50 a bad frame header (legacy frames included), -51 corrupt data, -52 content checksum,
+# -53 truncated input or bytes behind the last frame, -54 the frame names a dictionary, -6 a capacity too small.
+def zstd_sizes(frames, devices=None):
+    """decoded sizes of many Zstandard chunks held on the host (list of ints; negative = CJ_E_* code): Frame_Content_Size where a frame
+    carries it, else the walk of its blocks without its literals — exact for a chunk that is valid; the content checksum and what
+    only a full decode finds are NOT verified here (include/cramjam_hip.h lists them)"""
+    return _host_sizes(N.ZSTD, N.ZSTD_FRAMES, 0, frames, devices)
+
+
+def zstd_decompress_many(frames, devices=None, out=None):
+    """decode many Zstandard chunks; returns (results, outputs) as lz4_decompress_blocks.  The sizes are asked for first (zstd_sizes;
+    the input then crosses the link twice): a chunk the query rejects gets the query's code as its result and an empty output."""
+    run = lambda caps: _run(N.ZSTD_FRAMES, N.OP_DECOMPRESS, 0, frames, caps, devices, out, N.ZSTD)
+    return _sizes_first(zstd_sizes(frames, devices), run)
+
+
+def zstd_decompress_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of Zstandard chunks (arguments as lz4_decompress_blocks_device); enqueue-only with device-resident
+    metadata, a result tensor and sync=False (a call that has to grow the engine's literal slots waits for their previous user)."""
+    return _device_batch(N.ZSTD, N.ZSTD_FRAMES, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def zstd_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
+    """Decoded sizes of a device-resident batch of Zstandard chunks, as zstd_sizes; enqueue-only like lz4_block_sizes_device."""
+    return _device_sizes(N.ZSTD, N.ZSTD_FRAMES, 0, inp, in_off, in_len, result, device, stream, sync)
+
+
 # ---- ... and into them (cj_deflate_compress_batch_* / cj_deflate_compress_bound; DESIGN.md 5.13) --------------------------------------
 # One stream per buffer: independent pieces of at most 64 KiB, each one stored, fixed or dynamic block.  result[i] = the stream's length
 # or a negative CJ_E_* code (-6: the capacity is too small; -1: a buffer above 0x7E000000 bytes).

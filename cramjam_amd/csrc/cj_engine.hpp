@@ -162,6 +162,8 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     cj::DevBuf d_dict;             // ... the dictionary of a host batch (under `mu`)
     cj::Scratch deflate_slots;     // deflate_encode.hip: the workgroups' sequence-record slots of a compress batch
     cj::DevBuf d_deflate_slots;
+    cj::Scratch zstd_slots;        // zstd.hip: the wavefronts' literal slots of a decode batch
+    cj::DevBuf d_zstd_slots;
 };
 
 namespace cj {

@@ -451,6 +451,11 @@ const char* cj_strerror(int64_t code) {
     case CJ_E_DEFLATE_CHECKSUM: return "deflate: checksum mismatch (zlib: incorrect data check / incorrect length check)";
     case CJ_E_DEFLATE_EOF: return "deflate: the input ends inside the stream (zlib: incomplete or truncated stream)";
     case CJ_E_DEFLATE_TRAILING: return "deflate: bytes behind the end of the stream (zlib: unused data); one chunk is exactly one stream";
+    case CJ_E_ZSTD_HEADER: return "zstd: invalid frame header (libzstd: prefix_unknown / frameParameter_unsupported / frameParameter_windowTooLarge; legacy frames are not supported)";
+    case CJ_E_ZSTD_CORRUPT: return "zstd: corrupt block (libzstd: corruption_detected)";
+    case CJ_E_ZSTD_CHECKSUM: return "zstd: content checksum mismatch (libzstd: checksum_wrong)";
+    case CJ_E_ZSTD_SRC_SIZE: return "zstd: the input is truncated or has bytes behind the last frame (libzstd: srcSize_wrong)";
+    case CJ_E_ZSTD_DICT: return "zstd: the frame names a dictionary (libzstd: dictionary_wrong); dictionaries are not supported";
     case CJ_E_NO_DEVICE: return "cramjam_hip: no usable HIP device (no CPU fallback exists)";
     case CJ_E_BAD_ARG: return "cramjam_hip: bad argument";
     case CJ_E_OOM: return "cramjam_hip: out of memory";

@@ -73,6 +73,12 @@ extern "C" {
 #define CJ_E_DEFLATE_CHECKSUM   (-42) /* zlib: "incorrect data check" (Adler-32, CRC-32) / "incorrect length check" (gzip ISIZE) */
 #define CJ_E_DEFLATE_EOF        (-43) /* zlib: "incomplete or truncated stream" (Z_BUF_ERROR): the input ends inside the stream or its trailer */
 #define CJ_E_DEFLATE_TRAILING   (-44) /* bytes behind the stream (zlib leaves them as unused data; one chunk is exactly one stream here) */
+#define CJ_E_ZSTD_HEADER        (-50) /* libzstd: prefix_unknown (bad magic, legacy frames included) / frameParameter_unsupported (reserved bit) /
+                                         frameParameter_windowTooLarge */
+#define CJ_E_ZSTD_CORRUPT       (-51) /* libzstd: corruption_detected (and dictionary_corrupted: Treeless literals before any Huffman table) */
+#define CJ_E_ZSTD_CHECKSUM      (-52) /* libzstd: checksum_wrong (the content checksum differs or is cut off) */
+#define CJ_E_ZSTD_SRC_SIZE      (-53) /* libzstd: srcSize_wrong (a truncated input, or bytes behind the last frame) */
+#define CJ_E_ZSTD_DICT          (-54) /* libzstd: dictionary_wrong (the frame names a dictionary; none is supported) */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -414,6 +420,48 @@ CJ_API int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, ui
                                           const uint8_t* const* in_ptrs, const size_t* in_lens,
                                           uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 CJ_API size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap);
+
+/* Zstandard frames — decode only (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
+ * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an
+ * empty input decoding to 0 bytes.  One wavefront decodes a chunk; result[i] and the bytes are libzstd's (1.4.x).
+ * Addressing, the 16-byte-granule rule, stream rules, e == NULL, n_chunks == 0 and the null-pointer rules are cj_deflate_batch_*'s.
+ *   fmt         a cj_zstd_format; anything else is CJ_E_BAD_ARG.       op   CJ_OP_DECOMPRESS, anything else is CJ_E_BAD_ARG.
+ *   flags       0.  Any bit set is CJ_E_BAD_ARG.  These three checks come first and need no device.
+ *   result[i]   the decoded length (>= 0) or CJ_E_*; one bad chunk never affects another; nothing is written at or behind
+ *               out_base + out_off[i] + out_cap[i]; bytes between result[i] and out_cap[i] stay untouched (literals are staged in
+ *               engine scratch, never in the caller's output).  in_len[i] > 0x7FFFFFF0 is CJ_E_CORRUPT, out_cap[i] > 0x7E000000 is
+ *               CJ_E_PREFIX_TOO_BIG, in that chunk's own result[i].
+ *   errors      libzstd's, in libzstd's order.  CJ_E_ZSTD_HEADER: a bad magic in the first frame (legacy v0.1 - v0.7 frames
+ *               included), the reserved header bit, a window above 2^31.  CJ_E_ZSTD_DICT: a non-zero Dictionary_ID.
+ *               CJ_E_ZSTD_SRC_SIZE: the input ends inside a frame, a bad magic behind a frame, 1 - 4 bytes left over, a compressed
+ *               block of 128 KiB or more.  CJ_E_ZSTD_CORRUPT: a reserved block type, every rule of the literals and sequences
+ *               sections (sizes, Huffman tree descriptions, streams that do not end as the one of libzstd's two Huffman decoders that libzstd picks wants, FSE descriptions, Repeat / Treeless
+ *               without a table, an offset beyond the frame's output, literals that run out, a bitstream that does not end exactly),
+ *               a Frame_Content_Size the blocks do not produce.  CJ_E_OUT_TOO_SMALL: a block, a sequence or the last literals do
+ *               not fit.  CJ_E_ZSTD_CHECKSUM: the low 32 bits of XXH64 over the frame's output.
+ *   sizes       the exact decoded length of a chunk that is valid; a total above 0x7E000000 is CJ_E_PREFIX_TOO_BIG.  A frame with a
+ *               Frame_Content_Size contributes that number and only its block HEADERS are walked; in a frame without one the
+ *               sequences sections are decoded and the literals skipped.  The query therefore does NOT report: CJ_E_ZSTD_CHECKSUM;
+ *               in a frame with a content size, any CJ_E_ZSTD_CORRUPT cause but a reserved block type and the CJ_E_ZSTD_SRC_SIZE of a
+ *               sequences header that its block cuts short; in a frame without one, what
+ *               only decoding the literals finds (Huffman tree descriptions and streams, Treeless without a table).  A chunk the
+ *               decoder refuses for one of these may get a size or a later error; every other verdict is the decoder's.
+ * The _device calls only enqueue (a decode that has to GROW the engine's literal slots — one of 128 KiB + 32 per stream in flight,
+ * within a fixed budget; a batch runs in slices of that many streams — waits for their previous user while it reallocates; the size
+ * query uses no scratch).  The _host calls are cj_batch_host's one-shot staging, synchronous. */
+typedef enum { CJ_ZSTD_FRAMES = 0 } cj_zstd_format;     /* room for magicless frames / raw blocks later */
+CJ_API int cj_zstd_batch_device(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t flags, size_t n_chunks,
+                                const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                int64_t* result, void* hip_stream);
+CJ_API int cj_zstd_batch_host(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t flags, size_t n_chunks,
+                              const uint8_t* const* in_ptrs, const size_t* in_lens,
+                              uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API int cj_zstd_batch_sizes_device(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n_chunks,
+                                      const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                      int64_t* result, void* hip_stream);
+CJ_API int cj_zstd_batch_sizes_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n_chunks,
+                                    const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
 
 /* =====================================================================================
  * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706
