@@ -17,7 +17,8 @@
 // repeat offsets.  The lanes build the Huffman table, move the bytes and take the Huffman streams: a block has one or four, so one or
 // four lanes decode literals into the wavefront's literal slot in global memory (128 KiB + 32) while the other lanes idle — the
 // format's limit for one block.  A stream's end follows the one of libzstd's two Huffman decoders that libzstd would take (zs_huf_select_x2).  Each sequence is a wave_copy of its literals and a wave_match_copy, as the LZ4 and DEFLATE wave
-// decoders do.  XXH64 runs over the finished frame: the four accumulators on four lanes.
+// decoders do; the END of a block's sequence stream follows the one of libzstd's two sequence decoders that libzstd would take (a
+// frame with a window above 16 MiB may get the one that decodes ahead: the sequences section below).  XXH64 runs over the finished frame: the four accumulators on four lanes.
 //
 // The size query (SIZE) is the same walk without stores, literal decoding and checksum.  It does NOT report:
 //   - CJ_E_ZSTD_CHECKSUM (no output exists to sum)
@@ -311,6 +312,10 @@ __device__ __forceinline__ uint32_t zs_huf_read(ZsIn& in, ZstdLds* L, uint32_t a
         uint32_t wlog, nsym;
         const uint32_t h = zs_read_ncount(in, L, at + 1u, isize, 255u, wlog, nsym);
         if (h == 0u || wlog > 6u) return 0u;
+        // libzstd (1.4.7 and later) decodes the weights in a workspace sized for 12 symbols at log 6 (HUF_READ_STATS_WORKSPACE_SIZE_U32 =
+        // FSE_DECOMPRESS_WKSP_SIZE_U32(6, 11) = 89 words) and refuses a description whose table (1 + cells) and build space (two bytes a
+        // symbol described, a byte a cell, 8) need more: above 12 symbols at log 6, above 92 at log 5
+        if (1u + (1u << wlog) + ((2u * nsym + (1u << wlog) + 8u + 3u) >> 2) > 89u) return 0u;
         uint32_t* wtab = reinterpret_cast<uint32_t*>(L->huf);
         zs_fse_build(L, wtab, wlog, nsym);
         ZsBitD b;
@@ -558,8 +563,11 @@ __device__ __forceinline__ int64_t zstd_wave_decode(const uint8_t* in_ptr, uint3
         if (magic != 0xFD2FB528u) return more_than_one ? CJ_E_ZSTD_SRC_SIZE : CJ_E_ZSTD_HEADER;
         if (fhd & 8u) return CJ_E_ZSTD_HEADER;
         uint32_t q = ip + 5u;
+        uint64_t window = 0;
         if (!single) {
-            if ((in.f8(q) >> 3) + 10u > 31u) return CJ_E_ZSTD_HEADER;
+            const uint32_t wd = in.f8(q), wlog = (wd >> 3) + 10u;
+            if (wlog > 31u) return CJ_E_ZSTD_HEADER;
+            window = (1ull << wlog) + ((1ull << wlog) >> 3) * (wd & 7u);
             q += 1u;
         }
         const uint32_t did = did_len ? in.fle(q, did_len) : 0u;
@@ -572,6 +580,8 @@ __device__ __forceinline__ int64_t zstd_wave_decode(const uint8_t* in_ptr, uint3
             if (fcs_len == 2u) fcs += 256u;
         }
         if (did != 0u) return CJ_E_ZSTD_DICT;
+        if (single) window = fcs;
+        const bool long_window = window > (1ull << 24);                      // libzstd considers its other sequence decoder (below)
         const bool has_sum = (fhd & 4u) != 0u;
         ip += fhs;
 
@@ -734,8 +744,44 @@ __device__ __forceinline__ int64_t zstd_wave_decode(const uint8_t* in_ptr, uint3
                 uint32_t st_ll = b.read(ll_log); b.reload(in);
                 uint32_t st_of = b.read(of_log); b.reload(in);
                 uint32_t st_ml = b.read(ml_log); b.reload(in);
+                // libzstd has a second sequence decoder, which decodes four sequences ahead of the one it executes
+                // (ZSTD_decompressSequencesLong), and takes it in a frame whose window is above 16 MiB for a block of more than 4
+                // sequences whose offset table has 7 of 256 cells or more with over 22 extra bits.  It reads the same sequences but
+                // ends differently: it looks for an over-read BEFORE it decodes a sequence, and refuses then, four sequences short
+                // of that one executed; and it does not ask whether bits are left at the end.
+                uint32_t todo = nseq;
+                bool prefetch = false, cut = false;
+                if (long_window && nseq > 4u) {
+                    uint32_t share = 0;
+                    for (uint32_t u = 0; u < (1u << of_log); u++) share += (lds_ld(&L->fse[kZsOF + u]) & 255u) > 22u ? 1u : 0u;
+                    prefetch = (share << (8u - of_log)) >= 7u;
+                }
+                if (prefetch) {                                              // how far that decoder gets: the same walk without the sequences' values
+                    ZsBitD pb = b;
+                    uint32_t p_ll = st_ll, p_of = st_of, p_ml = st_ml, k = 0;
+                    for (; k < nseq; k++) {
+                        if (pb.reload(in) == kZsOverflow) break;
+                        const uint32_t e_ll = lds_ld(&L->fse[kZsLL + (p_ll & 511u)]), e_ml = lds_ld(&L->fse[kZsML + (p_ml & 511u)]);
+                        const uint32_t e_of = lds_ld(&L->fse[kZsOF + (p_of & 255u)]);
+                        uint32_t base, ll_bits, ml_bits;
+                        zs_ll_code(e_ll & 255u, base, ll_bits);
+                        zs_ml_code(e_ml & 255u, base, ml_bits);
+                        const uint32_t of_bits = e_of & 255u & 31u;
+                        pb.bc += of_bits + ml_bits;
+                        if (ll_bits + ml_bits + of_bits >= 31u) pb.reload(in);
+                        pb.bc += ll_bits;
+                        p_ll = (e_ll >> 16) + pb.read((e_ll >> 8) & 255u);
+                        p_ml = (e_ml >> 16) + pb.read((e_ml >> 8) & 255u);
+                        p_of = (e_of >> 16) + pb.read((e_of >> 8) & 255u);
+                    }
+                    if (k < nseq) {
+                        if (k <= 4u) return CJ_E_ZSTD_CORRUPT;               // found before anything was executed
+                        cut = true;                                          // ... behind sequences 0 .. k - 5: their errors come first
+                        todo = k - 4u;
+                    }
+                }
                 uint32_t r1 = rep1, r2 = rep2, r3 = rep3;
-                for (;;) {                                                   // nseq turns
+                for (;;) {                                                   // todo turns
                     const uint32_t e_ll = lds_ld(&L->fse[kZsLL + (st_ll & 511u)]), e_ml = lds_ld(&L->fse[kZsML + (st_ml & 511u)]);
                     const uint32_t e_of = lds_ld(&L->fse[kZsOF + (st_of & 255u)]);
                     uint32_t ll, ll_bits, ml, ml_bits;
@@ -772,10 +818,10 @@ __device__ __forceinline__ int64_t zstd_wave_decode(const uint8_t* in_ptr, uint3
                     if (offset > op - fstart) return CJ_E_ZSTD_CORRUPT;
                     if (!SIZE) { wave_match_copy(out + op, offset, ml); wave_order(); }
                     op += ml;
-                    if (--nseq == 0u) break;
+                    if (--todo == 0u) break;
                     b.reload(in);
                 }
-                if (b.reload(in) < kZsCompleted) return CJ_E_ZSTD_CORRUPT;
+                if (cut || (!prefetch && b.reload(in) < kZsCompleted)) return CJ_E_ZSTD_CORRUPT;
                 rep1 = r1; rep2 = r2; rep3 = r3;
             }
             const uint32_t rest = lit_size - lit_pos;

@@ -63,7 +63,7 @@ def _shuffled():
     return [cs[k] for k in np.random.default_rng(7).permutation(len(cs))]
 
 
-def _check(part, which, res, out, ooff, caps):
+def _check(part, which, res, out, ooff, caps, sha=Z.sha):
     for i, c in enumerate(part):
         want = c.verdicts[which]
         assert res[i] == want, (c.name, caps[i], int(res[i]), want)
@@ -72,7 +72,7 @@ def _check(part, which, res, out, ooff, caps):
         if want >= 0:
             assert (out[lo + want:lo + cap] == 0xA5).all(), c.name        # bytes between the result and the capacity stay untouched
             if which == 0:
-                assert Z.sha(out[lo:lo + want]) == c.sha, c.name
+                assert sha(out[lo:lo + want]) == c.sha, c.name
 
 
 @pytest.mark.parametrize("which", [0, 1, 2, 3])

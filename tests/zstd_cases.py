@@ -1,5 +1,7 @@
 """Zstandard decode cases: the recorded fixtures (tests/golden/golden_zstd.*), the hand-written streams, a classifier of frames by
-their block and section headers, libzstd through ctypes (the reference of every verdict; CPU tests only) and a scalar XXH64."""
+their block and section headers and a deeper one that reads table and tree descriptions and the sequences' codes (deep_classify: the
+reader that checks what tests/zstd_synth.py claims to write), libzstd through ctypes (the reference of every verdict; CPU tests only)
+and a scalar XXH64."""
 import ctypes as C
 import ctypes.util
 import hashlib
@@ -272,6 +274,300 @@ def classify(stream):
     if frames > 1:
         tags.add("chunk:multiframe")
     return tags
+
+
+# ---- a second reader, not the writer of zstd_synth.py: the grammar corners a chunk shows ------------------------------------------------
+# every corner a synthesized set has to show (test_zstd_synth_model.py asserts it)
+DEEP_COVERAGE = (["%s:log%d" % (c, k) for c, top in (("ll", 9), ("of", 8), ("ml", 9), ("w", 6)) for k in range(5, top + 1)]
+                 + ["nc:less_than_one", "nc:run0", "nc:run1", "nc:run2", "nc:run3chain", "nc:run12", "nc:short", "nc:long_low", "nc:long_high",
+                    "nc:under8", "nc:tail", "nc:block_end"]
+                 + ["huf:log%d" % k for k in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12)] + ["huf:last%d" % k for k in range(1, 13)] + ["huf:2symbols", "huf:256symbols", "huf:sym255", "huf:128direct"]
+                 + ["weights:direct", "weights:fse", "lit:huf1", "lit:huf4", "lit:treeless"]
+                 + ["lh:huf%d" % k for k in range(4)] + ["lh:treeless%d" % k for k in range(4)] + ["lh:raw%d" % k for k in range(4)] + ["lh:rle%d" % k for k in range(4)]
+                 + ["off:new", "off:rep1", "off:rep2", "off:rep3", "off:ll0_rep2", "off:ll0_rep3", "off:ll0_rep1m1", "off:forced1", "seq:reload31",
+                    "seq:bits30", "seq:bits31", "seq:bits32", "seq:prefetch", "seq:leftover_bits"]
+                 + ["%s:%s>%s" % (c, a, b) for c in ("ll", "of", "ml") for a in ("predefined", "rle", "fse", "repeat") for b in ("predefined", "rle", "fse", "repeat")]
+                 + ["fcs:1", "fcs:2", "fcs:4", "fcs:8", "frame:single", "frame:window", "wd:0x00", "wd:0xa8", "chunk:skippable0", "chunk:8frames",
+                    "block:empty_raw", "block:empty_rle"])
+
+
+class _Fwd:
+    """a forward bit reader, least significant bit first"""
+    def __init__(self, data):
+        self.v, self.n, self.at = int.from_bytes(data, "little"), 8 * len(data), 0
+
+    def peek(self, nb):
+        return (self.v >> self.at) & ((1 << nb) - 1)
+
+    def read(self, nb):
+        v = self.peek(nb)
+        self.at += nb
+        return v
+
+
+class _Bwd:
+    """a backward bit reader: bits behind the stream's start read as 0, `left` goes negative"""
+    def __init__(self, data):
+        assert data and data[-1]
+        self.v = int.from_bytes(data, "little")
+        self.left = self.v.bit_length() - 1
+
+    def read(self, nb):
+        self.left -= nb
+        return ((self.v >> self.left) if self.left >= 0 else (self.v << -self.left)) & ((1 << nb) - 1)
+
+
+def read_ncount(data, max_sv, tags):
+    """RFC 8878 4.1.1 over data (everything the description may use): (log, counts, bytes used); tags gets the forms met"""
+    b = _Fwd(data)
+    log = b.read(4) + 5
+    remaining, counts = (1 << log) + 1, []
+    if len(data) < 8:
+        tags.add("nc:under8")
+    while remaining > 1 and len(counts) <= max_sv:
+        if len(data) >= 8 and b.at // 8 > len(data) - 4:
+            tags.add("nc:tail")
+        nb = remaining.bit_length()                          # bits of the largest value, `remaining`
+        low = (1 << nb) - 1 - remaining                      # values below it take one bit less
+        v = b.peek(nb - 1)
+        if v < low:
+            b.read(nb - 1)
+            tags.add("nc:short")
+        else:
+            v = b.read(nb)
+            tags.add("nc:long_high" if v >= (1 << (nb - 1)) else "nc:long_low")
+            if v >= (1 << (nb - 1)):
+                v -= low
+        c = v - 1
+        counts.append(c)
+        remaining -= abs(c)
+        if c == -1:
+            tags.add("nc:less_than_one")
+        if c == 0:
+            run = 0
+            while True:
+                r = b.read(2)
+                counts += [0] * r
+                if r < 3:
+                    tags.add("nc:run%d" % r if run == 0 else "nc:run3chain")
+                    break
+                run += 1
+            if run >= 12:
+                tags.add("nc:run12")
+    assert remaining == 1 and len(counts) <= max_sv + 1 and (b.at + 7) // 8 <= len(data)
+    return log, counts, (b.at + 7) // 8
+
+
+def fse_cells(log, counts):
+    """RFC 8878 4.1.1: per cell (symbol, bits, base)"""
+    size = 1 << log
+    cell, top = [None] * size, size
+    for s, c in enumerate(counts):
+        if c == -1:
+            top -= 1
+            cell[top] = s
+    at = 0
+    for s, c in enumerate(counts):
+        for _ in range(max(c, 0)):
+            cell[at] = s
+            at = (at + (size >> 1) + (size >> 3) + 3) % size
+            while at >= top:
+                at = (at + (size >> 1) + (size >> 3) + 3) % size
+    seen, out = [abs(c) for c in counts], []
+    for s in cell:
+        x = seen[s]
+        seen[s] += 1
+        nb = log - (x.bit_length() - 1)
+        out.append((s, nb, (x << nb) - size))
+    return out
+
+
+_LLB = [0] * 16 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+_MLB = [0] * 32 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+_LLV = list(range(16)) + [16, 18, 20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536]
+_DEFAULTS = {"ll": (6, [4, 3] + [2] * 11 + [1, 1, 1] + [2] * 9 + [3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1]),
+             "of": (5, [1] * 6 + [2, 2, 2] + [1] * 15 + [-1] * 5),
+             "ml": (6, [1, 4, 3] + [2] * 6 + [1] * 37 + [-1] * 7)}
+
+
+def deep_classify(stream):
+    """classify() and the corners of DEEP_COVERAGE, by decoding table descriptions, tree descriptions and the sequences' codes; a
+    chunk that breaks the grammar yields what was met before the break"""
+    tags = set()
+    try:
+        _deep(bytes(stream), tags)
+    except (AssertionError, IndexError, struct.error, ValueError, StopIteration):
+        pass
+    return tags
+
+
+def _deep(s, tags):
+    ip, frames, skip0 = 0, 0, False
+    while len(s) - ip >= 8:
+        if struct.unpack_from("<I", s, ip)[0] & 0xFFFFFFF0 == 0x184D2A50:
+            size = struct.unpack_from("<I", s, ip + 4)[0]
+            tags.add("chunk:skippable")
+            if size == 0:
+                tags.add("chunk:skippable0")
+            ip += 8 + size
+            continue
+        assert s[ip:ip + 4] == b"\x28\xb5\x2f\xfd"
+        frames += 1
+        if frames == 8:
+            tags.add("chunk:8frames")
+        fhd = s[ip + 4]
+        single, code = (fhd >> 5) & 1, fhd >> 6
+        assert not fhd & 8 and not fhd & 3
+        fcs_len = (1 << code) if code else single
+        tags.add("frame:single" if single else "frame:window")
+        window = 0
+        if not single:
+            tags.add("wd:0x%02x" % s[ip + 5])
+            window = (8 + (s[ip + 5] & 7)) << (7 + (s[ip + 5] >> 3))
+        if fcs_len:
+            tags.add("fcs:%d" % fcs_len)
+        ip += 5 + (0 if single else 1) + fcs_len
+        tabs, prev, reps, produced = {}, {}, [1, 4, 8], 0
+        while True:
+            bh = int.from_bytes(s[ip:ip + 3], "little")
+            last, kind, size = bh & 1, (bh >> 1) & 3, bh >> 3
+            ip += 3
+            assert kind < 3
+            if last and size == 0:
+                tags.add("block:empty_" + ("raw", "rle", "compressed")[kind])
+            if kind < 2:
+                produced += size
+                ip += size if kind == 0 else 1
+            else:
+                end = ip + size
+                assert end <= len(s)
+                b0 = s[ip]
+                lk, lhl = b0 & 3, (b0 >> 2) & 3
+                if lk < 2:
+                    lh = (1, 2, 1, 3)[lhl]
+                    nlit = int.from_bytes(s[ip:ip + lh], "little") >> (3 if lh == 1 else 4)
+                    tags.add("lh:%s%d" % (("raw", "rle")[lk], lhl))
+                    q = ip + lh + (nlit if lk == 0 else 1)
+                else:
+                    lh, nb = (3, 3, 4, 5)[lhl], (10, 10, 14, 18)[lhl]
+                    v = int.from_bytes(s[ip:ip + lh], "little")
+                    nlit, lcs = (v >> 4) & ((1 << nb) - 1), (v >> (4 + nb)) & ((1 << nb) - 1)
+                    tags.add("lh:%s%d" % (("huf", "treeless")[lk - 2], lhl))
+                    q = ip + lh + lcs
+                    assert q <= end
+                    if lk == 2:
+                        _deep_tree(s[ip + lh:q], tags)
+                    tags.add("lit:treeless" if lk == 3 else "lit:huf1" if lhl == 0 else "lit:huf4")
+                nseq = s[q]
+                q += 1
+                if nseq >= 128:
+                    nseq = (s[q] | (s[q + 1] << 8)) + 0x7F00 if nseq == 255 else ((nseq - 128) << 8) + s[q]
+                    q += 2 if s[q - 1] == 255 else 1
+                if nseq:
+                    modes = s[q]
+                    q += 1
+                    for name, sh, max_sv in (("ll", 6, 35), ("of", 4, 31), ("ml", 2, 52)):
+                        m = (modes >> sh) & 3
+                        mname = ("predefined", "rle", "fse", "repeat")[m]
+                        if name in prev:
+                            tags.add("%s:%s>%s" % (name, prev[name], mname))
+                        prev[name] = mname
+                        if m == 0:
+                            tabs[name] = (_DEFAULTS[name][0], fse_cells(*_DEFAULTS[name]))
+                        elif m == 1:
+                            tabs[name] = (0, [(s[q], 0, 0)])
+                            q += 1
+                        elif m == 2:
+                            sub = set()
+                            log, counts, used = read_ncount(s[q:end], max_sv, sub)
+                            if q + used == end:
+                                sub.add("nc:block_end")
+                            tags |= sub
+                            tags.add("%s:log%d" % (name, log))
+                            tabs[name] = (log, fse_cells(log, counts))
+                            q += used
+                        else:
+                            assert name in tabs
+                    b = _Bwd(s[q:end])
+                    st = {k: b.read(tabs[k][0]) for k in ("ll", "of", "ml")}
+                    for i in range(nseq):
+                        cl, co, cm = (tabs[k][1][st[k]] for k in ("ll", "of", "ml"))
+                        extra = b.read(co[0])
+                        b.read(_MLB[cm[0]])
+                        ll = _LLV[cl[0]] + b.read(_LLB[cl[0]])
+                        total = co[0] + _MLB[cm[0]] + _LLB[cl[0]]
+                        if total >= 31:
+                            tags.add("seq:reload31")
+                        if 30 <= total <= 32:
+                            tags.add("seq:bits%d" % total)
+                        if co[0] > 1:
+                            tags.add("off:new")
+                            reps = [(1 << co[0]) + extra - 3, reps[0], reps[1]]
+                        else:
+                            k = co[0] + extra + (ll == 0)               # 0: the first repeat offset ... 3: that minus one
+                            tags.add(("off:rep1", "off:ll0_rep2" if ll == 0 else "off:rep2", "off:ll0_rep3" if ll == 0 else "off:rep3", "off:ll0_rep1m1")[k])
+                            if k:
+                                t = reps[k] if k < 3 else reps[0] - 1
+                                if t == 0:
+                                    tags.add("off:forced1")
+                                    t = 1
+                                reps = [t, reps[0], reps[1]] if k > 1 else [t, reps[0], reps[2]]
+                        if i + 1 < nseq:
+                            for k, c in (("ll", cl), ("ml", cm), ("of", co)):
+                                st[k] = c[2] + b.read(c[1])
+                    # libzstd's prefetching decoder (a window above 16 MiB, over 4 sequences, offset cells above 22 bits) takes leftovers
+                    far = sum(1 for c in tabs["of"][1] if c[0] > 22) << (8 - tabs["of"][0])
+                    if window > (1 << 24) and nseq > 4 and far >= 7:
+                        tags.add("seq:prefetch")
+                        if b.left > 0:
+                            tags.add("seq:leftover_bits")
+                    else:
+                        assert b.left == 0
+                ip = end
+            if last:
+                break
+        ip += 4 if fhd & 4 else 0
+
+
+def _deep_tree(d, tags):
+    """a Huffman tree description at the head of d"""
+    if d[0] >= 128:
+        n = d[0] - 127
+        w = [(d[1 + k // 2] >> (0 if k & 1 else 4)) & 15 for k in range(n)]
+        tags.add("weights:direct")
+        if n == 128:
+            tags.add("huf:128direct")
+    else:
+        sub = set()
+        log, counts, used = read_ncount(d[1:1 + d[0]], 255, sub)
+        cells = fse_cells(log, counts)
+        b = _Bwd(d[1 + used:1 + d[0]])
+        st, w, k = [b.read(log), b.read(log)], [], 0
+        while len(w) < 256:
+            c = cells[st[k]]
+            w.append(c[0])
+            st[k] = c[2] + b.read(c[1])
+            if b.left < 0:
+                w.append(cells[st[k ^ 1]][0])
+                break
+            k ^= 1
+        tags |= sub
+        tags.add("weights:fse")
+        tags.add("w:log%d" % log)
+        tags.add("w:%dsymbols" % len(counts))
+    total = sum(1 << (x - 1) for x in w if x)
+    hlog = total.bit_length()
+    rest = (1 << hlog) - total
+    assert rest & (rest - 1) == 0 and rest and max(w) < 12
+    tags.add("huf:log%d" % hlog)
+    tags.add("huf:last%d" % rest.bit_length())                # the implied last weight
+    nsym = sum(1 for x in w if x) + 1
+    if nsym == 2:
+        tags.add("huf:2symbols")
+    if nsym == 256:
+        tags.add("huf:256symbols")
+    if len(w) == 255:
+        tags.add("huf:sym255")
 
 
 def huffman_literals_before_failure(stream):
