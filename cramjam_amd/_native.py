@@ -123,6 +123,7 @@ BENCH_SYMBOLS = {
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_grid_chunks": (C.c_uint64, [C.c_uint64]),
 }
 
 _lib = None

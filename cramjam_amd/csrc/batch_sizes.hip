@@ -139,11 +139,8 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_size_wave_kernel(uint32_t n
     const uint64_t n64 = in_len[c];
     if (n64 <= kSizeLaneMaxIn || n64 > kLz4InMax) return;          // the lane kernel answers those
     const uint8_t* in = in_base + in_off[c];
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
     InWindow w;
-    w.base = in - mis;
-    w.iend = mis + (uint32_t)n64;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, (uint32_t)n64);
     const int64_t r = lz4_size_walk([&](uint32_t p) { p = uni(p); w.ensure(p); return w.fetch32(p); },
                                     [&](uint32_t p, uint32_t e) { return uni(lz4_ff_run(w.base, uni(p), e)); }, mis, w.iend);
     if (lane_id() == 0) result[c] = r;
@@ -196,7 +193,7 @@ int sizes_launch(Query q, int what, uint32_t flags, size_t n, const uint8_t* in_
     } else {
         const uint32_t per_block = 64u * cj::kParseWaves;
         hipLaunchKernelGGL(cj::lz4_size_lanes_kernel, dim3((n32 + per_block - 1u) / per_block), dim3(per_block), 0, s, n32, in_base, in_off, in_len, result);
-        hipLaunchKernelGGL(cj::lz4_size_wave_kernel, dim3((n32 + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), block, 0, s, n32, in_base, in_off, in_len, result);
+        hipLaunchKernelGGL(cj::lz4_size_wave_kernel, cj::wave_grid(n32), block, 0, s, n32, in_base, in_off, in_len, result);
     }
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;

@@ -31,8 +31,7 @@ __global__ __launch_bounds__(kBlockThreads) void blosclz_decode_kernel(BatchArgs
 
 void launch_blosclz_decode(const BatchArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return;
-    dim3 grid((a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlockThreads);
-    hipLaunchKernelGGL(blosclz_decode_kernel, grid, block, 0, s, a);
+    hipLaunchKernelGGL(blosclz_decode_kernel, wave_grid(a.n_chunks), dim3(kBlockThreads), 0, s, a);
 }
 
 }  // namespace cj

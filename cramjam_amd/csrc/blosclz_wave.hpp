@@ -1,8 +1,9 @@
 // blosclz_wave.hpp — the BloscLZ stream decoder of one wavefront (blosclz_decode.hip says what the format is).  It names only
-// InWindow, wave_copy, wave_match_copy and wave_order, which whoever includes it has declared in namespace cj: cj_common.hpp for the
-// device, tests/hostsim/sim_blosclz_decode.cpp for the host, where byte-exact stand-ins with bounds checks let the CPU tests hold
-// the grammar and every copy's bounds to tests/blosclz_model.py.  Not part of the C-ABI.
+// InWindow, wave_copy, wave_match_copy and wave_order of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
+// tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_blosclz_decode.cpp), where
+// the CPU tests hold the grammar and every copy's bounds to tests/blosclz_model.py.  Not part of the C-ABI.
 #pragma once
+#include "wave_window.hpp"
 
 namespace cj {
 
@@ -11,10 +12,7 @@ __device__ __forceinline__ int64_t blosclz_wave_decode(const uint8_t* in, uint32
     if (n == 0) return CJ_E_CORRUPT;
 
     InWindow w;
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-    w.base = in - mis;
-    w.iend = mis + n;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, n);
     const uint32_t iend = w.iend;
     uint32_t ip = mis;      // input position relative to w.base: at the top of the loop it names a control byte, ip < iend
     uint32_t op = 0;        // output position

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cramjam_hip_debug.h"      // (the drop-in ABI + the test / benchmark exports)
+#if defined(__HIPCC__)
+#include "wave_window.hpp"                        // window_open(w, in, n): the one way to open an InWindow
+#endif
 
 namespace cj {
 

@@ -189,4 +189,20 @@ inline BatchRows batch_rows(uint64_t* base, size_t n) {
 inline void fill_args(BatchArgs& a, uint32_t flags, const uint8_t* in_base, uint8_t* out_base, const BatchRows& r) {
     fill_args(a, flags, r.n, in_base, r.in_off, r.in_len, out_base, r.out_off, r.out_cap, r.result);
 }
+
+// ---- launches of the kernels that give every wavefront (or lane) one chunk ---------------------------------------------------------
+size_t grid_chunks();            // kGridChunks, unless cj_debug_grid_chunks has lowered it (engine.hip)
+inline dim3 wave_grid(size_t n_chunks) { return dim3((unsigned)((n_chunks + kWavesPerBlock - 1) / kWavesPerBlock)); }
+// A batch of n chunks in slices of at most `per`: launch(a) with the BatchArgs of each slice in turn — its rows begin at the slice's
+// first chunk (out_off / out_cap may be null: a size query), the base pointers are the batch's
+template <class F>
+void for_slices(size_t n, size_t per, uint32_t flags, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, F&& launch) {
+    for (size_t first = 0; first < n; first += per) {
+        BatchArgs a;
+        fill_args(a, flags, std::min(per, n - first), in_base, in_off + first, in_len + first, out_base, out_off ? out_off + first : nullptr,
+                  out_cap ? out_cap + first : nullptr, result + first);
+        launch(a);
+    }
+}
 }  // namespace cj

@@ -133,6 +133,8 @@ inline bool chunk_ptrs_ok(size_t n, const uint8_t* const* ptrs, const size_t* le
         if (lens[i] && !ptrs[i]) return false;
     return true;
 }
+// a cj_deflate_wrap that exists (the DEFLATE entries' own check, decode and compress)
+inline bool deflate_wrap_ok(int wrap) { return wrap == CJ_DEFLATE_RAW || wrap == CJ_DEFLATE_ZLIB || wrap == CJ_DEFLATE_GZIP; }
 // A device call: the gate, the engine (nullptr: the default one) and its device; launch(e, s) enqueues on the caller's stream or the engine's
 template <class F>
 int device_call(cj_engine* e, size_t n, std::initializer_list<const void*> rows, void* hip_stream, F&& launch) {

@@ -1,22 +1,10 @@
 // deflate.hip — batches of DEFLATE streams, decode only (cj_deflate_batch_device / _host, cj_deflate_batch_sizes_device / _host;
 // DESIGN.md §5.12): raw DEFLATE, zlib streams and gzip members, one stream per chunk, one wavefront per stream, workgroups of four
 // wavefronts.  The decoder is deflate_wave.hpp (the same text tests/hostsim compiles for the host); this file gives it the wavefront:
-// the LDS accessors and the lanes (deflate_lanes.hpp, shared with the encoder), each wavefront's private tables in static LDS (9.6 KiB each; the gzip decode adds the workgroup's 4 KiB
-// of CRC-32 tables), and the launches.  The size query is the same decoder with stores and checksums compiled out.
+// the accessors (wave_lanes.hpp), each wavefront's private tables in static LDS (9.6 KiB each; the gzip decode adds the workgroup's
+// 4 KiB of CRC-32 tables), and the launches.  The size query is the same decoder with stores and checksums compiled out.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock.
-#include "deflate_lanes.hpp"
-
-namespace cj {
-
-// the round's literals: lane k keeps literal k in a register, one store puts the run out
-struct LaneBytes {
-    uint32_t v;
-    __device__ __forceinline__ void put(uint32_t k, uint32_t byte) { if (lane_id() == k) v = byte; }
-    __device__ __forceinline__ void flush(uint8_t* dst, uint32_t n) { if (lane_id() < n) dst[lane_id()] = (uint8_t)v; }
-};
-
-}  // namespace cj
-
+#include "wave_lanes.hpp"
 #include "deflate_wave.hpp"
 
 namespace cj {
@@ -51,16 +39,13 @@ namespace {
 
 template <int WRAP, bool SIZE>
 void launch_one(const cj::BatchArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((cj::deflate_kernel<WRAP, SIZE>), dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a);
+    hipLaunchKernelGGL((cj::deflate_kernel<WRAP, SIZE>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a);
 }
 
 // enqueue only; size: the size query (the output rows are null)
 int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                    const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    for (size_t first = 0; first < n; first += cj::kGridChunks) {
-        cj::BatchArgs a;
-        cj::fill_args(a, 0u, std::min(cj::kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, size ? nullptr : out_off + first,
-                      size ? nullptr : out_cap + first, result + first);
+    cj::for_slices(n, cj::grid_chunks(), 0u, in_base, in_off, in_len, out_base, size ? nullptr : out_off, size ? nullptr : out_cap, result, [&](const cj::BatchArgs& a) {
         switch (wrap * 2 + (size ? 1 : 0)) {
         case 0: launch_one<CJ_DEFLATE_RAW, false>(a, s); break;
         case 1: launch_one<CJ_DEFLATE_RAW, true>(a, s); break;
@@ -69,7 +54,7 @@ int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const 
         case 4: launch_one<CJ_DEFLATE_GZIP, false>(a, s); break;
         default: launch_one<CJ_DEFLATE_GZIP, true>(a, s); break;
         }
-    }
+    });
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }

@@ -1,17 +1,12 @@
 // deflate_enc_wave.hpp — the entropy stage of the DEFLATE encoder, one wavefront per stream: the sequence records
 // that the matcher left in the workgroup's scratch slot become one block per piece — stored, fixed or dynamic by their exact costs —
 // behind a bit position that is carried from block to block.  tests/hostsim/deflate_enc_model.c states the same thing as scalar C;
-// this text emits exactly its bytes.  Written like deflate_wave.hpp: it names only what whoever includes it has declared in namespace cj —
-//     CJ_LANES(lane)            the body that follows runs once per lane.  A body never reads what another lane writes in the SAME body;
-//                               wave_order() separates bodies
-//     LaneU32, LaneU64          a value per lane: v[lane] inside a CJ_LANES body
-//     lane_excl_add(v, before)  before[lane] = the sum of v below that lane; returns the sum of all 64 (wave-uniform)
-//     lds_ld(p), lds_ld8(p)     a wave-uniform 32-bit / 8-bit read of the wavefront's LDS
-//     lds_add(p, v), lds_or(p, v)    lane-wise read-modify-write of an LDS word
-//     in_ld8(p)                 one byte of the piece;  rec_ld(slot, i): record i of the scratch slot
-//     out_st32(p, v), out_st8(p, v)  an (unaligned) dword / a byte of the output;  wave_copy, wave_order: as everywhere
-// — cj_common.hpp + deflate_encode.hip for the device, tests/hostsim/sim_deflate_encode.cpp for the host, where bounds-checked stand-ins
-// hold every access.  Not part of the C-ABI.
+// this text emits exactly its bytes.  Written like deflate_wave.hpp: it names only
+//     wave_copy, wave_order, CJ_LANES, LaneU32, LaneU64, lane_excl_add, lds_ld, lds_ld8, lds_add, lds_or, in_ld8, out_st8, out_st32
+// of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
+// tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_deflate_encode.cpp), and
+//     rec_ld(slot, i)           record i of the scratch slot, which whoever includes this declares (it needs the complete DfeRec)
+// Not part of the C-ABI.
 //
 // Mapping.  The bit position, the block's costs and its choice are wave-uniform.  The lanes take CONSECUTIVE SYMBOLS: 64 records are
 // loaded, a prefix sum over their symbol counts (literals + split matches) gives every symbol its record, and a round is 64 symbols —

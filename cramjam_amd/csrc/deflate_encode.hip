@@ -9,7 +9,7 @@
 // The bytes are those of tests/hostsim/deflate_enc_model.c.  The slots are engine scratch within a fixed budget: a batch goes through
 // in slices of as many streams as there are slots (cj::ScratchTurn).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
-#include "deflate_lanes.hpp"
+#include "wave_lanes.hpp"
 #include "cj_enc2.hpp"
 #include "crc32_lanes.hpp"
 
@@ -17,17 +17,6 @@
 
 namespace cj {
 
-// a value per lane: the lane's own register
-struct LaneU32 { uint32_t v; __device__ __forceinline__ uint32_t& operator[](uint32_t) { return v; } };
-struct LaneU64 { uint64_t v; __device__ __forceinline__ uint64_t& operator[](uint32_t) { return v; } };
-__device__ __forceinline__ uint32_t lane_excl_add(LaneU32& x, LaneU32& before) {
-    uint32_t total;
-    before.v = wave_excl_add(x.v, total);
-    return total;
-}
-__device__ __forceinline__ uint32_t in_ld8(const uint8_t* p) { return *p; }
-__device__ __forceinline__ void out_st8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
-__device__ __forceinline__ void out_st32(uint8_t* p, uint32_t v) { *reinterpret_cast<enc2::u32_unaligned*>(p) = v; }
 struct DfeRec;
 __device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i);
 
@@ -183,14 +172,12 @@ int compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, co
     cj::ScratchTurn turn(e->deflate_slots, s);
     if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_deflate_slots, per * (size_t)cj::kDfeSlotBytes)) != 0) return turn.rc;
     uint8_t* slots = (uint8_t*)e->d_deflate_slots.p;
-    for (size_t first = 0; first < n; first += per) {
-        cj::BatchArgs a;
-        cj::fill_args(a, 0u, std::min(per, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
+    cj::for_slices(n, per, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
         const dim3 grid(a.n_chunks), block(cj::kDfeThreads);
         if (wrap == CJ_DEFLATE_RAW) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeRaw>), grid, block, 0, s, a, slots);
         else if (wrap == CJ_DEFLATE_ZLIB) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeZlib>), grid, block, 0, s, a, slots);
         else hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeGzip>), grid, block, 0, s, a, slots);
-    }
+    });
     return turn.done(s);
 }
 

@@ -1,15 +1,9 @@
 // deflate_wave.hpp — the DEFLATE decoder of one wavefront (RFC 1951 behind no wrapper, RFC 1950 zlib or RFC 1952 gzip): one stream per
-// wavefront, accept / reject rules of zlib's inflate.  Written like lz4_dict_wave.hpp: it names only what whoever
-// includes it has declared in namespace cj —
-//     InWindow, wave_copy, wave_match_copy, wave_order                the register window over the input and the three byte movers
-//     lds_ld(p), lds_ld8(p)     a wave-uniform 32-bit / 8-bit read of the wavefront's LDS
-//     out_ld8(p)                a wave-uniform read of one byte of the output written so far
-//     lds_add(p, v), lds_xor(p, v)   lane-wise read-modify-write of an LDS word
-//     CJ_LANES(lane)            the body that follows runs once per lane (the device: for this lane; the host: a loop over 0..63).  A body
-//                               never reads what another lane writes in the SAME body; wave_order() separates bodies
-//     LaneBytes                 put(k, byte): lane k keeps a byte; flush(dst, n): lanes 0..n-1 store theirs to dst[lane]
-// — cj_common.hpp + deflate.hip for the device, tests/hostsim/sim_deflate_decode.cpp for the host, where bounds-checked stand-ins
-// let the CPU tests hold the grammar, every copy's bounds and every table index to zlib.  Not part of the C-ABI.
+// wavefront, accept / reject rules of zlib's inflate.  Written like lz4_dict_wave.hpp: it names only
+//     InWindow, wave_copy, wave_match_copy, wave_order, CJ_LANES, lds_ld, lds_ld8, lds_add, lds_xor, out_ld8, LaneBytes
+// of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
+// tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_deflate_decode.cpp), where
+// the CPU tests hold the grammar, every copy's bounds and every table index to zlib.  Not part of the C-ABI.
 //
 // Mapping.  All stream state (bit buffer, positions, the symbol being decoded) is wave-uniform; the lanes build the Huffman tables
 // and move the bytes.  A round is a run of up to 64 literals, lane k keeping literal k, stored in ONE step when a match, the
@@ -17,6 +11,7 @@
 // blocks are a wave_copy.  Checksums are one lane-parallel pass over the finished output (crc32_lanes.hpp).
 #pragma once
 #include "crc32_lanes.hpp"
+#include "wave_window.hpp"
 
 namespace cj {
 
@@ -196,11 +191,8 @@ struct DfBits {
     uint32_t cnt;      // valid bits in buf
     uint64_t buf;
     __device__ __forceinline__ void init(const uint8_t* in, uint32_t n) {
-        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-        w.base = in - mis;
-        w.iend = mis + n;
-        w.anchor(mis);
-        ip = mis; cnt = 0; buf = 0;
+        ip = window_open(w, in, n);
+        cnt = 0; buf = 0;
     }
     // afterwards cnt >= 33, or every bit of the input is in the buffer
     __device__ __forceinline__ void refill() {

@@ -6,6 +6,8 @@
 #include "big_chunks.hpp"
 #include "frame_grammar.hpp"
 
+#include <atomic>
+
 using cj::hip_ok;
 using cj::parallel_chunks;
 
@@ -20,6 +22,15 @@ void cj::fill_args(cj::BatchArgs& a, uint32_t flags, size_t n, const uint8_t* in
     a.in_base = in_base; a.in_off = in_off; a.in_len = in_len;
     a.out_base = out_base; a.out_off = out_off; a.out_cap = out_cap;
     a.result = result; a.n_chunks = (uint32_t)n; a.flags = flags; a.hist = nullptr;
+}
+
+namespace {
+std::atomic<size_t> g_grid_chunks{cj::kGridChunks};
+}
+size_t cj::grid_chunks() { return g_grid_chunks.load(); }
+// tests: the chunks per launch of the sliced wavefront-per-chunk kernels (0 or more than kGridChunks = the default); returns the previous value
+extern "C" uint64_t cj_debug_grid_chunks(uint64_t n) {
+    return g_grid_chunks.exchange(n == 0 || n > cj::kGridChunks ? cj::kGridChunks : (size_t)n);
 }
 
 namespace {

@@ -21,10 +21,7 @@ __device__ __forceinline__ int64_t lz4_wave_decode(const uint8_t* in, uint32_t n
     if (n == 0) return CJ_E_CORRUPT;
 
     InWindow w;
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-    w.base = in - mis;
-    w.iend = mis + n;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, n);
     const uint32_t iend = w.iend;
     uint32_t ip = mis;      // input position relative to w.base
     uint32_t op = 0;        // output position

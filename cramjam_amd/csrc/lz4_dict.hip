@@ -42,11 +42,8 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_dict_size_kernel(uint32_t n
     const uint64_t n64 = in_len[c];
     if (n64 == 0 || n64 > kLz4InMax) { if (lane_id() == 0) result[c] = CJ_E_CORRUPT; return; }
     const uint8_t* in = in_base + in_off[c];
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
     InWindow w;
-    w.base = in - mis;
-    w.iend = mis + (uint32_t)n64;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, (uint32_t)n64);
     const int64_t r = lz4_size_walk([&](uint32_t p) { p = uni(p); w.ensure(p); return w.fetch32(p); },
                                     [&](uint32_t p, uint32_t e) { return uni(lz4_ff_run(w.base, uni(p), e)); }, mis, w.iend, hist);
     if (lane_id() == 0) result[c] = r;
@@ -141,7 +138,7 @@ int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_ba
     uint8_t* stage = (uint8_t*)e->d_dict_stage.p;
     uint64_t* rows = reinterpret_cast<uint64_t*>(stage + slots_bytes);
     const uint32_t prefix = (flags & CJ_FLAG_LZ4_SIZE_PREFIX) ? 1u : 0u;
-    for (size_t first = 0; first < n; first += per) {
+    for (size_t first = 0; first < n; first += per) {      // (the slices of the staging budget: their rows are the slots', not the caller's)
         const uint32_t k = (uint32_t)std::min(per, n - first);
         cj::DictStage g = {in_base, in_off + first, in_len + first, out_off + first, out_cap + first, dict_tail, stage,
                            rows, rows + per, rows + 2 * per, rows + 3 * per, reinterpret_cast<uint32_t*>(rows + 4 * per), stride, hist, k, prefix};
@@ -151,11 +148,10 @@ int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_ba
         a.hist = g.r_hist;
         HIP_TRY(cj::launch_lz4_encode(a, s), CJ_E_NO_DEVICE);
     }
-    for (size_t first = 0; first < n; first += cj::kGridChunks << 6) {
-        const uint32_t k = (uint32_t)std::min(cj::kGridChunks << 6, n - first);
-        hipLaunchKernelGGL(cj::dict_finish_kernel, dim3((k + cj::kBlockThreads - 1) / cj::kBlockThreads), dim3(cj::kBlockThreads), 0, s, k, in_len + first, out_base,
-                           out_off + first, result + first, prefix);
-    }
+    cj::for_slices(n, cj::grid_chunks() << 6, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {      // one lane per chunk
+        hipLaunchKernelGGL(cj::dict_finish_kernel, dim3((a.n_chunks + cj::kBlockThreads - 1) / cj::kBlockThreads), dim3(cj::kBlockThreads), 0, s, a.n_chunks, a.in_len,
+                           out_base, a.out_off, a.result, prefix);
+    });
     return turn.done(s);
 }
 
@@ -166,22 +162,18 @@ int batch_launch(cj_engine* e, cj_op op, uint32_t flags, size_t n, const uint8_t
     const uint8_t* dict_end = dict + dict_len;
     if (op == CJ_OP_COMPRESS)
         return compress_device(e, flags, n, in_base, in_off, in_len, out_base, out_off, out_cap, result, dict_end - hist, hist, s);
-    for (size_t first = 0; first < n; first += cj::kGridChunks) {
-        cj::BatchArgs a;
-        cj::fill_args(a, flags, std::min(cj::kGridChunks, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
-        hipLaunchKernelGGL(cj::lz4_dict_decode_kernel, dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a, dict_end, hist);
-    }
+    cj::for_slices(n, cj::grid_chunks(), flags, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
+        hipLaunchKernelGGL(cj::lz4_dict_decode_kernel, cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, dict_end, hist);
+    });
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
 
 int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, size_t dict_len, hipStream_t s) {
     const uint32_t hist = (uint32_t)std::min<size_t>(dict_len, cj::kDictWindow);
-    for (size_t first = 0; first < n; first += cj::kGridChunks) {
-        const uint32_t k = (uint32_t)std::min(cj::kGridChunks, n - first);
-        hipLaunchKernelGGL(cj::lz4_dict_size_kernel, dim3((k + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, k, in_base, in_off + first,
-                           in_len + first, result + first, hist);
-    }
+    cj::for_slices(n, cj::grid_chunks(), 0u, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, [&](const cj::BatchArgs& a) {
+        hipLaunchKernelGGL(cj::lz4_dict_size_kernel, cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a.n_chunks, a.in_base, a.in_off, a.in_len, a.result, hist);
+    });
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }

@@ -1,10 +1,11 @@
 // lz4_dict_wave.hpp — the LZ4 block decoder of one wavefront for blocks written against a DICTIONARY (LZ4_loadDict +
 // LZ4_compress_fast_continue; read by LZ4_decompress_safe_usingDict): lz4_wave_decode's grammar and accept / reject rules
 // (lz4_decode.hip), only the match differs — its source may begin in a dictionary that does NOT lie in front of the output.  It names
-// only InWindow, wave_copy, wave_match_copy and wave_order, which whoever includes it has declared in namespace cj: cj_common.hpp for
-// the device, tests/hostsim/sim_lz4_dict_decode.cpp for the host, where byte-exact stand-ins with bounds checks let the CPU tests hold
-// the grammar and every copy's bounds to tests/lz4_dict_model.py.  Not part of the C-ABI.
+// only InWindow, wave_copy, wave_match_copy and wave_order of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
+// tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_lz4_dict_decode.cpp), where
+// the CPU tests hold the grammar and every copy's bounds to tests/lz4_dict_model.py.  Not part of the C-ABI.
 #pragma once
+#include "wave_window.hpp"
 
 namespace cj {
 
@@ -16,10 +17,7 @@ __device__ __forceinline__ int64_t lz4_dict_wave_decode(const uint8_t* in, uint3
     if (n == 0) return CJ_E_CORRUPT;
 
     InWindow w;
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-    w.base = in - mis;
-    w.iend = mis + n;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, n);
     const uint32_t iend = w.iend;
     uint32_t ip = mis;      // input position relative to w.base
     uint32_t op = 0;        // output position

@@ -29,10 +29,7 @@ __global__ __launch_bounds__(kBlockThreads) void snappy_decode_kernel(BatchArgs 
     if (status != 0) { if (lane_id() == 0) a.result[chunk] = status; return; }
 
     InWindow w;
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-    w.base = in - mis;
-    w.iend = mis + (uint32_t)n64;
-    w.anchor(mis);
+    const uint32_t mis = window_open(w, in, (uint32_t)n64);
     const uint32_t iend = w.iend;
     uint32_t ip = mis;
 

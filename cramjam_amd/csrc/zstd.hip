@@ -1,27 +1,13 @@
 // zstd.hip — batches of Zstandard chunks, decode only (cj_zstd_batch_device / _host, cj_zstd_batch_sizes_device / _host; DESIGN.md
 // §5.14): one chunk = what one ZSTD_decompress call reads, one wavefront per chunk, workgroups of four wavefronts.  The decoder is
-// zstd_wave.hpp (the same text tests/hostsim compiles for the host); this file gives it the wavefront: the accessors, each wavefront's
+// zstd_wave.hpp (the same text tests/hostsim compiles for the host); this file gives it the wavefront: the accessors (wave_lanes.hpp), each wavefront's
 // private tables in static LDS (10.0 KiB each), its literal slot in engine scratch and the launches.  The slots come from a fixed
 // budget (cj::ScratchTurn on e->zstd_slots): a batch goes through in slices of as many chunks as there are slots.  The size query is
 // the same decoder without stores and uses no scratch.  The device calls only enqueue (a decode that grows the slots waits for their
 // previous user while it reallocates).
-#include "deflate_lanes.hpp"
+#include "wave_lanes.hpp"
 
 #include <atomic>
-
-namespace cj {
-
-struct LaneBytes {
-    uint32_t v;
-    __device__ __forceinline__ void put(uint32_t k, uint32_t byte) { if (lane_id() == k) v = byte; }
-    __device__ __forceinline__ void flush(uint8_t* dst, uint32_t n) { if (lane_id() < n) dst[lane_id()] = (uint8_t)v; }
-};
-__device__ __forceinline__ uint32_t in_ld8(const uint8_t* p) { return *p; }
-__device__ __forceinline__ uint32_t in_ld32(const uint8_t* p) { return ld32u(p); }
-__device__ __forceinline__ void slot_st8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
-__device__ __forceinline__ uint32_t out_rd32(const uint8_t* p) { return ld32u(p); }
-
-}  // namespace cj
 
 #include "zstd_wave.hpp"
 
@@ -58,12 +44,9 @@ bool fmt_ok(int fmt) { return fmt == CJ_ZSTD_FRAMES; }
 
 // the size query: enqueue only, no scratch
 int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
-    for (size_t first = 0; first < n; first += cj::kGridChunks) {
-        cj::BatchArgs a;
-        cj::fill_args(a, 0u, std::min(cj::kGridChunks, n - first), in_base, in_off + first, in_len + first, nullptr, nullptr, nullptr, result + first);
-        hipLaunchKernelGGL((cj::zstd_kernel<true>), dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a,
-                           (uint8_t*)nullptr);
-    }
+    cj::for_slices(n, cj::grid_chunks(), 0u, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, [&](const cj::BatchArgs& a) {
+        hipLaunchKernelGGL((cj::zstd_kernel<true>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, (uint8_t*)nullptr);
+    });
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
@@ -72,15 +55,13 @@ int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const
 int decode_device(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                   const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     const uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kZsSlotBytes);
-    const size_t per = (size_t)std::min<uint64_t>(n, slots_max);
+    const size_t per = (size_t)std::min<uint64_t>(std::min<uint64_t>(n, slots_max), cj::grid_chunks());
     cj::ScratchTurn turn(e->zstd_slots, s);
     if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_zstd_slots, per * (size_t)cj::kZsSlotBytes)) != 0) return turn.rc;
     uint8_t* slots = (uint8_t*)e->d_zstd_slots.p;
-    for (size_t first = 0; first < n; first += per) {
-        cj::BatchArgs a;
-        cj::fill_args(a, 0u, std::min(per, n - first), in_base, in_off + first, in_len + first, out_base, out_off + first, out_cap + first, result + first);
-        hipLaunchKernelGGL((cj::zstd_kernel<false>), dim3((a.n_chunks + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock), dim3(cj::kBlockThreads), 0, s, a, slots);
-    }
+    cj::for_slices(n, per, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
+        hipLaunchKernelGGL((cj::zstd_kernel<false>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, slots);
+    });
     return turn.done(s);
 }
 

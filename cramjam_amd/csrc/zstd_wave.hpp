@@ -1,16 +1,10 @@
 // zstd_wave.hpp — the Zstandard decoder of one wavefront (RFC 8878 frames, no dictionary): one chunk of one or more frames per
 // wavefront, accept / reject rules of libzstd's one-shot ZSTD_decompress (1.4.x).  Written like deflate_wave.hpp: it
-// names only what whoever includes it has declared in namespace cj —
-//     InWindow, wave_copy, wave_match_copy, wave_order     the register window over the input and the three byte movers
-//     lds_ld(p)                 a wave-uniform 32-bit read of the wavefront's LDS
-//     lds_add(p, v), lds_or(p, v)    lane-wise read-modify-write of an LDS word
-//     in_ld8(p), in_ld32(p)     a lane's own read of the input (the Huffman streams: one lane per stream)
-//     slot_st8(p, v)            a lane's own store into the wavefront's literal slot
-//     out_ld8(p)                a wave-uniform read of one byte of the output;  out_rd32(p): a lane's own 32-bit read of it (XXH64)
-//     CJ_LANES(lane)            the body that follows runs once per lane; a body never reads what another lane writes in the SAME body
-//     LaneBytes                 put(k, byte) / flush(dst, n), as in deflate_wave.hpp
-// — cj_common.hpp + zstd.hip for the device, tests/hostsim/sim_zstd_decode.cpp for the host with bounds-checked stand-ins.  Not part of
-// the C-ABI.
+// names only
+//     InWindow, wave_copy, wave_match_copy, wave_order, CJ_LANES, lds_ld, lds_add, lds_or, in_ld8, in_ld32 (the Huffman streams: one
+//     lane per stream), slot_st8 (the literal slot), out_ld8, out_rd32 (XXH64), LaneBytes
+// of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
+// tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_zstd_decode.cpp).  Not part of the C-ABI.
 //
 // Mapping.  All grammar state is wave-uniform: frame and block headers, the FSE table descriptions, the sequences' backward
 // bitstream (an exact model of libzstd's 64-bit BIT_DStream_t, so that a stream that over-reads gets libzstd's verdict) and the three
@@ -30,6 +24,7 @@
 //     literal overruns are still checked
 // A chunk the decoder refuses for one of these may get a size or a later error from the query; every other verdict is the decoder's.
 #pragma once
+#include "wave_window.hpp"
 
 namespace cj {
 
@@ -57,12 +52,7 @@ __device__ __forceinline__ uint32_t zs_highbit(uint32_t v) { return 31u - (uint3
 // Positions are relative to w.base.  Callers read only below iend; what a 32-bit read brings from beyond is masked off.
 struct ZsIn {
     InWindow w;
-    __device__ __forceinline__ void init(const uint8_t* in, uint32_t n) {
-        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u);
-        w.base = in - mis;
-        w.iend = mis + n;
-        w.anchor(mis);
-    }
+    __device__ __forceinline__ void init(const uint8_t* in, uint32_t n) { window_open(w, in, n); }
     __device__ __forceinline__ uint32_t f32(uint32_t pos) {               // reading forward
         if (pos - w.wpos > 500u) w.anchor(pos);
         return w.fetch32(pos);

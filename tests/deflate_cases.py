@@ -7,8 +7,9 @@ import ctypes as C
 import hashlib
 import json
 import os
-import subprocess
 import zlib
+
+from hostsim_build import SIM_DIR, build_sim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -463,10 +464,7 @@ def cases(wrap=None):
 # ---- the kernel's decoder on the host ---------------------------------------------------------------------------------------------------
 def sim_lib():
     if "sim" not in _cache:
-        sim = os.path.join(ROOT, "tests", "hostsim")
-        so = os.path.join(sim, "libsim_deflate_decode.so")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", so, os.path.join(sim, "sim_deflate_decode.cpp")])
-        L = C.CDLL(so)
+        L = C.CDLL(build_sim("sim_deflate_decode.cpp", os.path.join(SIM_DIR, "libsim_deflate_decode.so")))
         L.sim_deflate_decode.restype = C.c_longlong
         L.sim_deflate_decode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint]
         _cache["sim"] = L

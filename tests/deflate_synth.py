@@ -627,7 +627,7 @@ def write_cases_file(path, others=(), only=None):
     of `others`; only: these cases and not all of them) at capacities n, n + 64, n - 1, 0 and its cuts, the four misalignments in turn, and in size mode, with zlib's verdict and
     bytes.  Format: that file's.  Returns the count.
         python -c "import sys; sys.path.insert(0, 'tests'); import deflate_synth as S, deflate_cases as D; print(S.write_cases_file('cases.bin', [(o['name'], o['wrap'], o['bytes']) for o in D.others()]))"
-        g++ -O1 -g -std=c++17 -DSIM_MAIN -fsanitize=address,undefined -o sim_main tests/hostsim/sim_deflate_decode.cpp && ./sim_main cases.bin"""
+        python -c "import sys; sys.path.insert(0, 'tests'); from hostsim_build import build_sim; build_sim('sim_deflate_decode.cpp', 'sim_main', main=True, sanitize=True)" && ./sim_main cases.bin"""
     import struct
     rows = []
     todo = [(c.wrap, c.stream, c.cuts) for c in (cases() if only is None else only)] + [(w, s, ()) for _, w, s in others]

@@ -14,6 +14,7 @@ import batch_sizes_cases as K
 from conftest import ROOT
 from cramjam_amd import _native as N
 from cramjam_amd import batch
+from hostsim_build import build_sim
 
 SIM_DIR = os.path.join(ROOT, "tests", "hostsim")
 SIM = os.path.join(SIM_DIR, "sim_lz4_size_walk")
@@ -22,8 +23,7 @@ SIM = os.path.join(SIM_DIR, "sim_lz4_size_walk")
 @pytest.fixture(scope="module")
 def walked():
     """[(tag, block, from_encoder, the host walk's answer)] for every case"""
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-static-libasan", "-o", SIM, os.path.join(SIM_DIR, "sim_lz4_size_walk.cpp")])
+    build_sim("sim_lz4_size_walk.cpp", SIM, main=True, sanitize=True, extra=["-static-libasan"])
     cases = K.lz4_cases()
     feed = b"".join(struct.pack("<I", len(b)) + b for _, b, _ in cases)
     r = subprocess.run([SIM], input=feed, capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=900)

@@ -219,7 +219,7 @@ def test_code_builder(nsym, limit, pad):
     for name, hist in _histograms(nsym):
         h = (C.c_uint32 * nsym)(*hist)
         got, want = (C.c_ubyte * nsym)(), (C.c_ubyte * nsym)()
-        L.sim_dfe_build_lens(h, nsym, limit, pad, got)
+        assert L.sim_dfe_build_lens(h, nsym, limit, pad, got) != E.SIM_BOUNDS, name
         L.dfe_model_build_lens(h, nsym, limit, pad, want)
         lens = list(got)
         assert lens == list(want), name
@@ -234,7 +234,7 @@ def test_code_builder(nsym, limit, pad):
             assert lens[used[0]] == 1
         # canonical order: by (length, symbol), each code the successor of the one before, shifted at a length's start
         codes = (C.c_uint32 * nsym)()
-        L.sim_dfe_assign_codes(got, nsym, limit, codes)
+        assert L.sim_dfe_assign_codes(got, nsym, limit, codes) != E.SIM_BOUNDS, name
         code, prev = 0, 0
         for ln, s in sorted((lens[s], s) for s in coded):
             code <<= ln - prev

@@ -13,6 +13,7 @@ import pytest
 import zstd_cases as Z
 import zstd_synth as S
 from conftest import ROOT
+from hostsim_build import SimBuildError, build_sim
 from test_zstd_model import SIM_BOUNDS, SIM_SRC, _decode, sim  # noqa: F401  (sim: the host build, a module fixture)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_zstd_synth.json")
@@ -127,11 +128,12 @@ def test_recorded_verdicts_are_what_generator_and_libzstd_say_today():
 
 def test_sanitizer_build_runs_every_synthesized_case_as_a_program(tmp_path):
     exe, cases_file = str(tmp_path / "simz_asan"), str(tmp_path / "cases.bin")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DSIM_MAIN", "-o", exe, SIM_SRC],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and ("asan" in r.stderr or "ubsan" in r.stderr or "sanitize" in r.stderr):
-        pytest.skip("the compiler has no sanitizer runtime")
-    assert r.returncode == 0, r.stderr[-2000:]
+    try:
+        build_sim(SIM_SRC, exe, main=True, sanitize=True)
+    except SimBuildError as e:
+        if "asan" in e.stderr or "ubsan" in e.stderr or "sanitize" in e.stderr:
+            pytest.skip("the compiler has no sanitizer runtime")
+        raise
     recs = []
     for c in S.cases():
         for k, (cap, (want, data)) in enumerate(zip(Z.capacities(cap_of(c)), verdicts(c))):

@@ -35,11 +35,26 @@ COVERAGE = ["block:raw", "block:rle", "block:compressed", "lit:raw", "lit:rle", 
 _zstd = None
 
 
+def _libzstd_file():
+    """The system's libzstd by its FILE.  By its soname, dlopen hands back whichever libzstd.so.1 the process already holds: behind a
+    libblosc that brings a libzstd of its own (one built without the legacy formats answers -50 on a v0.7 frame where the fixtures'
+    libzstd answers -53) the reference would silently be another library, and the fixtures would depend on the order of the tests."""
+    import subprocess
+    name = ctypes.util.find_library("zstd") or "libzstd.so.1"
+    try:
+        cache = subprocess.run(["/sbin/ldconfig", "-p"], capture_output=True, text=True).stdout
+    except OSError:
+        return name
+    for line in cache.splitlines():
+        if line.strip().startswith(name + " ") and "=>" in line:
+            return line.split("=>")[1].strip()
+    return name
+
+
 def libzstd():
     global _zstd
     if _zstd is None:
-        name = ctypes.util.find_library("zstd") or "libzstd.so.1"
-        L = C.CDLL(name)
+        L = C.CDLL(_libzstd_file(), mode=os.RTLD_NOW | getattr(os, "RTLD_DEEPBIND", 0))
         L.ZSTD_decompress.restype = C.c_size_t
         L.ZSTD_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.ZSTD_compress2.restype = C.c_size_t
