@@ -38,16 +38,19 @@ _layouts = {}
 
 def _layout(key, cases):
     """the host side of one batch, built once per case list: packed input, the four descriptor rows, the offsets, and the mask of the
-    output bytes that must still be 0xA5 after the call (everything but [0, result) of an accepted and [0, cap) of a refused chunk)"""
+    output bytes that must still be 0xA5 after the call (everything but [0, result) of an accepted and [0, cap) of a refused chunk).
+    A case may carry `after` (tests/input_cases.py): bytes packed right behind its in_len, inside its own slot — what a read past the
+    input's end sees; at least 16 zero bytes of the slot still follow them, so the next case's bytes never serve as `after`."""
     if key not in _layouts:
         n = len(cases)
         off, run = np.zeros(n, np.uint64), 0
         for i, c in enumerate(cases):
             m = (5 * i) % 16
-            off[i] = run + m; run += (m + len(c["bytes"]) + 15) // 16 * 16 + 16
+            off[i] = run + m; run += (m + len(c["bytes"]) + len(c.get("after", b"")) + 15) // 16 * 16 + 16
         blob = np.zeros(run + 64, np.uint8)
         for o, c in zip(off, cases):
-            blob[int(o):int(o) + len(c["bytes"])] = np.frombuffer(c["bytes"], np.uint8)
+            b = c["bytes"] + c.get("after", b"")
+            blob[int(o):int(o) + len(b)] = np.frombuffer(b, np.uint8)
         caps = np.array([c["cap"] for c in cases], np.uint64)
         ooff = (G + np.concatenate([[0], np.cumsum(caps + np.uint64(G))[:-1]])).astype(np.uint64)
         total = int(ooff[-1] + caps[-1]) + G + 64
