@@ -24,6 +24,7 @@ E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
 E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
 E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -50, -51, -52, -53, -54
 ZSTD_FRAMES = 0                    # cj_zstd_format (cj_zstd_batch_*)
+ZSTD_FLAG_CHECKSUM = 1             # cj_zstd_compress_batch_*: a Content_Checksum behind the last block
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
 
 
@@ -92,6 +93,9 @@ SYMBOLS = {
     "cj_deflate_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_bound": (_sz, [_sz, _int]),
+    "cj_zstd_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_zstd_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_zstd_compress_bound": (_sz, [_sz, _u32]),
     "cj_batch_device_timed": (C.c_double, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "cj_blosc_chunk_max_compressed_len": (_sz, [_sz]),
     "cj_blosc_chunk_info": (_i64, [_vp, _sz, _vp]),
@@ -123,6 +127,7 @@ BENCH_SYMBOLS = {
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_zstd_enc_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_grid_chunks": (C.c_uint64, [C.c_uint64]),
 }
 
@@ -201,8 +206,9 @@ DICT = Kind("cj_dict_batch_host", "cj_dict_batch_device", "cj_dict_batch_sizes_h
 DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_batch_sizes_host", "cj_deflate_batch_sizes_device")   # what = a DEFLATE_*
 DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_batch_device", None, None, one_op=True)      # what = a DEFLATE_*; no size query
 ZSTD = Kind("cj_zstd_batch_host", "cj_zstd_batch_device", "cj_zstd_batch_sizes_host", "cj_zstd_batch_sizes_device")   # what = ZSTD_FRAMES
+ZSTD_COMPRESS = Kind("cj_zstd_compress_batch_host", "cj_zstd_compress_batch_device", None, None, one_op=True)      # what = ZSTD_FRAMES; no size query
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
-_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, BLOSC)}
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BLOSC)}
 
 
 class Engine:
@@ -266,7 +272,7 @@ class Engine:
     def _host(self, entry, codec, op, flags, args, fn, params, dictionary):
         """entry: batch_host or batch_host_into of the CPython host layer (the engine scatters straight into the bytes objects / the buffer).
         fn: a Kind, or the name of its host entry — the call's signature is the Kind's: BLOSC takes params, the bytes of a cj_blosc_params
-        (b"" = decompress; codec is not used), DICT a dictionary, bytes-like (borrowed), DEFLATE_COMPRESS has no op.  None: DICT with a
+        (b"" = decompress; codec is not used), DICT a dictionary, bytes-like (borrowed), DEFLATE_COMPRESS and ZSTD_COMPRESS have no op.  None: DICT with a
         dictionary, BLOSC with params, else BLOCKS.  An argument the Kind does not take: ValueError."""
         from . import _cramjam
         if fn is None:

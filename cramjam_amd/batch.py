@@ -37,7 +37,7 @@ def _pick(seq, idx):
 
 def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None):
     """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress),
-    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*).
+    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*), N.ZSTD / N.ZSTD_COMPRESS (what = ZSTD_FRAMES).
     out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
     tail = {"dictionary": params} if kind is N.DICT else {"params": params}
@@ -583,7 +583,7 @@ def deflate_sizes_device(inp, in_off, in_len, wrapper="raw", result=None, device
     return _device_sizes(N.DEFLATE, _deflate_wrap(wrapper), 0, inp, in_off, in_len, result, device, stream, sync)
 
 
-# ---- Zstandard frames (cj_zstd_batch_* / cj_zstd_batch_sizes_*): decode only --------------------------------------------
+# ---- Zstandard frames (cj_zstd_batch_* / cj_zstd_batch_sizes_*): decode --------------------------------------------------
 # One entry is what one ZSTD_decompress call reads: one or more frames, skippable frames skipped, b"" decoding to b"".  result[i] = the
 # decoded length or a negative CJ_E_* code: -50 a bad frame header (legacy frames included), -51 corrupt data, -52 content checksum,
 # -53 truncated input or bytes behind the last frame, -54 the frame names a dictionary, -6 a capacity too small.
@@ -634,3 +634,32 @@ def deflate_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, wra
     deflate_compress_bound(in_len[i], wrapper) always suffices.  Enqueue-only with device-resident metadata, a result tensor and
     sync=False (a call that has to grow the engine's record slots waits for their previous user)."""
     return _device_batch(N.DEFLATE_COMPRESS, _deflate_wrap(wrapper), N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+# ---- ... and into Zstandard frames (cj_zstd_compress_batch_* / cj_zstd_compress_bound; DESIGN.md 5.15) --------------------------------
+# One frame per buffer: independent pieces of at most 64 KiB, each one RLE, Compressed or Raw block.  result[i] = the frame's length
+# or a negative CJ_E_* code (-6: the capacity is too small; -1: a buffer above 0x7E000000 bytes).
+def _zstd_flags(checksum):
+    return N.ZSTD_FLAG_CHECKSUM if checksum else 0
+
+
+def zstd_compress_bound(n, checksum=False):
+    """the capacity that always suffices for a buffer of n bytes (exact worst case of the layout: every piece a Raw block; 0 above
+    0x7E000000).  No device."""
+    return N.lib().cj_zstd_compress_bound(n, _zstd_flags(checksum))
+
+
+def zstd_compress_many(buffers, checksum=False, devices=None, out=None):
+    """one Zstandard frame per buffer; returns (results, outputs) as lz4_compress_blocks.  checksum: a Content_Checksum (XXH64's low 32
+    bits) behind the last block — what zstd_decompress_many and libzstd's ZSTD_decompress read and verify.  out: as in
+    lz4_decompress_blocks; it has to hold sum(zstd_compress_bound(len(buffer), checksum)) bytes."""
+    flags, L = _zstd_flags(checksum), N.lib()
+    caps = [L.cj_zstd_compress_bound(memoryview(b).nbytes, flags) for b in buffers]
+    return _run(N.ZSTD_FRAMES, N.OP_COMPRESS, flags, buffers, caps, devices, out, N.ZSTD_COMPRESS)
+
+
+def zstd_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, checksum=False, result=None, device=None, stream=None, sync=True):
+    """Compress a device-resident batch into Zstandard frames (arguments as lz4_compress_blocks_device); out_cap[i] >=
+    zstd_compress_bound(in_len[i], checksum) always suffices.  Enqueue-only with device-resident metadata, a result tensor and
+    sync=False (a call that has to grow the engine's record and literal slots waits for their previous user)."""
+    return _device_batch(N.ZSTD_COMPRESS, N.ZSTD_FRAMES, N.OP_COMPRESS, _zstd_flags(checksum), inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)

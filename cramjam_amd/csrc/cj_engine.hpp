@@ -164,6 +164,8 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     cj::DevBuf d_deflate_slots;
     cj::Scratch zstd_slots;        // zstd.hip: the wavefronts' literal slots of a decode batch
     cj::DevBuf d_zstd_slots;
+    cj::Scratch zstd_enc_slots;    // zstd_encode.hip: the workgroups' record and literal slots of a compress batch
+    cj::DevBuf d_zstd_enc_slots;
 };
 
 namespace cj {

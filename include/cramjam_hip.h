@@ -421,7 +421,7 @@ CJ_API int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, ui
                                           uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 CJ_API size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap);
 
-/* Zstandard frames — decode only (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
+/* Zstandard frames — decode (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
  * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an
  * empty input decoding to 0 bytes.  One wavefront decodes a chunk; result[i] and the bytes are libzstd's (1.4.x).
  * Addressing, the 16-byte-granule rule, stream rules, e == NULL, n_chunks == 0 and the null-pointer rules are cj_deflate_batch_*'s.
@@ -462,6 +462,36 @@ CJ_API int cj_zstd_batch_sizes_device(cj_engine* e, cj_zstd_format fmt, uint32_t
                                       int64_t* result, void* hip_stream);
 CJ_API int cj_zstd_batch_sizes_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n_chunks,
                                     const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+
+/* Batches of inputs INTO Zstandard frames: one chunk in gives exactly one frame out — magic, a descriptor with
+ * Frame_Content_Size always (Single_Segment up to 64 KiB, above that a Window_Descriptor of 64 KiB), no dictionary id, one block per
+ * independent piece of at most 64 KiB (no match crosses a piece, distances up to 65 535): RLE when the piece is one repeated byte,
+ * Compressed when its exact size is below the piece's, else Raw.  A Compressed block's literals are Raw, RLE or Huffman-coded (codes of
+ * at most 11 bits, the tree as direct or FSE-compressed weights, one stream up to 1023 literals and four above), its sequences FSE-coded,
+ * each table in RLE mode, FSE_Compressed or Predefined by an estimated cost; offsets are distance + 3 or the repeat code 1.  The bytes depend on nothing but the input and the
+ * flag; an empty input gives a header and one empty last Raw block.  What cj_zstd_batch_* (libzstd's ZSTD_decompress) accepts is the
+ * contract.  Addressing, the 16-byte-granule rule, stream rules, e == NULL, n_chunks == 0 and the null-pointer rules are
+ * cj_deflate_compress_batch_*'s.
+ *   fmt         CJ_ZSTD_FRAMES; anything else is CJ_E_BAD_ARG.      flags   0 or CJ_ZSTD_FLAG_CHECKSUM; any other bit is CJ_E_BAD_ARG.
+ *   result[i]   the frame's length or CJ_E_*: in_len[i] > 0x7E000000 is CJ_E_INPUT_TOO_LARGE in that chunk's own result;
+ *               CJ_E_OUT_TOO_SMALL when the frame does not fit out_cap[i] (checked per block from its exact size, before its first
+ *               store: nothing is written at or behind out_cap[i]; what lies in the slot of such a chunk is unspecified).
+ *   bound       cj_zstd_compress_bound(n, flags): the exact worst case of this layout, every piece a Raw block = the header (6 bytes
+ *               for n <= 255, 7 up to 65 536, 8 up to 65 791, else 10) + 3 * max(1, ceil(n / 65536)) + n + 4 with the checksum
+ *               <= n + 3 * (n / 65536 + 1) + 14; a capacity of that many bytes never gives CJ_E_OUT_TOO_SMALL.  0 for a bad flag or
+ *               n > 0x7E000000.  Pure arithmetic, no device.
+ * The _device call only enqueues (like every call, one that has to GROW the engine's scratch — the workgroups' record and literal
+ * slots, within a fixed budget — waits for its previous user while it reallocates).  The _host call is cj_batch_host's one-shot
+ * staging, synchronous.  cj_zstd_batch_* with CJ_OP_COMPRESS stays CJ_E_BAD_ARG. */
+#define CJ_ZSTD_FLAG_CHECKSUM 1u     /* Content_Checksum: low 32 bits of XXH64 of the input behind the last block */
+CJ_API int cj_zstd_compress_batch_device(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n_chunks,
+                                         const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                         uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                         int64_t* result, void* hip_stream);
+CJ_API int cj_zstd_compress_batch_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n_chunks,
+                                       const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                       uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API size_t cj_zstd_compress_bound(size_t n, uint32_t flags);
 
 /* =====================================================================================
  * Blosc chunks (reference src/blosc2.rs:133-210 compress_chunk / decompress_chunk and their _into forms, :702-706

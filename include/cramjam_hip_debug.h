@@ -47,6 +47,9 @@ CJ_API uint64_t cj_debug_deflate_slot_budget(uint64_t bytes);
 /* Zstandard decode (cj_zstd_batch_*): the bytes of literal slots per slice, one slot of 128 KiB + 32 per stream in flight (0 = the
  * default); returns the previous value */
 CJ_API uint64_t cj_debug_zstd_slot_budget(uint64_t bytes);
+/* Zstandard compress (cj_zstd_compress_batch_*): the bytes of record-and-literal slots per slice, one slot of 320.25 KiB per frame in
+ * flight (0 = the default, 1024 slots); returns the previous value.  Tests force more than one slice with it. */
+CJ_API uint64_t cj_debug_zstd_enc_slot_budget(uint64_t bytes);
 /* The wavefront-per-chunk batches (cj_deflate_batch_*, cj_zstd_batch_*, cj_dict_batch_* and their size queries): the chunks per
  * kernel launch (0 = the default, 2^22: a grid stays below 2^32 threads); returns the previous value.  Tests force more than one
  * launch with it. */
