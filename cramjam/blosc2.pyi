@@ -37,6 +37,6 @@ class Codec(IntEnum):
 
 def compress_chunk(data: BytesType, typesize: Optional[int] = None, clevel: Optional[CLevel] = None, filter: Optional[Filter] = None, codec: Optional[Codec] = None) -> Buffer: ...
 def compress_chunk_into(input: BytesType, output: BytesType, typesize: Optional[int] = None, clevel: Optional[CLevel] = None, filter: Optional[Filter] = None, codec: Optional[Codec] = None) -> int: ...
-def decompress_chunk(data: BytesType, output_len: Optional[int] = None, blosclz: bool = False) -> Buffer: ...
-def decompress_chunk_into(input: BytesType, output: BytesType, blosclz: bool = False) -> int: ...
+def decompress_chunk(data: BytesType, output_len: Optional[int] = None, blosclz: bool = False, zlib: bool = False, zstd: bool = False) -> Buffer: ...
+def decompress_chunk_into(input: BytesType, output: BytesType, blosclz: bool = False, zlib: bool = False, zstd: bool = False) -> int: ...
 def max_compressed_len(len_bytes: int) -> int: ...

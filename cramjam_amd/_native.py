@@ -26,6 +26,8 @@ E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -
 ZSTD_FRAMES = 0                    # cj_zstd_format (cj_zstd_batch_*)
 ZSTD_FLAG_CHECKSUM = 1             # cj_zstd_compress_batch_*: a Content_Checksum behind the last block
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
+BLOSC_FLAG_READ_ZLIB = 8           # ... zlib streams (compressor format 3)
+BLOSC_FLAG_READ_ZSTD = 16          # ... Zstandard frames (compressor format 4)
 
 
 class BloscParams(C.Structure):
@@ -183,11 +185,12 @@ class Kind:
         self.one_op = one_op                        # the calls have one direction: their argument lists carry no `op`
         self.dictionary = dictionary                # the calls take (dict, dict_len) / (dict_len,) behind result: `params` = that tuple
 
-    def read_flags(self, blosclz=False):
-        """the flags word of a reading call of this kind: `blosclz` (Blosc chunks only) asks for BloscLZ streams to be read too"""
-        if blosclz and not self.blosc:
-            raise ValueError("blosclz applies to Blosc chunks only")
-        return BLOSC_FLAG_READ_BLOSCLZ if blosclz else 0
+    def read_flags(self, blosclz=False, zlib=False, zstd=False):
+        """the flags word of a reading call of this kind: `blosclz`, `zlib`, `zstd` (Blosc chunks only) ask for chunks whose streams are
+        BloscLZ, zlib streams or Zstandard frames to be read too"""
+        if (blosclz or zlib or zstd) and not self.blosc:
+            raise ValueError("blosclz, zlib and zstd apply to Blosc chunks only")
+        return (BLOSC_FLAG_READ_BLOSCLZ if blosclz else 0) | (BLOSC_FLAG_READ_ZLIB if zlib else 0) | (BLOSC_FLAG_READ_ZSTD if zstd else 0)
 
     def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
         if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)

@@ -488,24 +488,27 @@ def snappy_framed_sizes(streams, devices=None):
 # result[i] = nbytes (decompress) / the chunk's size (compress) or a negative CJ_E_* code: -30 a malformed chunk, -31 one this
 # library does not read (another compressor format, C-Blosc2's extended header), -7 a bad LZ4 stream, -6 / -2 a capacity too small.
 # blosclz=True (reading calls; off by default): chunks whose streams are BloscLZ, c-blosc's default compressor, are read too
-# (CJ_BLOSC_FLAG_READ_BLOSCLZ); one batch may mix them with LZ4 chunks.
+# (CJ_BLOSC_FLAG_READ_BLOSCLZ); zlib=True / zstd=True: so are chunks whose streams are zlib streams / Zstandard frames (c-blosc's cname
+# "zlib" / "zstd"; CJ_BLOSC_FLAG_READ_ZLIB / _ZSTD).  One batch may mix all of them with LZ4 chunks.
 def _blosc_params(typesize, filter, clevel, codec, blocksize):
     from . import blosc2
     return bytes(blosc2._params(typesize, clevel, filter, codec, blocksize))
 
 
-def _chunk_nbytes(c, blosclz=False):
+def _chunk_nbytes(c, blosclz=False, zlib=False, zstd=False):
     """nbytes of a chunk on the host from its header alone, 0 for one that will be refused"""
     from . import blosc2
-    rc, nbytes = blosc2._info_nbytes(*_addr_len(c), blosclz)
+    rc, nbytes = blosc2._info_nbytes(*_addr_len(c), blosclz, zlib, zstd)
     return nbytes if rc == 0 else 0
 
 
-def blosc_decompress_chunks(chunks, devices=None, out=None, blosclz=False):
+def blosc_decompress_chunks(chunks, devices=None, out=None, blosclz=False, zlib=False, zstd=False):
     """decode many Blosc chunks; returns (results, outputs) as lz4_decompress_blocks.  The capacities are the chunks' own nbytes
     (read on the host from their headers); out: ONE writable buffer of at least their sum, the outputs are then views into it.
-    blosclz=True: chunks whose streams are BloscLZ are decoded too (the default refuses them with -31)."""
-    return _run(0, N.OP_DECOMPRESS, N.BLOSC.read_flags(blosclz), chunks, [_chunk_nbytes(c, blosclz) for c in chunks], devices, out, N.BLOSC, b"")
+    blosclz=True / zlib=True / zstd=True: chunks whose streams are BloscLZ / zlib streams / Zstandard frames are decoded too (the
+    default refuses them with -31)."""
+    return _run(0, N.OP_DECOMPRESS, N.BLOSC.read_flags(blosclz, zlib, zstd), chunks, [_chunk_nbytes(c, blosclz, zlib, zstd) for c in chunks], devices, out,
+                N.BLOSC, b"")
 
 
 def blosc_compress_chunks(buffers, typesize, filter=1, clevel=5, codec=1, blocksize=0, devices=None, out=None):
@@ -515,15 +518,17 @@ def blosc_compress_chunks(buffers, typesize, filter=1, clevel=5, codec=1, blocks
     return _run(0, N.OP_COMPRESS, 0, buffers, caps, devices, out, N.BLOSC, _blosc_params(typesize, filter, clevel, codec, blocksize))
 
 
-def blosc_chunk_sizes(chunks, devices=None, blosclz=False):
-    """nbytes of many Blosc chunks held on the host (list of ints; negative = the header's CJ_E_* code); blosclz: as in blosc_decompress_chunks"""
-    return _host_sizes(N.BLOSC, 0, N.BLOSC.read_flags(blosclz), chunks, devices)
+def blosc_chunk_sizes(chunks, devices=None, blosclz=False, zlib=False, zstd=False):
+    """nbytes of many Blosc chunks held on the host (list of ints; negative = the header's CJ_E_* code); blosclz, zlib, zstd: as in
+    blosc_decompress_chunks"""
+    return _host_sizes(N.BLOSC, 0, N.BLOSC.read_flags(blosclz, zlib, zstd), chunks, devices)
 
 
-def blosc_decompress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True, blosclz=False):
+def blosc_decompress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True, blosclz=False,
+                                   zlib=False, zstd=False):
     """Decode a device-resident batch of Blosc chunks (arguments as lz4_decompress_frames_device; the call waits for the stream once).
-    blosclz: as in blosc_decompress_chunks."""
-    return _device_batch(N.BLOSC, 0, N.OP_DECOMPRESS, N.BLOSC.read_flags(blosclz), inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    blosclz, zlib, zstd: as in blosc_decompress_chunks."""
+    return _device_batch(N.BLOSC, 0, N.OP_DECOMPRESS, N.BLOSC.read_flags(blosclz, zlib, zstd), inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
 def blosc_compress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, typesize, filter=1, clevel=5, codec=1, blocksize=0,
@@ -534,10 +539,10 @@ def blosc_compress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, typ
                          blosc2._params(typesize, clevel, filter, codec, blocksize))
 
 
-def blosc_chunk_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True, blosclz=False):
+def blosc_chunk_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True, blosclz=False, zlib=False, zstd=False):
     """nbytes of every chunk of a device-resident batch after the header checks, or their error; enqueue-only like lz4_block_sizes_device.
-    blosclz: as in blosc_decompress_chunks."""
-    return _device_sizes(N.BLOSC, 0, N.BLOSC.read_flags(blosclz), inp, in_off, in_len, result, device, stream, sync)
+    blosclz, zlib, zstd: as in blosc_decompress_chunks."""
+    return _device_sizes(N.BLOSC, 0, N.BLOSC.read_flags(blosclz, zlib, zstd), inp, in_off, in_len, result, device, stream, sync)
 
 
 # ---- DEFLATE streams (cj_deflate_batch_* / cj_deflate_batch_sizes_*): raw DEFLATE, zlib streams, gzip members; decode only -----------

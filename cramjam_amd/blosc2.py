@@ -5,8 +5,10 @@
 What is read and written: Blosc1-format chunks (16-byte header, format version 2) whose streams are LZ4, behind no filter, the
 byte shuffle or the bitshuffle.  With `blosclz=True` the decompress calls also read chunks whose streams are BloscLZ (c-blosc's default
 compressor, what the reference's `compress_chunk` writes by default); it is off by default, and BloscLZ is never written.
-Refused with an error (never a wrong result): the other compressor formats (BloscLZ without that keyword, Zlib, Zstd,
-Snappy; on compress `Codec.BloscLz / ZLIB / ZSTD`), `Filter.Delta / TruncPrec`, and C-Blosc2's extended 32-byte header.  Not here:
+`zlib=True` and `zstd=True` do the same for chunks whose streams are zlib streams and Zstandard frames (c-blosc's cname "zlib" and
+"zstd", the reference's `Codec.ZLIB` / `Codec.ZSTD` on decompress: what `Blosc(cname="zstd")` of Zarr / numcodecs stores); neither is
+written.  Refused with an error (never a wrong result): the other compressor formats (BloscLZ, Zlib, Zstd without their keyword,
+Snappy always; on compress `Codec.BloscLz / ZLIB / ZSTD`), `Filter.Delta / TruncPrec`, and C-Blosc2's extended 32-byte header.  Not here:
 `SChunk`, the `compress` / `decompress` frame container, `Compressor` / `Decompressor`, `set_nthreads`.
 Deviations: `codec=None` means LZ4 (the reference's default is BloscLZ; every Blosc reader decodes either); `clevel` 1-9 select the
 one matcher of the engine, `clevel=0` stores; `typesize=None` is the itemsize of the buffer handed in (1 for `bytes`) as the
@@ -76,9 +78,9 @@ def _raise(exc, rc):
     raise exc("blosc2: %s" % _N.strerror(rc))
 
 
-def _one(op, data, cap, out, params, exc, blosclz=False):
+def _one(op, data, cap, out, params, exc, blosclz=False, zlib=False, zstd=False):
     from .batch import _engine
-    flags = _N.BLOSC.read_flags(blosclz)
+    flags = _N.BLOSC.read_flags(blosclz, zlib, zstd)
     try:
         eng = _engine(0)
         if out is None:
@@ -114,39 +116,41 @@ def compress_chunk_into(input, output, typesize=None, clevel=None, filter=None, 
     return _one(_N.OP_COMPRESS, mv, out.nbytes, out, bytes(p), _errors()[0])[0]
 
 
-def _info_nbytes(addr, n, blosclz=False):
-    """(cj_blosc_chunk_info's code, nbytes) of a chunk on the host.  cj_blosc_chunk_info reports the default reading; with `blosclz`
-    the one refusal that keyword lifts — compressor format 0 with versionlz 1, the last check before the block table's — is taken
-    back here.  The decode call checks the whole chunk again with the flag."""
+def _info_nbytes(addr, n, blosclz=False, zlib=False, zstd=False):
+    """(cj_blosc_chunk_info's code, nbytes) of a chunk on the host.  cj_blosc_chunk_info reports the default reading; with `blosclz`,
+    `zlib` or `zstd` the one refusal that keyword lifts — compressor format 0, 3 or 4 with versionlz 1, the last check before the block
+    table's — is taken back here.  The decode call checks the whole chunk again with the flags."""
     import ctypes as C
     info = _N.BloscInfo()
     rc = _N.lib().cj_blosc_chunk_info(addr, n, C.byref(info))
-    if rc == _N.E_BLOSC_UNSUPPORTED and blosclz and info.version == 2 and info.flags >> 5 == 0 and info.versionlz == 1 and not info.flags & 2:
+    opted = {0: blosclz, 3: zlib, 4: zstd}.get(info.flags >> 5, False)
+    if rc == _N.E_BLOSC_UNSUPPORTED and opted and info.version == 2 and info.versionlz == 1 and not info.flags & 2:
         rc = 0
     return rc, info.nbytes
 
 
-def _nbytes(mv, exc, blosclz=False):
+def _nbytes(mv, exc, blosclz=False, zlib=False, zstd=False):
     import numpy as np
     a = np.frombuffer(mv, dtype=np.uint8)
-    rc, nbytes = _info_nbytes(a.ctypes.data if a.size else None, a.size, blosclz)
+    rc, nbytes = _info_nbytes(a.ctypes.data if a.size else None, a.size, blosclz, zlib, zstd)
     if rc != 0:
         _raise(exc, rc)
     return nbytes
 
 
-def decompress_chunk(data, output_len=None, blosclz=False):
+def decompress_chunk(data, output_len=None, blosclz=False, zlib=False, zstd=False):
     """Blosc chunk decompression -> cramjam.Buffer (output_len is accepted and ignored, as in the reference: the chunk names its size).
-    blosclz=True: a chunk whose streams are BloscLZ is decoded too (the default refuses it as unsupported)"""
+    blosclz=True / zlib=True / zstd=True: a chunk whose streams are BloscLZ / zlib streams / Zstandard frames is decoded too (the
+    default refuses each as unsupported)"""
     from . import _cramjam
     mv, _ = _view(data)
     exc = _errors()[1]
-    _, outs = _one(_N.OP_DECOMPRESS, mv, _nbytes(mv, exc, blosclz), None, b"", exc, blosclz)
+    _, outs = _one(_N.OP_DECOMPRESS, mv, _nbytes(mv, exc, blosclz, zlib, zstd), None, b"", exc, blosclz, zlib, zstd)
     return _cramjam.Buffer(outs[0])
 
 
-def decompress_chunk_into(input, output, blosclz=False):
-    """Decompress a chunk into `output`; returns nbytes.  blosclz: as in decompress_chunk"""
+def decompress_chunk_into(input, output, blosclz=False, zlib=False, zstd=False):
+    """Decompress a chunk into `output`; returns nbytes.  blosclz, zlib, zstd: as in decompress_chunk"""
     mv, _ = _view(input)
     out = memoryview(output).cast("B")
-    return _one(_N.OP_DECOMPRESS, mv, out.nbytes, out, b"", _errors()[1], blosclz)[0]
+    return _one(_N.OP_DECOMPRESS, mv, out.nbytes, out, b"", _errors()[1], blosclz, zlib, zstd)[0]

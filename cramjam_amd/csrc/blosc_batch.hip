@@ -4,7 +4,8 @@
 //               (stream rows, filter block rows) -> the LZ4 streams of all chunks through the engine: those of transposed blocks as
 //               one batch into the scratch, those of blocks that need no transposition (no filter, typesize 1 under shuffle,
 //               bitshuffle's odd blocks) as one batch straight into the callers' slots — no scratch, no second pass; the BloscLZ
-//               streams (CJ_BLOSC_FLAG_READ_BLOSCLZ) the same two ways through blosclz_decode.hip; stored streams
+//               streams (CJ_BLOSC_FLAG_READ_BLOSCLZ) the same two ways through blosclz_decode.hip, the Zlib and Zstd streams
+//               (CJ_BLOSC_FLAG_READ_ZLIB / _ZSTD) through the launchers of deflate.hip and zstd.hip; stored streams
 //               by copy_segments likewise -> the verdict (one lane per chunk) -> ONE unfilter launch from the scratch into the
 //               callers' slots (blocks of a chunk with an error are skipped)
 //   compress    in_len read back -> rows -> ONE filter launch into the scratch (transposed blocks only) -> the engine over all
@@ -21,7 +22,8 @@ struct BlCount { uint32_t nstr, ndir, nblk, nbytes, scratch, maxlen, tiles, form
 // one row per chunk: where its streams (scratch / direct), filter blocks and scratch begin (host prefix sums)
 struct BlChunk { uint64_t strm0, dstrm0, blk0, slot0, cslot0; int64_t err; uint32_t nstr, ndir, nblk, nbytes; };
 // the per-stream rows: the engine's batch and the stored streams' copy_segments rows; rows [0, na) are the scratch streams of all
-// chunks, [na, na + nd) the direct ones; in either range the streams of LZ4 chunks come first, those of BloscLZ chunks behind them
+// chunks, behind them the direct ones; either half is ordered by format — LZ4 | BloscLZ | Zlib | Zstd (bl_class) —, and the streams of
+// a chunk, which all have its one format, lie together
 struct BlRows { BatchRows b; uint64_t *cp_src, *cp_dst, *cp_len; };
 constexpr size_t kBlRowWords = 8;
 inline BlRows bl_rows(uint64_t* base, size_t ns) {
@@ -29,6 +31,12 @@ inline BlRows bl_rows(uint64_t* base, size_t ns) {
     r.b = batch_rows(base, ns);
     r.cp_src = r.b.end; r.cp_dst = r.b.end + ns; r.cp_len = r.b.end + 2 * ns;
     return r;
+}
+
+// the row range of a chunk's streams by its compressor format: 0 LZ4 (and every chunk without streams), 1 BloscLZ, 2 Zlib, 3 Zstd
+constexpr int kBlClasses = 4;
+inline int bl_class(uint32_t format) {
+    return format == kBloscFormatBlosclz ? 1 : format == kBloscFormatZlib ? 2 : format == kBloscFormatZstd ? 3 : 0;
 }
 
 constexpr uint32_t kMemcpyPiece = 1u << 20;          // a memcpyed chunk goes through the filter launch as copy rows of this size
@@ -217,8 +225,9 @@ using cj::BlCount;
 inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
 inline dim3 per_lane(size_t n) { return dim3((uint32_t)((n + cj::kBlockThreads - 1) / cj::kBlockThreads)); }
 
-// flags: 0 or CJ_BLOSC_FLAG_READ_BLOSCLZ (bit 0 stays reserved), the latter for reading only
-bool flags_ok(uint32_t flags, bool reading) { return flags == 0 || (reading && flags == CJ_BLOSC_FLAG_READ_BLOSCLZ); }
+// flags: any subset of CJ_BLOSC_FLAG_READ_BLOSCLZ / _ZLIB / _ZSTD for reading, 0 for writing (bits 0 and 2 and every higher bit stay reserved)
+constexpr uint32_t kReadFlags = CJ_BLOSC_FLAG_READ_BLOSCLZ | CJ_BLOSC_FLAG_READ_ZLIB | CJ_BLOSC_FLAG_READ_ZSTD;
+bool flags_ok(uint32_t flags, bool reading) { return flags == 0 || (reading && (flags & ~kReadFlags) == 0); }
 
 int params_check(cj_op op, const cj_blosc_params* p) {
     if (op == CJ_OP_DECOMPRESS) return 0;
@@ -235,12 +244,15 @@ int run_rows(cj_engine* e, cj_op op, uint32_t flags, const uint8_t* in_base, uin
     return cj::launch(e, CJ_CODEC_LZ4_BLOCK, op, a, s);
 }
 
-// the BloscLZ streams in rows [a0, a0 + k) of r: one wavefront each
-void run_blosclz_rows(const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, size_t a0, size_t k, hipStream_t s) {
-    if (k == 0) return;
+// the streams of one of the other formats (bl_class 1 .. 3) in rows [a0, a0 + k) of r: one wavefront each
+int run_wave_rows(cj_engine* e, int cls, const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, size_t a0, size_t k, hipStream_t s) {
+    if (k == 0) return 0;
     cj::BatchArgs a;
     cj::fill_args(a, 0, in_base, out_base, r.sub(a0, k));
+    if (cls == 2) return cj::launch_zlib_decode(a, s);
+    if (cls == 3) return cj::launch_zstd_decode(e, a, s);           // (takes e->zstd_slots inside this call's e->fb turn: cj_engine.hpp)
     cj::launch_blosclz_decode(a, s);
+    return 0;
 }
 
 int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
@@ -263,20 +275,20 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
         HIP_TRY(hipMemcpyAsync(h_cnt, in_len, 8 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     }
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    // na / nd: scratch / direct streams of LZ4 chunks, za / zd: of BloscLZ chunks (a chunk's streams are all of its one format)
-    uint64_t na = 0, nd = 0, za = 0, zd = 0, nb = 0, slot = 0, cslot = 0;
+    // sa[f] / sd[f]: scratch / direct streams of the chunks of format class f (a chunk's streams are all of its one format)
+    uint64_t sa[cj::kBlClasses] = {}, sd[cj::kBlClasses] = {}, nb = 0, slot = 0, cslot = 0;
     uint32_t maxlen = 0, tiles = 1;
     std::memset(h_tab, 0, n * sizeof(BlChunk));
-    const auto blosclz = [&](size_t i) { return dec && reinterpret_cast<const BlCount*>(h_cnt)[i].format == cj::kBloscFormatBlosclz; };
+    const auto cls = [&](size_t i) { return dec ? cj::bl_class(reinterpret_cast<const BlCount*>(h_cnt)[i].format) : 0; };
     for (size_t i = 0; i < n; i++) {
         BlChunk& c = h_tab[i];
-        const bool z = blosclz(i);
-        c.strm0 = z ? za : na; c.dstrm0 = z ? zd : nd; c.blk0 = nb; c.slot0 = slot; c.cslot0 = cslot;
+        const int z = cls(i);
+        c.strm0 = sa[z]; c.dstrm0 = sd[z]; c.blk0 = nb; c.slot0 = slot; c.cslot0 = cslot;
         if (dec) {
             const BlCount& k = reinterpret_cast<const BlCount*>(h_cnt)[i];
             c.err = k.err; c.nstr = k.nstr; c.ndir = k.ndir; c.nblk = k.nblk; c.nbytes = k.nbytes;
             if (k.scratch) slot += up16(k.nbytes);
-            if (!z) maxlen = std::max(maxlen, k.maxlen);              // (the engine's size classes are about the LZ4 streams alone)
+            if (z == 0) maxlen = std::max(maxlen, k.maxlen);              // (the engine's size classes are about the LZ4 streams alone)
             tiles = std::max(tiles, k.tiles);
         } else {
             const uint64_t len = reinterpret_cast<const uint64_t*>(h_cnt)[i];
@@ -294,15 +306,15 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
             if (c.nblk) { slot += up16(c.nbytes); tiles = std::max(tiles, cj::blosc_tiles(params->typesize, l.blocksize)); }
             cslot += (uint64_t)full * per * cj::bl_enc_room(l.blocksize / per) + (rest ? cj::bl_enc_room(rest) : 0);
         }
-        (z ? za : na) += c.nstr; (z ? zd : nd) += c.ndir; nb += c.nblk;
+        sa[z] += c.nstr; sd[z] += c.ndir; nb += c.nblk;
     }
-    const uint64_t ns = na + za + nd + zd;
+    // rows: scratch LZ4 | BloscLZ | Zlib | Zstd, then direct LZ4 | BloscLZ | Zlib | Zstd; a0[f] / d0[f]: where class f begins in either half
+    uint64_t a0[cj::kBlClasses], d0[cj::kBlClasses], ta = 0, td = 0;
+    for (int f = 0; f < cj::kBlClasses; f++) { a0[f] = ta; ta += sa[f]; }
+    for (int f = 0; f < cj::kBlClasses; f++) { d0[f] = ta + td; td += sd[f]; }
+    const uint64_t ns = ta + td;
     if (ns > 0xFFFFFFF0ull || nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    // rows: scratch LZ4 | scratch BloscLZ | direct LZ4 | direct BloscLZ
-    for (size_t i = 0; i < n; i++) {
-        const bool z = blosclz(i);
-        h_tab[i].strm0 += z ? na : 0; h_tab[i].dstrm0 += na + za + (z ? nd : 0);
-    }
+    for (size_t i = 0; i < n; i++) { h_tab[i].strm0 += a0[cls(i)]; h_tab[i].dstrm0 += d0[cls(i)]; }
     // d_fb: chunk table | stream rows | block rows | scratch (the filtered images of chunks with transposed blocks) | compressed slots (compress)
     const size_t o_rows = tab, o_blocks = o_rows + cj::kBlRowWords * 8 * ns, o_scr = up16(o_blocks + nb * sizeof(cj::BloscBlockRow));
     const size_t o_packed = o_scr + slot + 16;
@@ -319,20 +331,21 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
                            (BlCount*)nullptr, (const BlChunk*)d_tab, r, blocks, scratch, rflags);
         const uint32_t flags = maxlen <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : maxlen <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : maxlen > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
         // streams of transposed blocks into the scratch, the others straight into the callers' slots
-        const uint64_t ta = na + za;                                        // all scratch streams
-        if ((rc = run_rows(e, op, flags, in_base, scratch, r.b, 0, na, s)) != 0) return rc;
-        if ((rc = run_rows(e, op, flags, in_base, out_base, r.b, ta, nd, s)) != 0) return rc;
-        run_blosclz_rows(in_base, scratch, r.b, na, za, s);
-        run_blosclz_rows(in_base, out_base, r.b, ta + nd, zd, s);
+        if ((rc = run_rows(e, op, flags, in_base, scratch, r.b, a0[0], sa[0], s)) != 0) return rc;
+        if ((rc = run_rows(e, op, flags, in_base, out_base, r.b, d0[0], sd[0], s)) != 0) return rc;
+        for (int f = 1; f < cj::kBlClasses; f++) {
+            if ((rc = run_wave_rows(e, f, in_base, scratch, r.b, a0[f], sa[f], s)) != 0) return rc;
+            if ((rc = run_wave_rows(e, f, in_base, out_base, r.b, d0[f], sd[f], s)) != 0) return rc;
+        }
         cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)ta, s);
-        cj::launch_copy_segments(r.cp_src + ta, out_base, r.cp_dst + ta, r.cp_len + ta, nullptr, 0, (uint32_t)(nd + zd), s);
+        cj::launch_copy_segments(r.cp_src + ta, out_base, r.cp_dst + ta, r.cp_len + ta, nullptr, 0, (uint32_t)td, s);
         hipLaunchKernelGGL(cj::bl_verdict_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, r, result);
         cj::launch_blosc_filter(blocks, nb, tiles, false, result, s);
     } else {
         hipLaunchKernelGGL(cj::bl_pieces_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, in_base, in_off, *params, r.b, blocks, scratch);
         cj::launch_blosc_filter(blocks, nb, tiles, true, nullptr, s);
-        if ((rc = run_rows(e, op, 0, scratch, packed, r.b, 0, na, s)) != 0) return rc;
-        if ((rc = run_rows(e, op, 0, in_base, packed, r.b, na, nd, s)) != 0) return rc;
+        if ((rc = run_rows(e, op, 0, scratch, packed, r.b, 0, sa[0], s)) != 0) return rc;
+        if ((rc = run_rows(e, op, 0, in_base, packed, r.b, sa[0], sd[0], s)) != 0) return rc;
         hipLaunchKernelGGL(cj::bl_assemble_kernel, dim3((uint32_t)((n + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock)), dim3(cj::kBlockThreads), 0, s,
                            (uint32_t)n, (const BlChunk*)d_tab, *params, r.b, in_base, in_off, scratch, packed, out_base, out_off, out_cap, result);
     }

@@ -33,4 +33,13 @@ void launch_blosc_filter(const BloscBlockRow* rows, size_t n_rows, uint32_t tile
 // CJ_E_CORRUPT; a row with out_cap == 0 is skipped (result 0).  Nothing is written beyond out_off + out_cap.  Enqueue only.
 void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
 
+// The streams of Zlib / Zstd chunks (CJ_BLOSC_FLAG_READ_ZLIB / _ZSTD), one wavefront per row of a, by the decoders of the plain batches:
+// result = the decoded length (good iff it is out_cap) or a CJ_E_DEFLATE_* / CJ_E_ZSTD_* code.  A row of a stored stream (in_len and
+// out_cap 0) reads and writes nothing; its result (0 or a code) is not looked at.  Both decoders check every store against
+// out_off + out_cap (the wave-decoder contract).  0 or CJ_E_*; enqueue only.
+// deflate.hip: deflate_launch for CJ_DEFLATE_ZLIB, not in size mode
+int launch_zlib_decode(const BatchArgs& a, hipStream_t s);
+// zstd.hip: the decode of cj_zstd_batch_device — its own cj::ScratchTurn on e->zstd_slots, slices by the literal-slot budget
+int launch_zstd_decode(::cj_engine* e, const BatchArgs& a, hipStream_t s);
+
 }  // namespace cj

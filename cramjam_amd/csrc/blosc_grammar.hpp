@@ -1,16 +1,16 @@
 // blosc_grammar.hpp — the grammar of a Blosc1-format chunk (c-blosc 1.x, format version 2: 16-byte header) whose compressor format
-// is LZ4 (or, where the caller's flags ask for it, BloscLZ), for the host (one chunk per call, cj_blosc_chunk_info) and the device (blosc_batch.hip: one lane per chunk).  The walk checks
+// is LZ4 (or, where the caller's flags ask for it, BloscLZ, Zlib or Zstd), for the host (one chunk per call, cj_blosc_chunk_info) and the device (blosc_batch.hip: one lane per chunk).  The walk checks
 // the header and the block table, reports every stream to a visitor and returns 0 or the first error.  Format rules only: no staging,
 // no decoding, no filters.  Every read stays inside [chunk, chunk + in_len).  Not part of the C-ABI.
 //
 //   header   version = 2 | versionlz | flags | typesize | nbytes u32 | blocksize u32 | cbytes u32            (little endian)
 //   flags    0x01 byte shuffle, 0x02 memcpyed, 0x04 bitshuffle, 0x10 blocks are not split, bits 5..7 compressor format (1 = LZ4,
-//            0 = BloscLZ: read only with CJ_BLOSC_FLAG_READ_BLOSCLZ in the caller's flags)
+//            0 = BloscLZ, 3 = Zlib, 4 = Zstd: each read only with its CJ_BLOSC_FLAG_READ_* in the caller's flags; 2 = Snappy: never)
 //   memcpyed nbytes raw bytes behind the header
 //   else     nblocks = ceil(nbytes / blocksize) u32 bstarts (from the chunk's start); block = nsplits streams of i32 cbytes + payload;
 //            nsplits = typesize iff 0x10 is clear and the block is not the leftover block (nbytes % blocksize != 0: the last one),
 //            else 1; a stream decodes to block_bytes / nsplits bytes: stored raw when its cbytes says exactly that, else one LZ4 block
-//            (one BloscLZ stream: blosclz_decode.hip)
+//            (one BloscLZ stream: blosclz_decode.hip; one zlib stream: deflate.hip; one ZSTD_decompress input: zstd.hip)
 // The 32-byte header of C-Blosc2 (format version > 2) is refused, not guessed at: DESIGN.md §5.10.
 #pragma once
 #include "frame_grammar.hpp"
@@ -20,7 +20,7 @@ namespace cj {
 constexpr uint32_t kBloscHeader = 16;
 constexpr uint32_t kBloscMaxBytes = 0x7FFFFFFFu - 16u;     // BLOSC_MAX_BUFFERSIZE
 constexpr uint32_t kBloscShuffle = 1, kBloscMemcpyed = 2, kBloscBitshuffle = 4, kBloscReserved = 8, kBloscNoSplit = 16;
-constexpr uint32_t kBloscFormatBlosclz = 0, kBloscFormatLz4 = 1;
+constexpr uint32_t kBloscFormatBlosclz = 0, kBloscFormatLz4 = 1, kBloscFormatSnappy = 2, kBloscFormatZlib = 3, kBloscFormatZstd = 4;
 
 struct BloscHeader {
     uint32_t version, versionlz, flags, typesize, nbytes, blocksize, cbytes;
@@ -57,7 +57,7 @@ CJ_HD inline uint64_t blosc_tr8(uint64_t x) {
 }
 
 // header checks alone: 0, CJ_E_BLOSC_HEADER or CJ_E_BLOSC_UNSUPPORTED.  The ORDER of the checks is relied on outside this file:
-// cramjam_amd/blosc2.py _info_nbytes sizes the output of a BloscLZ chunk from cj_blosc_chunk_info (which passes no flags) by taking
+// cramjam_amd/blosc2.py _info_nbytes sizes the output of a BloscLZ, Zlib or Zstd chunk from cj_blosc_chunk_info (which passes no flags) by taking
 // back exactly the compressor-format refusal below, the last check before the block table's — keep the two together.  read_flags: the caller's flags word (CJ_BLOSC_FLAG_*; 0 = the
 // default reading: LZ4 streams only)
 CJ_HD inline int64_t blosc_header(const uint8_t* in, size_t in_len, BloscHeader& h, uint32_t read_flags = 0) {
@@ -74,8 +74,10 @@ CJ_HD inline int64_t blosc_header(const uint8_t* in, size_t in_len, BloscHeader&
     if (h.nbytes == 0) return 0;                                           // (an empty chunk: nothing else is looked at)
     if (h.blocksize == 0 || h.blocksize > h.nbytes) return CJ_E_BLOSC_HEADER;
     if (h.flags & kBloscMemcpyed) return h.cbytes == h.nbytes + kBloscHeader ? 0 : (int64_t)CJ_E_BLOSC_HEADER;
-    const bool blosclz = (read_flags & CJ_BLOSC_FLAG_READ_BLOSCLZ) && (h.flags >> 5) == kBloscFormatBlosclz;
-    if (((h.flags >> 5) != kBloscFormatLz4 && !blosclz) || h.versionlz != 1) return CJ_E_BLOSC_UNSUPPORTED;     // BloscLZ 0, Snappy 2, Zlib 3, Zstd 4
+    const uint32_t fmt = h.flags >> 5;
+    const bool opted = (fmt == kBloscFormatBlosclz && (read_flags & CJ_BLOSC_FLAG_READ_BLOSCLZ)) || (fmt == kBloscFormatZlib && (read_flags & CJ_BLOSC_FLAG_READ_ZLIB)) ||
+                       (fmt == kBloscFormatZstd && (read_flags & CJ_BLOSC_FLAG_READ_ZSTD));
+    if ((fmt != kBloscFormatLz4 && !opted) || h.versionlz != 1) return CJ_E_BLOSC_UNSUPPORTED;     // BloscLZ 0, Snappy 2, Zlib 3, Zstd 4
     h.format = h.flags >> 5;
     const uint64_t nblocks = ((uint64_t)h.nbytes + h.blocksize - 1) / h.blocksize;
     if (kBloscHeader + 4 * nblocks > h.cbytes) return CJ_E_BLOSC_HEADER;

@@ -133,6 +133,9 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 
 }  // namespace cj
 
+// LOCK ORDER of the engine's mutexes: e->mu -> fb -> zstd_slots.  A host batch stages under `mu` and takes the scratches inside it; a
+// Blosc batch holds its `fb` turn while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the streams of Zstd
+// chunks.  No path takes two of them the other way round; the other scratches are taken alone or under `mu` only.
 struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
     int device = 0;
     cj::Stream stream;

@@ -6,6 +6,7 @@
 // the same decoder without stores and uses no scratch.  The device calls only enqueue (a decode that grows the slots waits for their
 // previous user while it reallocates).
 #include "wave_lanes.hpp"
+#include "blosc_filters.hpp"      // (declares launch_zstd_decode)
 
 #include <atomic>
 
@@ -51,7 +52,8 @@ int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const
     return 0;
 }
 
-// One turn at the engine's literal slots (cj::ScratchTurn); enqueue only
+// One turn at the engine's literal slots (cj::ScratchTurn); enqueue only.  A caller may hold the e->fb turn (blosc_batch.hip), never
+// the other way round: the lock order is written down where cj_engine declares the scratches
 int decode_device(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                   const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     const uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kZsSlotBytes);
@@ -66,6 +68,11 @@ int decode_device(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t
 }
 
 }  // namespace
+
+int cj::launch_zstd_decode(cj_engine* e, const cj::BatchArgs& a, hipStream_t s) {
+    if (a.n_chunks == 0) return 0;
+    return decode_device(e, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
+}
 
 extern "C" {
 

@@ -505,16 +505,22 @@ CJ_API size_t cj_zstd_compress_bound(size_t n, uint32_t flags);
  *            FastLZ family decoded by one wavefront (blosclz_decode.hip; the stream rules of c-blosc 1.21's blosclz_decompress).  One
  *            batch may mix LZ4 and BloscLZ chunks.  Without the flag (the default) such a chunk is refused as before.  BloscLZ is
  *            never written.
+ *            With CJ_BLOSC_FLAG_READ_ZLIB / CJ_BLOSC_FLAG_READ_ZSTD also chunks whose compressor format is Zlib (format 3) / Zstd
+ *            (format 4), versionlz 1 (c-blosc's cname "zlib" / "zstd": what most archival Zarr stores hold).  The container is the
+ *            same; each stream that is not stored is one zlib-wrapped DEFLATE stream (CJ_DEFLATE_ZLIB, deflate.hip) / what one
+ *            ZSTD_decompress call reads (zstd.hip), and is good iff it decodes to exactly its length: whatever CJ_E_DEFLATE_* /
+ *            CJ_E_ZSTD_* code a stream produced, the chunk's result is CJ_E_CORRUPT.  One batch may mix all four formats.  Neither
+ *            format is written.
  *   WRITTEN  the same format: blocks of 64 KiB x typesize split into typesize streams for typesize 2 .. 16 (else 64 KiB unsplit,
  *            flag 0x10), every stream at most 64 KiB; a stream that does not shrink is stored, a chunk that would not be smaller than
  *            nbytes + 16 (and every clevel 0 chunk) is memcpyed.  clevel 1 .. 9 select the one matcher of cj_batch_device.
  *   REFUSED  CJ_E_BLOSC_UNSUPPORTED: a format version other than 2 — above all C-Blosc2's extended 32-byte header (version > 2, with its
  *            filter pipeline: delta, truncated precision); nothing that writes such a chunk was at hand when this was built, so there is
- *            no decoder guessed from memory — and the compressor formats BloscLZ (unless the flag above is set), Snappy, Zlib, Zstd (on compress: any codec but
+ *            no decoder guessed from memory — and the compressor formats BloscLZ, Zlib, Zstd (each unless its flag above is set) and Snappy (always; on compress: any codec but
  *            CJ_BLOSC_LZ4 / CJ_BLOSC_LZ4HC, any filter but the three above).
  *            CJ_E_BLOSC_HEADER: a malformed container (short header, reserved flag, both shuffle bits, typesize 0, cbytes beyond the
  *            bytes given, blocksize 0 or above nbytes, a block start or stream word outside the chunk).
- *            CJ_E_CORRUPT: a stream that is not an LZ4 block (a BloscLZ stream) of exactly its length.  CJ_E_OUT_TOO_SMALL: nbytes above the capacity.
+ *            CJ_E_CORRUPT: a stream that is not an LZ4 block (a BloscLZ stream, a zlib stream, a Zstandard frame) of exactly its length.  CJ_E_OUT_TOO_SMALL: nbytes above the capacity.
  *            A chunk refused for its header or its size writes nothing; one with a bad stream may have written inside its own slot.
  * ===================================================================================== */
 typedef enum { CJ_BLOSC_NOFILTER = 0, CJ_BLOSC_SHUFFLE = 1, CJ_BLOSC_BITSHUFFLE = 2 } cj_blosc_filter;      /* the reference's Filter */
@@ -527,15 +533,17 @@ typedef struct {
     uint32_t blocksize;   /* 0 = default; a value above the default block size is cut to it */
 } cj_blosc_params;
 typedef struct { uint32_t version, versionlz, flags, typesize, nbytes, blocksize, cbytes, nblocks; } cj_blosc_info;
-/* flags of cj_blosc_batch_device / _host (decompress only) and cj_blosc_chunk_sizes_device / _host.  Bit 0 is reserved; any other
- * non-zero value is CJ_E_BAD_ARG, and so is this one with CJ_OP_COMPRESS. */
+/* flags of cj_blosc_batch_device / _host (decompress only) and cj_blosc_chunk_sizes_device / _host: any subset of the three below.
+ * Bit 0 and bit 2 (value 4) are reserved; they and every higher bit are CJ_E_BAD_ARG, and so is any of these with CJ_OP_COMPRESS. */
 #define CJ_BLOSC_FLAG_READ_BLOSCLZ 2u   /* also read chunks whose streams are BloscLZ */
+#define CJ_BLOSC_FLAG_READ_ZLIB 8u      /* ... whose streams are zlib streams (compressor format 3) */
+#define CJ_BLOSC_FLAG_READ_ZSTD 16u     /* ... whose streams are Zstandard frames (compressor format 4) */
 
 /* src/blosc2.rs:702  upper bound of a chunk of n bytes: n + 32 (this library needs n + 16: the memcpyed chunk). No device. */
 CJ_API size_t cj_blosc_chunk_max_compressed_len(size_t n);
 /* the header of a chunk after its checks (0, CJ_E_BLOSC_HEADER or CJ_E_BLOSC_UNSUPPORTED; info is filled from the 16 bytes whenever
- * there are that many).  It takes no flags and reports the default reading: a BloscLZ chunk is CJ_E_BLOSC_UNSUPPORTED here (info is
- * still filled: flags >> 5 == 0 and versionlz == 1 name such a chunk).  No device. */
+ * there are that many).  It takes no flags and reports the default reading: a BloscLZ, Zlib or Zstd chunk is CJ_E_BLOSC_UNSUPPORTED here
+ * (info is still filled: flags >> 5 == 0 / 3 / 4 and versionlz == 1 name such a chunk).  No device. */
 CJ_API int64_t cj_blosc_chunk_info(const uint8_t* in, size_t n, cj_blosc_info* info);
 /* src/blosc2.rs:143,153  decompress_chunk / decompress_chunk_into: returns nbytes */
 CJ_API int64_t cj_blosc_chunk_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap);
@@ -544,14 +552,14 @@ CJ_API int64_t cj_blosc_chunk_compress(const uint8_t* in, size_t n, uint8_t* out
 /* Batches of chunks, device-resident or on the host: addressing, alignment, stream rules and the one wait of cj_frame_batch_device /
  * _host (decompress reads back the chunks' stream counts, compress in_len).  result[i] = nbytes (decompress) / the chunk's size
  * (compress) or CJ_E_*; nothing is written outside out_off[i] .. + out_cap[i] (a chunk with a header or size error writes nothing at all).  params:
- * compress only (one set for the batch); flags: 0 or CJ_BLOSC_FLAG_READ_BLOSCLZ (decompress only).  e == NULL: the default engine of device 0. */
+ * compress only (one set for the batch); flags: 0 or CJ_BLOSC_FLAG_READ_* (decompress only).  e == NULL: the default engine of device 0. */
 CJ_API int cj_blosc_batch_device(cj_engine* e, cj_op op, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                                  uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, size_t n_chunks,
                                  const cj_blosc_params* params, uint32_t flags, void* hip_stream);
 CJ_API int cj_blosc_batch_host(cj_engine* e, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* const* in_ptrs, const size_t* in_lens,
                                uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result, const cj_blosc_params* params);
 /* result[i] = nbytes of chunk i after the header checks of cj_blosc_chunk_info, or their error; flags as above (with
- * CJ_BLOSC_FLAG_READ_BLOSCLZ a BloscLZ chunk reports its nbytes).  Enqueue-only like cj_batch_sizes_device. */
+ * its CJ_BLOSC_FLAG_READ_* flag a BloscLZ, Zlib or Zstd chunk reports its nbytes).  Enqueue-only like cj_batch_sizes_device. */
 CJ_API int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                                        const uint64_t* in_len, int64_t* result, void* hip_stream);
 CJ_API int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n_chunks, const uint8_t* const* in_ptrs, const size_t* in_lens,
