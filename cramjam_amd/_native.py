@@ -95,6 +95,11 @@ SYMBOLS = {
     "cj_deflate_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_deflate_compress_bound": (_sz, [_sz, _int]),
+    "cj_bgzf_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_bgzf_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_bgzf_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_bgzf_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_bgzf_compress_bound": (_sz, [_sz]),
     "cj_zstd_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_bound": (_sz, [_sz, _u32]),
@@ -128,6 +133,7 @@ BENCH_SYMBOLS = {
     "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_bgzf_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_enc_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_grid_chunks": (C.c_uint64, [C.c_uint64]),
@@ -210,8 +216,9 @@ DEFLATE = Kind("cj_deflate_batch_host", "cj_deflate_batch_device", "cj_deflate_b
 DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_batch_device", None, None, one_op=True)      # what = a DEFLATE_*; no size query
 ZSTD = Kind("cj_zstd_batch_host", "cj_zstd_batch_device", "cj_zstd_batch_sizes_host", "cj_zstd_batch_sizes_device")   # what = ZSTD_FRAMES
 ZSTD_COMPRESS = Kind("cj_zstd_compress_batch_host", "cj_zstd_compress_batch_device", None, None, one_op=True)      # what = ZSTD_FRAMES; no size query
+BGZF = Kind("cj_bgzf_batch_host", "cj_bgzf_batch_device", "cj_bgzf_sizes_host", "cj_bgzf_sizes_device")   # what = 0; both directions
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
-_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BLOSC)}
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BGZF, BLOSC)}
 
 
 class Engine:

@@ -641,6 +641,59 @@ def deflate_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, wra
     return _device_batch(N.DEFLATE_COMPRESS, _deflate_wrap(wrapper), N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
 
 
+# ---- BGZF streams (cj_bgzf_batch_* / cj_bgzf_sizes_* / cj_bgzf_compress_bound): blocked gzip, both directions ----------
+# One entry is a whole stream of any size — a BAM, BCF or `bgzip` file: gzip members of at most 64 KiB that state their own length, so
+# every member of every stream is decoded (encoded) on its own.  result[i] = the decoded (the stream's) length or a negative CJ_E_*
+# code: -43 / -41 from the walk over the members' heads (truncated; not BGZF — bytes behind the last member, zero padding too), then
+# -6 when the members' ISIZE sum exceeds the capacity, then the first bad member's code in stream order (-40, -42, ...).
+def bgzf_sizes(streams, devices=None):
+    """decoded sizes of many BGZF streams held on the host (list of ints; negative = CJ_E_* code): the sum of the members' ISIZE fields
+    from the walk alone — claims read from the trailers, verified only by the decode"""
+    return _host_sizes(N.BGZF, 0, 0, streams, devices)
+
+
+def bgzf_decompress_many(streams, output_lens=None, devices=None, out=None):
+    """decode many BGZF streams, member-parallel; returns (results, outputs) as lz4_decompress_blocks.  output_lens=None: the sizes are
+    asked for first (bgzf_sizes; the input then crosses the link twice): a stream the walk rejects gets the walk's code as its result
+    and an empty output."""
+    run = lambda caps: _run(0, N.OP_DECOMPRESS, 0, streams, caps, devices, out, N.BGZF)
+    if output_lens is not None:
+        return run(output_lens)
+    return _sizes_first(bgzf_sizes(streams, devices), run)
+
+
+def bgzf_decompress_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of BGZF streams (arguments as lz4_decompress_frames_device; the call waits for the stream once, for
+    the streams' member counts)."""
+    return _device_batch(N.BGZF, 0, N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def bgzf_sizes_device(inp, in_off, in_len, result=None, device=None, stream=None, sync=True):
+    """Decoded sizes of a device-resident batch of BGZF streams, as bgzf_sizes; enqueue-only like lz4_block_sizes_device."""
+    return _device_sizes(N.BGZF, 0, 0, inp, in_off, in_len, result, device, stream, sync)
+
+
+def bgzf_compress_bound(n):
+    """the capacity that always suffices for a buffer of n bytes (the members' worst cases and the end-of-file marker; 0 above
+    0x7E000000).  No device."""
+    return N.lib().cj_bgzf_compress_bound(n)
+
+
+def bgzf_compress_many(buffers, devices=None, out=None):
+    """one BGZF stream per buffer — members of 65 280 input bytes, then the end-of-file marker: what bgzf_decompress_many, htslib and
+    gzip.decompress read; returns (results, outputs) as lz4_compress_blocks.  out: as in lz4_decompress_blocks; it has to hold
+    sum(bgzf_compress_bound(len(buffer))) bytes."""
+    L = N.lib()
+    caps = [L.cj_bgzf_compress_bound(memoryview(b).nbytes) for b in buffers]
+    return _run(0, N.OP_COMPRESS, 0, buffers, caps, devices, out, N.BGZF)
+
+
+def bgzf_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, result=None, device=None, stream=None, sync=True):
+    """Compress a device-resident batch into BGZF streams (arguments as lz4_compress_frames_device; the call waits for the stream once,
+    for the buffers' lengths); out_cap[i] >= bgzf_compress_bound(in_len[i]) always suffices."""
+    return _device_batch(N.BGZF, 0, N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
 # ---- ... and into Zstandard frames (cj_zstd_compress_batch_* / cj_zstd_compress_bound; DESIGN.md 5.15) --------------------------------
 # One frame per buffer: independent pieces of at most 64 KiB, each one RLE, Compressed or Raw block.  result[i] = the frame's length
 # or a negative CJ_E_* code (-6: the capacity is too small; -1: a buffer above 0x7E000000 bytes).

@@ -39,6 +39,8 @@ void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
 // out_off + out_cap (the wave-decoder contract).  0 or CJ_E_*; enqueue only.
 // deflate.hip: deflate_launch for CJ_DEFLATE_ZLIB, not in size mode
 int launch_zlib_decode(const BatchArgs& a, hipStream_t s);
+// ... for CJ_DEFLATE_GZIP: the members of BGZF streams (bgzf_batch.hip), one row each
+int launch_gzip_decode(const BatchArgs& a, hipStream_t s);
 // zstd.hip: the decode of cj_zstd_batch_device — its own cj::ScratchTurn on e->zstd_slots, slices by the literal-slot budget
 int launch_zstd_decode(::cj_engine* e, const BatchArgs& a, hipStream_t s);
 

@@ -133,9 +133,10 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 
 }  // namespace cj
 
-// LOCK ORDER of the engine's mutexes: e->mu -> fb -> zstd_slots.  A host batch stages under `mu` and takes the scratches inside it; a
-// Blosc batch holds its `fb` turn while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the streams of Zstd
-// chunks.  No path takes two of them the other way round; the other scratches are taken alone or under `mu` only.
+// LOCK ORDER of the engine's mutexes: e->mu -> fb -> zstd_slots / deflate_slots.  A host batch stages under `mu` and takes the
+// scratches inside it; a Blosc batch holds its `fb` turn while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for
+// the streams of Zstd chunks, a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for
+// its members.  No path takes two of them the other way round; the other scratches are taken alone or under `mu` only.
 struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
     int device = 0;
     cj::Stream stream;
@@ -157,7 +158,7 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     int big_next = 0;
     cj::DevBuf d_big, d_bigtab;    // large.hip: parse scratch / record tables of one large stream (under `mu`)
     int n_cu = 0;
-    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip: batches of framed streams / Blosc chunks — frame table, block rows and decode slots, its staging
+    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip, bgzf_batch.hip: batches of framed streams / Blosc chunks / BGZF streams — frame table, block rows and decode slots, its staging
     cj::DevBuf d_fb;
     cj::PinnedBuf h_fb;
     cj::Scratch dict_stage;        // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows

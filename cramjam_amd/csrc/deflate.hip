@@ -5,7 +5,7 @@
 // 4 KiB of CRC-32 tables), and the launches.  The size query is the same decoder with stores and checksums compiled out.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock.
 #include "wave_lanes.hpp"
-#include "blosc_filters.hpp"      // (declares launch_zlib_decode)
+#include "blosc_filters.hpp"      // (declares launch_zlib_decode, launch_gzip_decode)
 #include "deflate_wave.hpp"
 
 namespace cj {
@@ -65,6 +65,11 @@ int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const 
 int cj::launch_zlib_decode(const cj::BatchArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return 0;
     return deflate_launch(CJ_DEFLATE_ZLIB, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
+}
+
+int cj::launch_gzip_decode(const cj::BatchArgs& a, hipStream_t s) {
+    if (a.n_chunks == 0) return 0;
+    return deflate_launch(CJ_DEFLATE_GZIP, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
 }
 
 extern "C" {

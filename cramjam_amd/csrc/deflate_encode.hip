@@ -159,11 +159,13 @@ int resident_per_cu(int wrap) {
     return v;
 }
 
+}  // namespace
+
 // One turn at the engine's record slots (cj::ScratchTurn); enqueue only.  A slice is what the device holds at once — a launch of more
 // workgroups than that ends in a tail of a few of them (gzip, four per CU, on synth-v1: 25.7 GB/s in slices of 1280, 37.8 in slices of 1024) —
-// within the budget.
-int compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                    const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
+// within the budget.  (Declared in cj_stage.hpp: the BGZF batch runs its members through it.)
+int cj::deflate_compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+                                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
     uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kDfeSlotBytes);
     const uint64_t resident = (uint64_t)resident_per_cu(wrap) * (uint64_t)e->n_cu;
@@ -181,8 +183,6 @@ int compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, co
     return turn.done(s);
 }
 
-}  // namespace
-
 extern "C" {
 
 size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap) {
@@ -195,7 +195,7 @@ int cj_deflate_compress_batch_device(cj_engine* e, cj_deflate_wrap wrap, uint32_
                                      void* hip_stream) {
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        return cj::deflate_compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
     });
 }
 
@@ -204,7 +204,7 @@ int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t 
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return compress_device(e, (int)wrap, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        return cj::deflate_compress_device(e, (int)wrap, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }
 

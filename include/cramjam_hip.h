@@ -421,6 +421,56 @@ CJ_API int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, ui
                                           uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
 CJ_API size_t cj_deflate_compress_bound(size_t n, cj_deflate_wrap wrap);
 
+/* Batches of BGZF streams, both directions: the blocked gzip of the SAM specification (4.1) — BAM, BCF, tabix-indexed
+ * VCF, every `bgzip` file.  A stream is zero or more RFC 1952 gzip members of at most 64 KiB laid end to end with nothing between or
+ * behind them; each has FEXTRA set and, among its extra subfields, one `BC` subfield of two bytes: BSIZE, the member's length - 1 (the
+ * first one counts; other subfields, FNAME, FCOMMENT and FHCRC are walked).  The members are found without decoding, so one entry of
+ * these batches is a whole stream of any size and every member of every stream is decoded (encoded) by a wavefront (workgroup) of its
+ * own.  The end-of-file marker, an empty member of 28 bytes, is not required and decodes to nothing, like an empty member anywhere.
+ * The argument shape is cj_frame_batch_*'s; addressing, the 16-byte-granule rule, stream rules, e == NULL, n_streams == 0 and the
+ * null-pointer rules are cj_deflate_batch_*'s.
+ *   what        0; anything else is CJ_E_BAD_ARG.      flags   0; any bit set is CJ_E_BAD_ARG.
+ *   op          CJ_OP_DECOMPRESS or CJ_OP_COMPRESS; anything else is CJ_E_BAD_ARG.  These checks come first and need no device.
+ *   decompress  result[i] = the decoded length, the sum of the members' ISIZE, or CJ_E_*.  The walk's errors come first, at the first
+ *               member in stream order that has one: CJ_E_DEFLATE_EOF — fewer than 12 bytes, or than 12 + XLEN, are left, or the
+ *               member runs past the input's end; CJ_E_DEFLATE_HEADER — a bad magic, CM != 8, FEXTRA clear, a subfield that runs
+ *               past XLEN, no BC subfield of two bytes, a BSIZE without room for an empty block and the trailer.  Bytes behind the
+ *               last member fail these checks: zero padding, which other gzip readers tolerate, is an error here.  Then
+ *               CJ_E_OUT_TOO_SMALL when the ISIZE sum exceeds out_cap[i].  A stream refused so far is not decoded and its slot is not
+ *               written.  Every member then decodes into its own ISIZE bytes of the slot, behind those of the members before it, by
+ *               cj_deflate_batch_*'s rules for CJ_DEFLATE_GZIP; the stream's result is the code of the first failing member in stream
+ *               order, a member that holds more than its ISIZE says being CJ_E_DEFLATE_CHECKSUM (zlib's "incorrect length check").
+ *               A stream with a bad member may have written inside its own slot, never outside it; one bad stream never affects
+ *               another.
+ *   sizes       cj_bgzf_sizes_*: the walk alone — result[i] = the ISIZE sum or the walk's error.  The sizes are CLAIMS read from the
+ *               members' trailers: only the decode verifies them (and the checksums).
+ *   compress    one stream per buffer: members of 65 280 input bytes (htslib's block size), the last one shorter, then the marker;
+ *               an empty buffer gives the marker alone.  A member is the 18-byte header 1f 8b 08 04, MTIME 0, XFL 0, OS 255, XLEN 6,
+ *               `BC` 2 0 BSIZE, then exactly the DEFLATE block, CRC-32 and ISIZE that cj_deflate_compress_batch_* writes for that
+ *               piece.  The bytes depend on nothing but the input.  result[i] = the stream's length; CJ_E_INPUT_TOO_LARGE for
+ *               in_len[i] > 0x7E000000; CJ_E_OUT_TOO_SMALL when the stream does not fit out_cap[i] — decided before the first store:
+ *               a stream that fails writes nothing.
+ *   bound       cj_bgzf_compress_bound(n): the members' worst cases (65 311 bytes for a full one, r + 31 for a last one of r bytes)
+ *               plus the marker's 28; a capacity of that many bytes never gives CJ_E_OUT_TOO_SMALL.  0 for n > 0x7E000000.  Pure
+ *               arithmetic, no device.
+ * The batch calls take one turn at the engine's container scratch and wait for the stream ONCE (decompress: for the streams' member
+ * counts; compress: for the buffers' lengths and capacities), like cj_frame_batch_*; the member encoder's slots are engine scratch
+ * within a fixed budget, a large batch runs in turns.  The size query only enqueues.  The _host calls are cj_batch_host's one-shot
+ * staging, synchronous. */
+CJ_API int cj_bgzf_batch_device(cj_engine* e, int what, cj_op op, uint32_t flags, size_t n_streams,
+                                const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                int64_t* result, void* hip_stream);
+CJ_API int cj_bgzf_batch_host(cj_engine* e, int what, cj_op op, uint32_t flags, size_t n_streams,
+                              const uint8_t* const* in_ptrs, const size_t* in_lens,
+                              uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API int cj_bgzf_sizes_device(cj_engine* e, int what, uint32_t flags, size_t n_streams,
+                                const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                int64_t* result, void* hip_stream);
+CJ_API int cj_bgzf_sizes_host(cj_engine* e, int what, uint32_t flags, size_t n_streams,
+                              const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+CJ_API size_t cj_bgzf_compress_bound(size_t n);
+
 /* Zstandard frames — decode (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
  * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an
  * empty input decoding to 0 bytes.  One wavefront decodes a chunk; result[i] and the bytes are libzstd's (1.4.x).

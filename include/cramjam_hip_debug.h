@@ -44,6 +44,9 @@ CJ_API uint64_t cj_debug_dict_stage_budget(uint64_t bytes);
 /* DEFLATE compress (cj_deflate_compress_batch_*): the bytes of sequence-record slots per slice, one slot of 256.25 KiB per stream in flight
  * (0 = the default, 1280 slots = 320 MiB); returns the previous value.  Tests force more than one slice with it. */
 CJ_API uint64_t cj_debug_deflate_slot_budget(uint64_t bytes);
+/* BGZF compress (cj_bgzf_batch_* with CJ_OP_COMPRESS): the bytes of bound-sized member slots per turn, one slot of 65 312 bytes per member
+ * in flight (0 = the default, 4096 slots); returns the previous value.  Tests force more than one turn with it. */
+CJ_API uint64_t cj_debug_bgzf_slot_budget(uint64_t bytes);
 /* Zstandard decode (cj_zstd_batch_*): the bytes of literal slots per slice, one slot of 128 KiB + 32 per stream in flight (0 = the
  * default); returns the previous value */
 CJ_API uint64_t cj_debug_zstd_slot_budget(uint64_t bytes);
