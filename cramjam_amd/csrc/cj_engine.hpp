@@ -133,10 +133,13 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 
 }  // namespace cj
 
-// LOCK ORDER of the engine's mutexes: e->mu -> fb -> zstd_slots / deflate_slots.  A host batch stages under `mu` and takes the
-// scratches inside it; a Blosc batch holds its `fb` turn while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for
-// the streams of Zstd chunks, a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for
-// its members.  No path takes two of them the other way round; the other scratches are taken alone or under `mu` only.
+// LOCK ORDER of the engine's mutexes: mu -> fb -> {scratch, zstd_slots, deflate_slots}.  A host batch stages under `mu` and takes the
+// scratches inside it.  A frame batch and a Blosc batch hold their `fb` turn while cj::launch takes `scratch` for their LZ4 / Snappy
+// blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
+// streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
+// members, once per turn of member slots.  The three inner ones are taken one after another, never one inside another, and no path
+// takes two of the graph's mutexes the other way round; `dict_stage` and `zstd_enc_slots` are taken alone or under `mu` only.  The table
+// of every entry's turns: DESIGN.md §2; two streams and two threads per scratch: tests/test_scratch_streams_gpu.py.
 struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
     int device = 0;
     cj::Stream stream;

@@ -1,14 +1,16 @@
-"""One turn after another at each of an engine's three scratches (cj::ScratchTurn, csrc/cj_engine.hpp): a small batch A and, with no wait
+"""One turn after another at each of an engine's seven scratches (cj::ScratchTurn, csrc/cj_engine.hpp): a small batch A and, with no wait
 between them, a batch B that makes every buffer of the scratch grow while A may still be in flight — on a FRESH engine, so that the
 scratch starts empty.  Metadata and results are device-resident; the engine is waited for once.  The same two batches on a second fresh
-engine, each waited for, must give the same results and bytes; both are held to the oracle / the encoder's model, with guard bytes around
-every output slot.  Then B, A, B on the first engine: a turn that does not grow, and one that does not shrink.  Closing the engines runs
-their teardown.  Every input is a valid stream."""
+engine, each waited for, must give the same results and bytes; both are held to the oracle / the encoder's model / the recorded
+fixtures, with guard bytes around every output slot.  Then B, A, B on the first engine: a turn that does not grow, and one that does
+not shrink.  Closing the engines runs their teardown.  Every input is a valid stream.  (Two caller streams and two host threads on one
+engine: tests/test_scratch_streams_gpu.py.)"""
 import numpy as np
 import pytest
 
 import lz4_dict_model as D
 import oracle
+import scratch_streams_cases as S
 from cramjam_amd import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -133,11 +135,61 @@ class Dict:
             e.free(p)
 
 
+class FromCall:
+    """the scratches the cases above predate, on the chunks of a call of tests/scratch_streams_cases.py that its reference accepts (at most
+    `largest` bytes of capacity each), `times` times over: chunks(n) -> (inputs, capacities, their Wants)"""
+    A = 4
+
+    def __init__(self, call, kind, what, op, flags=0, times=1, largest=70000, B=None):
+        rows = [(c, cap, w) for c, cap, w in zip(call.chunks, call.caps, call.want) if w.good and cap <= largest] * times
+        self.rows, self.kind, self.what, self.op, self.flags = rows, kind, what, op, flags
+        self.B = B or len(rows)
+        assert self.A < self.B <= len(rows)
+
+    def chunks(self, n):
+        return [r[0] for r in self.rows[:n]], [r[1] for r in self.rows[:n]], [r[2] for r in self.rows[:n]]
+
+    def enqueue(self, e, b):
+        a = b.args()
+        N.check(getattr(N.lib(), self.kind.device)(*self.kind.device_args(e.h, self.what, self.op, self.flags, b.n, a[0:3], a[3:6], a[6], None, None)))
+
+    @staticmethod
+    def held_to(want, res, out, ooff):
+        """chunk i is what want[i] says, and nothing was written outside [slot, slot + result) of any chunk"""
+        keep = np.ones(out.size, bool)
+        for i, (o, w) in enumerate(zip(ooff, want)):
+            r = int(res[i])
+            assert r >= 0 and w.problem(r, out[o:o + r]) is None, (i, w.problem(r, out[o:o + max(r, 0)]))
+            keep[o:o + r] = False
+        assert (out[keep] == FILL).all(), "a write outside a chunk's result"
+
+
+def _small_bgzf_buffers():
+    """BGZF compress: 160 buffers of a few hundred bytes (the staging of the buffers' rows grows with their number) and the call's own
+    buffers of three to five members behind the first three (the member slots grow with the members of a turn)"""
+    import deflate_cases as DC
+    c = S.bgzf_compress()
+    small = [DC.words(200 + 17 * (k % 23), 400 + k) for k in range(160)]
+    bufs = small[:3] + [c.chunks[1]] + small[3:] + [x for x, w in zip(c.chunks, c.want) if w.good]
+    caps = [N.lib().cj_bgzf_compress_bound(len(b)) for b in bufs]
+    want = [S.Want(verify=lambda s, b=b: S._member_payloads_are_the_models(s, b)) for b in bufs]
+    return S.Call("buffers into BGZF streams", "bgzf_compress_many_device", bufs, caps, want)
+
+
 CASES = {
     "workgroup decoder, parse inside the decoder": lambda: Blocks(0),
     "workgroup decoder, parse kernel": lambda: Blocks(N.FLAG_FORCE_PARSE_KERNEL),
     "frame batches": Frames,
     "dictionary staging": Dict,
+    # cj_engine::deflate_slots, ::zstd_slots, ::zstd_enc_slots: one slot per stream in flight, so B's 60 and more streams grow what A's four left
+    "DEFLATE compress": lambda: FromCall(S.deflate_zlib_compress(), N.DEFLATE_COMPRESS, N.DEFLATE_ZLIB, N.OP_COMPRESS),
+    "Zstandard decode": lambda: FromCall(S.zstd_decode(2), N.ZSTD, N.ZSTD_FRAMES, N.OP_DECOMPRESS),
+    "Zstandard compress": lambda: FromCall(S.zstd_compress(0, False), N.ZSTD_COMPRESS, N.ZSTD_FRAMES, N.OP_COMPRESS),
+    # cj_engine::fb through the entries that came after the frame batches: tables and pinned staging by the number of chunks, rows and
+    # data scratch by their streams; the Zstandard launcher (Blosc) and the DEFLATE encoder (BGZF compress) take their turns inside
+    "Blosc chunks, LZ4 streams": lambda: FromCall(S.blosc_lz4_shuffle(), N.BLOSC, 0, N.OP_DECOMPRESS, times=6),
+    "BGZF decode": lambda: FromCall(S.bgzf_decode(), N.BGZF, 0, N.OP_DECOMPRESS, times=8),
+    "BGZF compress": lambda: FromCall(_small_bgzf_buffers(), N.BGZF, 0, N.OP_COMPRESS, largest=1 << 30),
 }
 
 
@@ -168,7 +220,7 @@ def test_a_turn_that_grows_the_scratch_behind_one_in_flight(name):
         for key, x, y, chunks in (("a", a1, a2, a), ("b", b1, b2, b)):
             (rx, ox), (ry, oy) = x.read(), y.read()
             assert (rx == ry).all() and (ox == oy).all(), key
-            _held_to(chunks[2], rx, ox, x.ooff)
+            getattr(case, "held_to", _held_to)(chunks[2], rx, ox, x.ooff)
             ref[key] = (rx, ox)
         # a turn that does not grow, then one that does not shrink
         again = [("b", batch(first, b)), ("a", batch(first, a)), ("b", batch(first, b))]
