@@ -8,7 +8,6 @@
 #include "blosc_filters.hpp"      // (cj_stage.hpp; declares launch_gzip_decode)
 #include "bgzf_grammar.hpp"
 
-#include <atomic>
 
 namespace cj {
 
@@ -231,8 +230,7 @@ using cj::BgStream;
 inline dim3 lane_grid(size_t n) { return dim3((uint32_t)((n + cj::kBlockThreads - 1) / cj::kBlockThreads)); }
 
 // bytes of bound-sized member slots per turn of a compress batch at most: 4096 slots
-constexpr uint64_t kSlotBudgetDefault = 4096ull * cj::kSlotStride;
-std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
+cj::SlotBudget g_slot_budget{4096ull * cj::kSlotStride};
 
 // enqueue only: pass 1 with the results straight into the caller's row
 int bgzf_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
@@ -326,7 +324,9 @@ int bgzf_encode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* 
             if (pass != 0 && std::none_of(h_enc + sa, h_enc + sb + 1, [](const BgEnc& x) { return x.mode == 2u; })) continue;
             hipLaunchKernelGGL(cj::bgzf_piece_rows_kernel, lane_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, (uint32_t)n, enc, in_off, in_len, r, owner,
                                (uint64_t)cj::kSlotStride);
-            if ((rc = cj::deflate_compress_device(e, CJ_DEFLATE_GZIP, cnt, in_base, r.in_off, r.in_len, slots, r.out_off, r.out_cap, r.result, s)) != 0) return rc;
+            cj::BatchArgs a;
+            cj::fill_args(a, 0, cnt, in_base, r.in_off, r.in_len, slots, r.out_off, r.out_cap, r.result);
+            if ((rc = cj::deflate_compress_device(e, CJ_DEFLATE_GZIP, a, s)) != 0) return rc;
             hipLaunchKernelGGL(cj::bgzf_layout_kernel, cj::wave_grid(sb - sa + 1), dim3(cj::kBlockThreads), 0, s, t0, cnt, (uint32_t)sa, (uint32_t)(sb - sa + 1),
                                pass, enc, r.result, moff, out_cap, result);
             hipLaunchKernelGGL(cj::bgzf_assemble_kernel, cj::wave_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, enc, owner, r.result, moff, slots,
@@ -377,6 +377,6 @@ int cj_bgzf_sizes_host(cj_engine* e, int what, uint32_t flags, size_t n, const u
 }
 
 // tests: the bytes of member slots per turn of a BGZF compress batch (0 = the default); returns the previous value
-uint64_t cj_debug_bgzf_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes ? bytes : kSlotBudgetDefault); }
+uint64_t cj_debug_bgzf_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes); }
 
 }  // extern "C"

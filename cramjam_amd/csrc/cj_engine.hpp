@@ -4,6 +4,7 @@
 #include "cj_common.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -116,6 +117,16 @@ private:
     }
 };
 
+// The bytes of a scratch that one slice of a batch may take: a default that the tests lower through a cj_debug_*_budget export
+// (0 = back to the default; returns the previous value)
+struct SlotBudget {
+    const uint64_t def;
+    std::atomic<uint64_t> cur;
+    explicit SlotBudget(uint64_t d) : def(d), cur(d) {}
+    uint64_t load() const { return cur.load(); }
+    uint64_t exchange(uint64_t bytes) { return cur.exchange(bytes ? bytes : def); }
+};
+
 // host-side pack/scatter of many small buffers is memcpy-bound on one core (~20 GB/s); split it over a few threads
 template <class F>
 void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
@@ -138,7 +149,8 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 // blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
 // streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
 // members, once per turn of member slots.  The three inner ones are taken one after another, never one inside another, and no path
-// takes two of the graph's mutexes the other way round; `dict_stage` and `zstd_enc_slots` are taken alone or under `mu` only.  The table
+// takes two of the graph's mutexes the other way round; `dict_stage` and `zstd_enc_slots` are taken alone or under `mu` only.  The three
+// slotted scratches (`zstd_slots`, `deflate_slots`, `zstd_enc_slots`) are taken in one place, cj::slot_slices below.  The table
 // of every entry's turns: DESIGN.md §2; two streams and two threads per scratch: tests/test_scratch_streams_gpu.py.
 struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
     int device = 0;
@@ -214,4 +226,46 @@ void for_slices(size_t n, size_t per, uint32_t flags, const uint8_t* in_base, co
         launch(a);
     }
 }
+template <class F>
+void for_slices(const BatchArgs& b, size_t per, F&& launch) {
+    for_slices(b.n_chunks, per, b.flags, b.in_base, b.in_off, b.in_len, b.out_base, b.out_off, b.out_cap, b.result, launch);
+}
+
+// One turn at a slotted scratch (`sc`, its slots in `buf`): batch `b` in slices of as many chunks as there are slots — what `budget`
+// bytes hold (one at least) and `limit` allows — launch(a, slots) for each; enqueue only (a turn that grows the slots waits for their
+// previous user while it reallocates).  It is the one turn its caller takes at `sc`, under whatever outer turns the caller holds
+// (LOCK ORDER above).  0 or CJ_E_*.
+template <class F>
+int slot_slices(Scratch& sc, DevBuf& buf, size_t slot_bytes, uint64_t budget, uint64_t limit, const BatchArgs& b, hipStream_t s, F&& launch) {
+    const size_t per = (size_t)std::min<uint64_t>({b.n_chunks, std::max<uint64_t>(1, budget / slot_bytes), limit});
+    ScratchTurn turn(sc, s);
+    if (turn.rc != 0 || (turn.rc = turn.reserve(buf, per * slot_bytes)) != 0) return turn.rc;
+    uint8_t* slots = (uint8_t*)buf.p;
+    for_slices(b, per, [&](const BatchArgs& a) { launch(a, slots); });
+    return turn.done(s);
+}
+
+#if defined(__HIPCC__)
+// the workgroups of Kernel that one CU holds at once (asked once per kernel; 0: not known)
+template <auto Kernel>
+int resident_per_cu(int threads) {
+    static std::atomic<int> known{-1};
+    int v = known.load();
+    if (v < 0) {
+        v = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, Kernel, threads, 0) != hipSuccess) { (void)hipGetLastError(); v = 0; }
+        known.store(v);
+    }
+    return v;
+}
+// ... that the device holds at once, as the `limit` of slot_slices: a launch of more workgroups than that ends in a tail of a few of
+// them.  Not known: no limit.  0 or CJ_E_*.
+template <auto Kernel>
+int resident_limit(cj_engine* e, int threads, uint64_t& limit) {
+    if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
+    const uint64_t resident = (uint64_t)resident_per_cu<Kernel>(threads) * (uint64_t)e->n_cu;
+    limit = resident != 0 ? resident : ~0ull;
+    return 0;
+}
+#endif
 }  // namespace cj

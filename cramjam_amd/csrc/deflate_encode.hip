@@ -1,65 +1,26 @@
 // deflate_encode.hip — batches of inputs into DEFLATE streams (cj_deflate_compress_batch_device / _host, cj_deflate_compress_bound;
 // DESIGN.md §5.13): raw DEFLATE, zlib streams and gzip members, one stream per chunk.  One workgroup of two wavefronts owns a stream
 // and walks its independent pieces of at most 64 KiB in order:
-//   stage 1   enc2::Walk<DeflateFmt, 2> (cj_enc2.hpp: the matcher of the LZ4 and Snappy encoders, candidates limited to 32 768 back)
-//             leaves fixed-size sequence records in the workgroup's scratch slot; the literals stay in the input
+//   stage 1   enc2::Walk<RecFmt<32768>, 2> (cj_rec_encode.hpp, cj_enc2.hpp: the matcher of the LZ4 and Snappy encoders, candidates
+//             limited to 32 768 back) leaves fixed-size sequence records in the workgroup's scratch slot; the literals stay in the input
 //   stage 2   deflate_enc_wave.hpp on the first wavefront: histograms, length-limited codes, the exact costs of a stored, a fixed and
 //             a dynamic block, the block behind the bit position the previous one left.  The second wavefront sums the input meanwhile
 //             (Adler-32 / CRC-32, once per stream)
 // The bytes are those of tests/hostsim/deflate_enc_model.c.  The slots are engine scratch within a fixed budget: a batch goes through
-// in slices of as many streams as there are slots (cj::ScratchTurn).  The device call only enqueues (a call that grows the scratch
+// in slices of as many streams as there are slots (cj::slot_slices).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
-#include "wave_lanes.hpp"
-#include "cj_enc2.hpp"
+#include "cj_rec_encode.hpp"
 #include "crc32_lanes.hpp"
 
-#include <atomic>
-
 namespace cj {
-
-struct DfeRec;
-__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i);
-
-}  // namespace cj
-
-#include "deflate_enc_wave.hpp"
-
-namespace cj {
-
-__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i) {
-    const uint4 v = *reinterpret_cast<const uint4*>(slot + i);
-    return DfeRec{v.x, v.y, v.z, v.w};
-}
 
 __device__ const Crc32Tables d_crc32_enc_tables = make_crc32_tables();
 
-// The matcher's format: a sequence is one record in the scratch slot (`out`), counted in records
-struct DeflateFmt {
-    static constexpr uint32_t kMaxDist = 32768u;
-    static constexpr bool kStreamLiterals = false;
-    static __device__ __forceinline__ uint32_t last_start(uint32_t n) { return n - 8u; }      // Snappy's: the position lanes read 8 bytes at a time
-    static __device__ __forceinline__ uint32_t limit(uint32_t n) { return n; }
-    static __device__ __forceinline__ uint32_t seq_size(uint32_t, uint32_t, uint32_t) { return 1u; }
-    static __device__ __forceinline__ void put(enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
-        if (o + 1u < kDfeSlotRecs) enc2::s128(out, 16u * o, make_uint4(lit0, lit, off, mlen));      // (the last record is the final literals')
-    }
-    static __device__ __forceinline__ uint32_t emit_lane(enc2::gcptr, enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t code, uint32_t off) {
-        put(out, o, lit0, lit, off, code + 4u);
-        return 0u;
-    }
-    static __device__ __forceinline__ uint32_t emit_wave(enc2::gcptr, enc2::gptr out, uint32_t op, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
-        if (lane_id() == 0u) put(out, op, lit0, lit, off, mlen);
-        return op + 1u;
-    }
-};
-
-constexpr uint32_t kDfeSlotBytes = (kDfeSlotRecs * 16u + 255u) & ~255u;
-constexpr int kDfeThreads = 128;
-
 // One workgroup per stream of the slice; slot blockIdx.x of `slots` is its own
 template <int WRAP>
-__global__ __launch_bounds__(kDfeThreads) void deflate_encode_kernel(BatchArgs a, uint8_t* slots) {
-    typedef enc2::Walk<DeflateFmt, 2> Matcher;
+__global__ __launch_bounds__(kRecEncThreads) void deflate_encode_kernel(BatchArgs a, uint8_t* slots) {
+    typedef RecFmt<32768u> Fmt;
+    typedef enc2::Walk<Fmt, 2> Matcher;
     __shared__ uint16_t ht_lds[kHashSize];
     __shared__ uint32_t scr[Matcher::kWords];
     __shared__ DfeLds lds;
@@ -73,9 +34,9 @@ __global__ __launch_bounds__(kDfeThreads) void deflate_encode_kernel(BatchArgs a
     const uint32_t n = (uint32_t)n64, cap = (uint32_t)(cap64 < 0xFFFFFFF0ull ? cap64 : 0xFFFFFFF0ull);
     const uint8_t* in = a.in_base + a.in_off[chunk];
     uint8_t* out = a.out_base + a.out_off[chunk];
-    DfeRec* slot = reinterpret_cast<DfeRec*>(slots + (uint64_t)blockIdx.x * kDfeSlotBytes);
+    DfeRec* slot = reinterpret_cast<DfeRec*>(slots + (uint64_t)blockIdx.x * kRecBytes);
     if (WRAP == kDfeGzip)
-        for (uint32_t i = threadIdx.x; i < 1024u; i += kDfeThreads) crc_adv[i] = (&d_crc32_enc_tables.adv256[0][0])[i];
+        for (uint32_t i = threadIdx.x; i < 1024u; i += kRecEncThreads) crc_adv[i] = (&d_crc32_enc_tables.adv256[0][0])[i];
     if (threadIdx.x < 8) sh[threadIdx.x] = 0u;
     __syncthreads();
 
@@ -90,10 +51,10 @@ __global__ __launch_bounds__(kDfeThreads) void deflate_encode_kernel(BatchArgs a
         // ---- stage 1: both wavefronts
         uint32_t nrec = 0, anchor = 0;
         if (pn >= 8u) {
-            ht.clear(threadIdx.x, kDfeThreads);
+            ht.clear(threadIdx.x, kRecEncThreads);
             ht.settle();
-            Matcher w{enc2::uniform_gptr(pin), (enc2::gptr)enc2::uniform_gptr(reinterpret_cast<const uint8_t*>(slot)), pn, DeflateFmt::last_start(pn),
-                      DeflateFmt::limit(pn), scr, ht, 0u, 0u, wave};
+            Matcher w{enc2::uniform_gptr(pin), (enc2::gptr)enc2::uniform_gptr(reinterpret_cast<const uint8_t*>(slot)), pn, Fmt::last_start(pn),
+                      Fmt::limit(pn), scr, ht, 0u, 0u, wave};
             anchor = w.run(0u);
             nrec = w.op;                                         // (the first wavefront's: it flushed the queue last)
         }
@@ -140,47 +101,27 @@ namespace {
 
 // bytes of record slots per slice at most: 1280 slots, the workgroups of the raw / zlib kernel that 256 CUs hold at
 // once (five per CU by LDS) — more slots would only be memory the engine keeps
-constexpr uint64_t kSlotBudgetDefault = 1280ull * cj::kDfeSlotBytes;
-std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
+cj::SlotBudget g_slot_budget{1280ull * cj::kRecBytes};
 
-// the workgroups of a wrapper's kernel that one CU holds at once (asked once; 0: not known)
-int resident_per_cu(int wrap) {
-    static std::atomic<int> known[3] = {{-1}, {-1}, {-1}};
-    int v = known[wrap].load();
-    if (v < 0) {
-        v = 0;
-        hipError_t err;
-        if (wrap == CJ_DEFLATE_RAW) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeRaw>, cj::kDfeThreads, 0);
-        else if (wrap == CJ_DEFLATE_ZLIB) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeZlib>, cj::kDfeThreads, 0);
-        else err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::deflate_encode_kernel<cj::kDfeGzip>, cj::kDfeThreads, 0);
-        if (err != hipSuccess) { (void)hipGetLastError(); v = 0; }
-        known[wrap].store(v);
-    }
-    return v;
+template <int WRAP>
+int compress_wrap(cj_engine* e, const cj::BatchArgs& b, hipStream_t s) {
+    constexpr auto kernel = &cj::deflate_encode_kernel<WRAP>;
+    uint64_t limit;
+    if (const int rc = cj::resident_limit<kernel>(e, cj::kRecEncThreads, limit)) return rc;
+    return cj::slot_slices(e->deflate_slots, e->d_deflate_slots, cj::kRecBytes, g_slot_budget.load(), limit, b, s, [&](const cj::BatchArgs& a, uint8_t* slots) {
+        hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(cj::kRecEncThreads), 0, s, a, slots);
+    });
 }
 
 }  // namespace
 
-// One turn at the engine's record slots (cj::ScratchTurn); enqueue only.  A slice is what the device holds at once — a launch of more
+// One turn at the engine's record slots (cj::slot_slices); enqueue only.  A slice is what the device holds at once — a launch of more
 // workgroups than that ends in a tail of a few of them (gzip, four per CU, on synth-v1: 25.7 GB/s in slices of 1280, 37.8 in slices of 1024) —
 // within the budget.  (Declared in cj_stage.hpp: the BGZF batch runs its members through it.)
-int cj::deflate_compress_device(cj_engine* e, int wrap, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-    uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kDfeSlotBytes);
-    const uint64_t resident = (uint64_t)resident_per_cu(wrap) * (uint64_t)e->n_cu;
-    if (resident != 0) slots_max = std::min(slots_max, resident);
-    const size_t per = (size_t)std::min<uint64_t>(n, slots_max);
-    cj::ScratchTurn turn(e->deflate_slots, s);
-    if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_deflate_slots, per * (size_t)cj::kDfeSlotBytes)) != 0) return turn.rc;
-    uint8_t* slots = (uint8_t*)e->d_deflate_slots.p;
-    cj::for_slices(n, per, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
-        const dim3 grid(a.n_chunks), block(cj::kDfeThreads);
-        if (wrap == CJ_DEFLATE_RAW) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeRaw>), grid, block, 0, s, a, slots);
-        else if (wrap == CJ_DEFLATE_ZLIB) hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeZlib>), grid, block, 0, s, a, slots);
-        else hipLaunchKernelGGL((cj::deflate_encode_kernel<cj::kDfeGzip>), grid, block, 0, s, a, slots);
-    });
-    return turn.done(s);
+int cj::deflate_compress_device(cj_engine* e, int wrap, const cj::BatchArgs& b, hipStream_t s) {
+    if (wrap == CJ_DEFLATE_RAW) return compress_wrap<cj::kDfeRaw>(e, b, s);
+    if (wrap == CJ_DEFLATE_ZLIB) return compress_wrap<cj::kDfeZlib>(e, b, s);
+    return compress_wrap<cj::kDfeGzip>(e, b, s);
 }
 
 extern "C" {
@@ -195,7 +136,9 @@ int cj_deflate_compress_batch_device(cj_engine* e, cj_deflate_wrap wrap, uint32_
                                      void* hip_stream) {
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return cj::deflate_compress_device(e, (int)wrap, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
+        return cj::deflate_compress_device(e, (int)wrap, a, s);
     });
 }
 
@@ -204,11 +147,13 @@ int cj_deflate_compress_batch_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t 
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return cj::deflate_compress_device(e, (int)wrap, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, d_in, d_out, d);
+        return cj::deflate_compress_device(e, (int)wrap, a, s);
     });
 }
 
 // tests: the bytes of record slots per slice of a DEFLATE compress batch (0 = the default); returns the previous value
-uint64_t cj_debug_deflate_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes ? bytes : kSlotBudgetDefault); }
+uint64_t cj_debug_deflate_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes); }
 
 }  // extern "C"

@@ -13,7 +13,6 @@
 #include "lz4_size_walk.hpp"
 #include "lz4_dict_wave.hpp"
 
-#include <atomic>
 
 namespace cj {
 
@@ -118,8 +117,7 @@ __global__ __launch_bounds__(kBlockThreads) void dict_finish_kernel(uint32_t n, 
 
 namespace {
 
-constexpr uint64_t kStageBudgetDefault = 1ull << 30;      // bytes of staged slots per slice
-std::atomic<uint64_t> g_stage_budget{kStageBudgetDefault};
+cj::SlotBudget g_stage_budget{1ull << 30};      // bytes of staged slots per slice
 
 bool args_ok(int codec, uint32_t flags, const void* dict, size_t dict_len) {
     return codec == CJ_CODEC_LZ4_BLOCK && (flags & ~CJ_FLAG_LZ4_SIZE_PREFIX) == 0u && (dict_len == 0 || dict != nullptr);
@@ -240,6 +238,6 @@ int cj_dict_batch_sizes_host(cj_engine* e, cj_codec codec, uint32_t flags, size_
 }
 
 // tests: the staging budget of dictionary compress in bytes (0 = the default); returns the previous value
-uint64_t cj_debug_dict_stage_budget(uint64_t bytes) { return g_stage_budget.exchange(bytes ? bytes : kStageBudgetDefault); }
+uint64_t cj_debug_dict_stage_budget(uint64_t bytes) { return g_stage_budget.exchange(bytes); }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 //     LaneBytes                 put(k, byte): lane k keeps a byte; flush(dst, n): lanes 0..n-1 store theirs to dst[lane], n <= 64
 //     LaneU32, LaneU64          a value per lane: v[lane] inside a CJ_LANES body
 //     lane_excl_add(v, before)  before[lane] = the sum of v below that lane; returns the sum of all 64 (wave-uniform)
-// (rec_ld, the encoder's read of a sequence record, needs the complete DfeRec and stays with deflate_encode.hip.)  Not part of the C-ABI.
+// (rec_ld, the encoder's read of a sequence record, needs the complete DfeRec and is cj_rec_encode.hpp's.)  Not part of the C-ABI.
 #pragma once
 #include "cj_stage.hpp"
 #include "cj_match.hpp"

@@ -2,13 +2,12 @@
 // §5.14): one chunk = what one ZSTD_decompress call reads, one wavefront per chunk, workgroups of four wavefronts.  The decoder is
 // zstd_wave.hpp (the same text tests/hostsim compiles for the host); this file gives it the wavefront: the accessors (wave_lanes.hpp), each wavefront's
 // private tables in static LDS (10.0 KiB each), its literal slot in engine scratch and the launches.  The slots come from a fixed
-// budget (cj::ScratchTurn on e->zstd_slots): a batch goes through in slices of as many chunks as there are slots.  The size query is
+// budget (cj::slot_slices on e->zstd_slots): a batch goes through in slices of as many chunks as there are slots.  The size query is
 // the same decoder without stores and uses no scratch.  The device calls only enqueue (a decode that grows the slots waits for their
 // previous user while it reallocates).
 #include "wave_lanes.hpp"
 #include "blosc_filters.hpp"      // (declares launch_zstd_decode)
 
-#include <atomic>
 
 #include "zstd_wave.hpp"
 
@@ -38,8 +37,7 @@ __global__ __launch_bounds__(kBlockThreads) void zstd_kernel(BatchArgs a, uint8_
 namespace {
 
 // bytes of literal slots per slice at most: 4096 slots, the wavefronts that 256 CUs hold at once (four workgroups per CU by LDS)
-constexpr uint64_t kSlotBudgetDefault = 4096ull * cj::kZsSlotBytes;
-std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
+cj::SlotBudget g_slot_budget{4096ull * cj::kZsSlotBytes};
 
 bool fmt_ok(int fmt) { return fmt == CJ_ZSTD_FRAMES; }
 
@@ -52,26 +50,20 @@ int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const
     return 0;
 }
 
-// One turn at the engine's literal slots (cj::ScratchTurn); enqueue only.  A caller may hold the e->fb turn (blosc_batch.hip), never
+// One turn at the engine's literal slots (cj::slot_slices); enqueue only.  A caller may hold the e->fb turn (blosc_batch.hip), never
 // the other way round: the lock order is written down where cj_engine declares the scratches
-int decode_device(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                  const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    const uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kZsSlotBytes);
-    const size_t per = (size_t)std::min<uint64_t>(std::min<uint64_t>(n, slots_max), cj::grid_chunks());
-    cj::ScratchTurn turn(e->zstd_slots, s);
-    if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_zstd_slots, per * (size_t)cj::kZsSlotBytes)) != 0) return turn.rc;
-    uint8_t* slots = (uint8_t*)e->d_zstd_slots.p;
-    cj::for_slices(n, per, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
+int decode_device(cj_engine* e, const cj::BatchArgs& b, hipStream_t s) {
+    return cj::slot_slices(e->zstd_slots, e->d_zstd_slots, cj::kZsSlotBytes, g_slot_budget.load(), cj::grid_chunks(), b, s,
+                           [&](const cj::BatchArgs& a, uint8_t* slots) {
         hipLaunchKernelGGL((cj::zstd_kernel<false>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, slots);
     });
-    return turn.done(s);
 }
 
 }  // namespace
 
 int cj::launch_zstd_decode(cj_engine* e, const cj::BatchArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return 0;
-    return decode_device(e, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
+    return decode_device(e, a, s);
 }
 
 extern "C" {
@@ -80,7 +72,9 @@ int cj_zstd_batch_device(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t fl
                          const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, void* hip_stream) {
     if (!fmt_ok((int)fmt) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return decode_device(e, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
+        return decode_device(e, a, s);
     });
 }
 
@@ -89,7 +83,9 @@ int cj_zstd_batch_host(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t flag
     if (!fmt_ok((int)fmt) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return decode_device(e, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, d_in, d_out, d);
+        return decode_device(e, a, s);
     });
 }
 
@@ -109,6 +105,6 @@ int cj_zstd_batch_sizes_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags, s
 }
 
 // tests: the bytes of literal slots per slice of a Zstandard decode batch (0 = the default); returns the previous value
-uint64_t cj_debug_zstd_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes ? bytes : kSlotBudgetDefault); }
+uint64_t cj_debug_zstd_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes); }
 
 }  // extern "C"

@@ -1,23 +1,18 @@
 // zstd_encode.hip — batches of inputs into Zstandard frames (cj_zstd_compress_batch_device / _host, cj_zstd_compress_bound;
 // DESIGN.md §5.15), one frame per chunk.  One workgroup of two wavefronts owns a frame and walks its independent pieces of at most
 // 64 KiB in order, one block a piece:
-//   stage 1   enc2::Walk<ZstdFmt, 2> (cj_enc2.hpp: the matcher of the LZ4, Snappy and DEFLATE encoders; candidates up to the 16-bit
-//             table's lap, 65 535 back) leaves fixed-size sequence records in the workgroup's scratch slot
+//   stage 1   enc2::Walk<RecFmt<65535>, 2> (cj_rec_encode.hpp, cj_enc2.hpp: the matcher of the LZ4, Snappy and DEFLATE encoders;
+//             candidates up to the 16-bit table's lap, 65 535 back) leaves fixed-size sequence records in the workgroup's scratch slot
 //   stage 2   zstd_enc_wave.hpp on the first wavefront: the literals gathered into the slot's literal area, Huffman or not by exact
 //             size under a tree of direct or FSE-compressed weights, each sequence table RLE, FSE_Compressed or Predefined by cost (zstd_fse_enc.h), the FSE state chains walked once (pass A) and written in parallel (pass B), the block RLE, Compressed
 //             or Raw.  The second wavefront runs XXH64 over the input meanwhile (once per frame, only with CJ_ZSTD_FLAG_CHECKSUM)
 // The bytes are those of tests/hostsim/zstd_enc_model.c.  The slots are engine scratch within a fixed budget: a batch goes through
-// in slices of as many frames as there are slots (cj::ScratchTurn).  The device call only enqueues (a call that grows the scratch
+// in slices of as many frames as there are slots (cj::slot_slices).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
-#include "wave_lanes.hpp"
-#include "cj_enc2.hpp"
-
-#include <atomic>
+#include "cj_rec_encode.hpp"
 
 namespace cj {
 
-struct DfeRec;
-__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i);
 __device__ __forceinline__ void rec_st32(DfeRec* slot, uint32_t i, uint32_t w, uint32_t v) { reinterpret_cast<uint32_t*>(slot)[4u * i + (w & 3u)] = v; }
 __device__ __forceinline__ uint32_t lit_ld8(const uint8_t* p) { return *p; }
 __device__ __forceinline__ void lit_st8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
@@ -28,38 +23,12 @@ __device__ __forceinline__ void lit_st8(uint8_t* p, uint32_t v) { *p = (uint8_t)
 
 namespace cj {
 
-__device__ __forceinline__ DfeRec rec_ld(const DfeRec* slot, uint32_t i) {
-    const uint4 v = *reinterpret_cast<const uint4*>(slot + i);
-    return DfeRec{v.x, v.y, v.z, v.w};
-}
-
-// The matcher's format: a sequence is one record in the scratch slot (`out`), counted in records
-struct ZstdFmt {
-    // the lap of the matcher's 16-bit table.  A match starts at most 8 bytes before a piece's end (last_start), so the largest distance a
-    // 64 KiB piece holds is 65 528: the limit is never the one that binds, and offset code 16 (Offset_Value >= 65 536) never occurs
-    static constexpr uint32_t kMaxDist = 65535u;
-    static constexpr bool kStreamLiterals = false;
-    static __device__ __forceinline__ uint32_t last_start(uint32_t n) { return n - 8u; }      // Snappy's: the position lanes read 8 bytes at a time
-    static __device__ __forceinline__ uint32_t limit(uint32_t n) { return n; }
-    static __device__ __forceinline__ uint32_t seq_size(uint32_t, uint32_t, uint32_t) { return 1u; }
-    static __device__ __forceinline__ void put(enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
-        if (o + 1u < kZseSlotRecs) enc2::s128(out, 16u * o, make_uint4(lit0, lit, off, mlen));      // (the last record is the final literals')
-    }
-    static __device__ __forceinline__ uint32_t emit_lane(enc2::gcptr, enc2::gptr out, uint32_t o, uint32_t lit0, uint32_t lit, uint32_t code, uint32_t off) {
-        put(out, o, lit0, lit, off, code + 4u);
-        return 0u;
-    }
-    static __device__ __forceinline__ uint32_t emit_wave(enc2::gcptr, enc2::gptr out, uint32_t op, uint32_t lit0, uint32_t lit, uint32_t off, uint32_t mlen) {
-        if (lane_id() == 0u) put(out, op, lit0, lit, off, mlen);
-        return op + 1u;
-    }
-};
-
-constexpr int kZseThreads = 128;
+static_assert(kZseSlotRecs == kDfeSlotRecs, "RecFmt's slot-record bound");
 
 // One workgroup per frame of the slice; slot blockIdx.x of `slots` is its own
-__global__ __launch_bounds__(kZseThreads) void zstd_encode_kernel(BatchArgs a, uint8_t* slots, uint32_t flags) {
-    typedef enc2::Walk<ZstdFmt, 2> Matcher;
+__global__ __launch_bounds__(kRecEncThreads) void zstd_encode_kernel(BatchArgs a, uint8_t* slots, uint32_t flags) {
+    typedef RecFmt<65535u> Fmt;
+    typedef enc2::Walk<Fmt, 2> Matcher;
     __shared__ uint16_t ht_lds[kHashSize];
     __shared__ uint32_t scr[Matcher::kWords];
     __shared__ ZseLds lds;
@@ -90,10 +59,10 @@ __global__ __launch_bounds__(kZseThreads) void zstd_encode_kernel(BatchArgs a, u
         // ---- stage 1: both wavefronts
         uint32_t nrec = 0, anchor = 0;
         if (pn >= 8u) {
-            ht.clear(threadIdx.x, kZseThreads);
+            ht.clear(threadIdx.x, kRecEncThreads);
             ht.settle();
-            Matcher w{enc2::uniform_gptr(pin), (enc2::gptr)enc2::uniform_gptr(reinterpret_cast<const uint8_t*>(slot)), pn, ZstdFmt::last_start(pn),
-                      ZstdFmt::limit(pn), scr, ht, 0u, 0u, wave};
+            Matcher w{enc2::uniform_gptr(pin), (enc2::gptr)enc2::uniform_gptr(reinterpret_cast<const uint8_t*>(slot)), pn, Fmt::last_start(pn),
+                      Fmt::limit(pn), scr, ht, 0u, 0u, wave};
             anchor = w.run(0u);
             nrec = w.op;                                         // (the first wavefront's: it flushed the queue last)
         }
@@ -126,36 +95,16 @@ namespace {
 
 // bytes of slots per slice at most: 1024 slots of 320 KiB — four workgroups per CU by LDS on 256 CUs; more slots
 // would only be memory the engine keeps
-constexpr uint64_t kSlotBudgetDefault = 1024ull * cj::kZseSlotBytes;
-std::atomic<uint64_t> g_slot_budget{kSlotBudgetDefault};
+cj::SlotBudget g_slot_budget{1024ull * cj::kZseSlotBytes};
 
-// the workgroups of the kernel that one CU holds at once (asked once; 0: not known)
-int resident_per_cu() {
-    static std::atomic<int> known{-1};
-    int v = known.load();
-    if (v < 0) {
-        v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, cj::zstd_encode_kernel, cj::kZseThreads, 0) != hipSuccess) { (void)hipGetLastError(); v = 0; }
-        known.store(v);
-    }
-    return v;
-}
-
-// One turn at the engine's slots (cj::ScratchTurn); enqueue only.  A slice is what the device holds at once, within the budget.
-int compress_device(cj_engine* e, uint32_t flags, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                    const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-    uint64_t slots_max = std::max<uint64_t>(1, g_slot_budget.load() / cj::kZseSlotBytes);
-    const uint64_t resident = (uint64_t)resident_per_cu() * (uint64_t)e->n_cu;
-    if (resident != 0) slots_max = std::min(slots_max, resident);
-    const size_t per = (size_t)std::min<uint64_t>(n, slots_max);
-    cj::ScratchTurn turn(e->zstd_enc_slots, s);
-    if (turn.rc != 0 || (turn.rc = turn.reserve(e->d_zstd_enc_slots, per * (size_t)cj::kZseSlotBytes)) != 0) return turn.rc;
-    uint8_t* slots = (uint8_t*)e->d_zstd_enc_slots.p;
-    cj::for_slices(n, per, 0u, in_base, in_off, in_len, out_base, out_off, out_cap, result, [&](const cj::BatchArgs& a) {
-        hipLaunchKernelGGL(cj::zstd_encode_kernel, dim3(a.n_chunks), dim3(cj::kZseThreads), 0, s, a, slots, flags);
+// One turn at the engine's slots (cj::slot_slices); enqueue only.  A slice is what the device holds at once, within the budget.
+int compress_device(cj_engine* e, uint32_t flags, const cj::BatchArgs& b, hipStream_t s) {
+    constexpr auto kernel = &cj::zstd_encode_kernel;
+    uint64_t limit;
+    if (const int rc = cj::resident_limit<kernel>(e, cj::kRecEncThreads, limit)) return rc;
+    return cj::slot_slices(e->zstd_enc_slots, e->d_zstd_enc_slots, cj::kZseSlotBytes, g_slot_budget.load(), limit, b, s, [&](const cj::BatchArgs& a, uint8_t* slots) {
+        hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(cj::kRecEncThreads), 0, s, a, slots, flags);
     });
-    return turn.done(s);
 }
 
 bool args_ok(cj_zstd_format fmt, uint32_t flags) { return fmt == CJ_ZSTD_FRAMES && (flags & ~CJ_ZSTD_FLAG_CHECKSUM) == 0u; }
@@ -174,7 +123,9 @@ int cj_zstd_compress_batch_device(cj_engine* e, cj_zstd_format fmt, uint32_t fla
                                   void* hip_stream) {
     if (!args_ok(fmt, flags)) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return compress_device(e, flags, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
+        return compress_device(e, flags, a, s);
     });
 }
 
@@ -183,11 +134,13 @@ int cj_zstd_compress_batch_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags
     if (!args_ok(fmt, flags)) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return compress_device(e, flags, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        cj::BatchArgs a;
+        cj::fill_args(a, 0, d_in, d_out, d);
+        return compress_device(e, flags, a, s);
     });
 }
 
 // tests: the bytes of slots per slice of a Zstandard compress batch (0 = the default); returns the previous value
-uint64_t cj_debug_zstd_enc_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes ? bytes : kSlotBudgetDefault); }
+uint64_t cj_debug_zstd_enc_slot_budget(uint64_t bytes) { return g_slot_budget.exchange(bytes); }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ def lib():
     """the model and the host build in one library (built by __graft_entry__.build() or here)"""
     if "lib" not in _cache:
         so = os.path.join(SIM, "libsim_deflate_encode.so")
-        srcs = [os.path.join(SIM, "sim_deflate_encode.cpp"), os.path.join(SIM, "sim_wave.hpp"), os.path.join(SIM, "deflate_enc_model.c"), os.path.join(ROOT, "cramjam_amd", "csrc", "deflate_enc_wave.hpp")]
+        srcs = [os.path.join(SIM, "sim_deflate_encode.cpp"), os.path.join(SIM, "sim_wave.hpp"), os.path.join(SIM, "deflate_enc_model.c"), os.path.join(SIM, "enc2_round.h"), os.path.join(ROOT, "cramjam_amd", "csrc", "deflate_enc_wave.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             build_lib(so)
         L = C.CDLL(so)
@@ -250,6 +250,7 @@ def write_cases_file(path):
     """the file a stand-alone build of tests/hostsim/sim_deflate_encode.cpp (-DSIM_MAIN) runs: every case x wrapper at capacities the bound,
     exact, exact - 1 and 0, the alignments in turn, with the model's verdict and bytes.  Format: u32 count, then per case u32 wrap, n, cap,
     input misalignment, output misalignment | i64 expected result | the input | the expected stream (result > 0).  Returns the count.
+    (The model includes the matcher's round, tests/hostsim/enc2_round.h, from its own directory.)
         python -c "import sys; sys.path.insert(0, 'tests'); import deflate_enc_cases as E; print(E.write_cases_file('cases.bin'))"
         gcc -O1 -g -fsanitize=address,undefined -c -o model.o tests/hostsim/deflate_enc_model.c
         python -c "import os, sys; sys.path.insert(0, 'tests'); from hostsim_build import build_sim; build_sim(['sim_deflate_encode.cpp', os.path.abspath('model.o')], 'sim_main', main=True, sanitize=True)" && ./sim_main cases.bin"""

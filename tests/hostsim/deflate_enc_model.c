@@ -2,7 +2,7 @@
  * DESIGN.md 5.13).  The kernel and the host build of its entropy stage (sim_deflate_encode.cpp) emit exactly these bytes.
  *
  *   pieces    the input is cut into independent pieces of at most 65 536 bytes; no match crosses a piece
- *   matching  enc2_model.c's round (R = 512, restated below) with candidates limited to a distance of 32 768; last_start = n - 8,
+ *   matching  enc2_round.h's round (R = 512) with candidates limited to a distance of 32 768; last_start = n - 8,
  *             limit = n; a piece shorter than 8 bytes is all literals.  A piece becomes records (literal start, literal count,
  *             distance, match length); the last record carries the final literals and no match
  *   symbols   literals, length / distance pairs (a match above 258 is split into pieces of at most 258, none below 3), end of block
@@ -13,102 +13,16 @@
  *   choice    stored, fixed or dynamic by their exact bit costs at the block's bit position; a tie goes to the simpler block
  *   wrappers  none / zlib (78 01 .. Adler-32) / gzip (fixed 10-byte header .. CRC-32, ISIZE)
  */
-#include <stdint.h>
-#include <stddef.h>
-#include <string.h>
-#include <stdlib.h>
+#include "enc2_round.h"
 
-#define HASH_BITS 13
-#define HASH_SIZE (1u << HASH_BITS)
-#define RMAX 512
-#define BLOCK 128u
 #define MAX_DIST 32768u
 #define PIECE 65536u
 #define E_OUT_TOO_SMALL (-6)
 
-static inline uint32_t ld32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static inline uint32_t hash_slot(uint32_t v) { return (v * 2654435761u) >> (32 - HASH_BITS); }
-
-typedef struct { uint32_t s, e, off; } sel_t;
-typedef struct { uint32_t lit0, lit, dist, mlen; } rec_t;
-
-/* enc2_model.c's round, with the distance limit where the candidate distance is formed */
-static int model_round(const uint8_t* in, uint16_t* tab, uint32_t pos, uint32_t span, uint32_t R, uint32_t last_start, uint32_t limit,
-                       uint32_t* cur_io, sel_t* sel) {
-    static uint32_t hs[RMAX], d[RMAX];
-    static uint8_t ok[RMAX], valid[RMAX];
-    const uint32_t anchor = *cur_io;
-    for (uint32_t b0 = 0; b0 < R; b0 += BLOCK) {
-        for (uint32_t i = b0; i < b0 + BLOCK; i++) {
-            const uint32_t p = pos + i;
-            valid[i] = i < span && p <= last_start;
-            ok[i] = 0; d[i] = 0;
-            if (!valid[i]) continue;
-            hs[i] = hash_slot(ld32(in + p));
-            const uint32_t dist = (p - tab[hs[i]]) & 0xffffu;
-            if (dist != 0u && dist <= p && dist <= MAX_DIST) d[i] = dist;
-        }
-        for (uint32_t k = 0; k < 4u; k++)
-            for (uint32_t i = b0 + k; i < b0 + BLOCK; i += 4u) {
-                if (!valid[i]) continue;
-                if (d[i] != 0u && (i & 255u) != 0u && d[i - 1] == d[i]) continue;
-                tab[hs[i]] = (uint16_t)(pos + i);
-            }
-    }
-    for (uint32_t i = 0; i < R; i++) {
-        if (d[i] == 0u) continue;
-        if ((i & 255u) != 0u && d[i - 1] == d[i]) continue;
-        if (ld32(in + pos + i - d[i]) == ld32(in + pos + i)) ok[i] = 1;
-    }
-    uint32_t cur = anchor;
-    int ns = 0;
-    for (uint32_t i = 0; i < R; i++) {
-        if (!ok[i]) continue;
-        const uint32_t p = pos + i, c = p - d[i];
-        uint32_t e = p + 4u;
-        while (e < limit && in[e] == in[e - d[i]]) e++;
-        uint32_t s;
-        if (p >= cur) {
-            uint32_t room = p - cur, bk = 0;
-            if (room > c) room = c;
-            while (bk < room && in[p - 1u - bk] == in[c - 1u - bk]) bk++;
-            s = p - bk;
-        } else s = cur;
-        if (e < s + 4u || s > last_start) continue;
-        sel[ns].s = s; sel[ns].e = e; sel[ns].off = d[i]; ns++;
-        cur = e;
-    }
-    *cur_io = cur;
-    return ns;
-}
+typedef enc2_rec_t rec_t;
 
 /* the records of one piece (n <= 65536); rec must hold n / 4 + 2 records.  Returns their number (the last one has no match) */
-uint32_t dfe_model_records(const uint8_t* in, uint32_t n, uint32_t* rec_out) {
-    rec_t* rec = (rec_t*)rec_out;
-    uint32_t nr = 0, anchor = 0;
-    if (n >= 8u) {
-        uint16_t* tab = (uint16_t*)calloc(HASH_SIZE, 2);
-        sel_t* sel = (sel_t*)malloc(sizeof(sel_t) * (RMAX + 2));
-        const uint32_t last_start = n - 8u, limit = n;
-        uint32_t pos = 0, span = 64u;
-        while (pos <= last_start) {
-            uint32_t cur = anchor;
-            const int ns = model_round(in, tab, pos, span, RMAX, last_start, limit, &cur, sel);
-            uint32_t a = anchor;
-            for (int q = 0; q < ns; q++) {
-                rec[nr].lit0 = a; rec[nr].lit = sel[q].s - a; rec[nr].dist = sel[q].off; rec[nr].mlen = sel[q].e - sel[q].s; nr++;
-                a = sel[q].e;
-            }
-            anchor = cur;
-            const uint32_t round_end = pos + span;
-            span = span * 2u < RMAX ? span * 2u : RMAX;
-            pos = anchor > round_end ? anchor : round_end;
-        }
-        free(tab); free(sel);
-    }
-    rec[nr].lit0 = anchor; rec[nr].lit = n - anchor; rec[nr].dist = 0; rec[nr].mlen = 0; nr++;
-    return nr;
-}
+uint32_t dfe_model_records(const uint8_t* in, uint32_t n, uint32_t* rec_out) { return enc2_records(in, n, MAX_DIST, 512u, rec_out); }
 
 /* ---- symbols ------------------------------------------------------------------------------------------------------------------- */
 static uint32_t n_split(uint32_t m) { return m ? (m + 257u) / 258u : 0u; }

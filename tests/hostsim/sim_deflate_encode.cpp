@@ -1,6 +1,6 @@
 // deflate_enc_wave.hpp compiled for the host over sim_wave.hpp's checked stand-ins, for tests/test_deflate_encode_model.py (and, with
 // SIM_MAIN, a stand-alone program that runs a file of cases).  The matcher is the model's (deflate_enc_model.c: dfe_model_records,
-// linked in) — on the device it is enc2::Walk<DeflateFmt, 2>, held to the same records by the GPU tests.  The input range is the
+// linked in) — on the device it is enc2::Walk<RecFmt<32768>, 2>, held to the same records by the GPU tests.  The input range is the
 // piece, the record range what the matcher wrote of a slot that is a heap block of exactly what the piece may need.
 #include "sim_wave.hpp"
 

@@ -1,6 +1,6 @@
 // zstd_enc_wave.hpp compiled for the host over sim_wave.hpp's checked stand-ins, for tests/test_zstd_encode_model.py (and, with
 // SIM_MAIN, a stand-alone program that runs a file of cases).  The matcher is the model's (zstd_enc_model.c: zse_model_records,
-// linked in) — on the device it is enc2::Walk<ZstdFmt, 2>, held to the same records by the GPU tests.  The input range is the piece,
+// linked in) — on the device it is enc2::Walk<RecFmt<65535>, 2>, held to the same records by the GPU tests.  The input range is the piece,
 // the record range what the matcher wrote of a slot that is a heap block of exactly what the piece may need, the literal area
 // (sim_src2) a heap block of the piece's length.
 #include "sim_wave.hpp"

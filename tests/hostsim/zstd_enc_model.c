@@ -5,7 +5,7 @@
  *             Window_Descriptor of 0x30 (64 KiB: no match crosses a piece) and 2 (n <= 65791) or 4 bytes.  No dictionary id
  *   pieces    the input is cut into independent pieces of at most 65 536 bytes, one block each: RLE (one repeated byte), Compressed
  *             (its exact size is below the piece's) or Raw.  An empty input is a header and one empty last Raw block
- *   matching  enc2_model.c's round (included below, unchanged: no distance limit but the 16-bit table's lap), R = 512, last_start =
+ *   matching  enc2_round.h's round (no distance limit but the 16-bit table's lap), R = 512, last_start =
  *             n - 8, limit = n; a piece below 8 bytes is all literals.  Records (literal start, literal count, distance, match length)
  *   literals  all literal runs in order: Raw or Huffman by exact size (one distinct literal is one distinct byte: an RLE block), a tie to the simpler.  Huffman: the
  *             DEFLATE model's builder at limit 11 (dfe_model_build_lens, linked in), weight = max length + 1 - length, codes by
@@ -16,7 +16,7 @@
  *             bitstream in libzstd's order with the final 1-bit
  *   checksum  the low 32 bits of XXH64 (seed 0) of the input, behind the last block, when asked for
  */
-#include "enc2_model.c"
+#include "enc2_round.h"
 #include "../../cramjam_amd/csrc/zstd_fse_enc.h"      /* the FSE stage's serial arithmetic: the kernel includes the same text */
 
 #define ZPIECE 65536u
@@ -26,35 +26,10 @@
 
 uint32_t dfe_model_build_lens(const uint32_t* hist, uint32_t nsym, uint32_t maxbits, int pad_single, uint8_t* lens);
 
-typedef struct { uint32_t lit0, lit, dist, mlen; } zrec_t;
+typedef enc2_rec_t zrec_t;
 
 /* the records of one piece (n <= 65536); rec must hold n / 4 + 2 records.  Returns their number (the last one has no match) */
-uint32_t zse_model_records(const uint8_t* in, uint32_t n, uint32_t* rec_out) {
-    zrec_t* rec = (zrec_t*)rec_out;
-    uint32_t nr = 0, anchor = 0;
-    if (n >= 8u) {
-        uint16_t* tab = (uint16_t*)calloc(HASH_SIZE, 2);
-        sel_t* sel = (sel_t*)malloc(sizeof(sel_t) * (RMAX + 2));
-        const uint32_t last_start = n - 8u, limit = n, R = 512u;
-        uint32_t pos = 0, span = 64u;
-        while (pos <= last_start) {
-            uint32_t cur = anchor;
-            const int ns = model_round(in, n, tab, pos, span, R, last_start, limit, &cur, sel);
-            uint32_t a = anchor;
-            for (int q = 0; q < ns; q++) {
-                rec[nr].lit0 = a; rec[nr].lit = sel[q].s - a; rec[nr].dist = sel[q].off; rec[nr].mlen = sel[q].e - sel[q].s; nr++;
-                a = sel[q].e;
-            }
-            anchor = cur;
-            const uint32_t round_end = pos + span;
-            span = span * 2u < R ? span * 2u : R;
-            pos = anchor > round_end ? anchor : round_end;
-        }
-        free(tab); free(sel);
-    }
-    rec[nr].lit0 = anchor; rec[nr].lit = n - anchor; rec[nr].dist = 0; rec[nr].mlen = 0; nr++;
-    return nr;
-}
+uint32_t zse_model_records(const uint8_t* in, uint32_t n, uint32_t* rec_out) { return enc2_records(in, n, ENC2_NO_MAX_DIST, 512u, rec_out); }
 
 /* ---- the codes ------------------------------------------------------------------------------------------------------------------- */
 static const uint32_t kLLBase[36] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18, 20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024,

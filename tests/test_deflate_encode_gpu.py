@@ -235,6 +235,29 @@ def test_twenty_chunks_through_several_turns_of_a_shrunken_slot_budget(eng):
     assert _guards_intact(out, ooff, caps) is None
 
 
+def test_five_chunks_of_two_pieces_at_a_budget_below_one_slot(eng):
+    """a budget of one byte is one slot: five slices of one chunk each, every stream what the same call writes at the default budget"""
+    import oracle
+    e, N = eng
+    L = N.lib()
+    default = 1280 * 262400
+    chunks = [oracle.synth_v1(70000, i) for i in range(5)]
+    caps = [E.bound(len(c), E.GZIP) for c in chunks]
+    res0, out0, ooff = _device_call(e, N, E.GZIP, chunks, caps)
+    assert L.cj_debug_deflate_slot_budget(1) == default               # (the setter returns the previous value)
+    try:
+        res, out, ooff1 = _device_call(e, N, E.GZIP, chunks, caps)
+    finally:
+        assert L.cj_debug_deflate_slot_budget(0) == 1                 # 0: back to the default
+    assert L.cj_debug_deflate_slot_budget(0) == default
+    assert ooff1 == ooff
+    for i, c in enumerate(chunks):
+        assert int(res[i]) == int(res0[i]) > 0, i
+        assert out[ooff[i]:ooff[i] + int(res[i])].tobytes() == out0[ooff[i]:ooff[i] + int(res0[i])].tobytes(), i
+        assert zlib.decompress(out[ooff[i]:ooff[i] + int(res[i])].tobytes(), 31) == c, i
+    assert _guards_intact(out, ooff, caps) is None
+
+
 def test_empty_batches_and_bad_arguments(eng):
     e, N = eng
     L = N.lib()

@@ -20,7 +20,7 @@ BLOCK = 65536
 
 
 def linked_lib():
-    srcs = [os.path.join(SIM_DIR, f) for f in ("enc2_linked_model.c", "enc2_model.c")]
+    srcs = [os.path.join(SIM_DIR, f) for f in ("enc2_linked_model.c", "enc2_model.c", "enc2_round.h")]
     if not os.path.exists(SIM_SO) or os.path.getmtime(SIM_SO) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-o", SIM_SO, srcs[0]])
     L = C.CDLL(SIM_SO)

@@ -18,7 +18,8 @@ SIM_SO = os.path.join(SIM_DIR, "libsim_enc2.so")
 
 def model_lib():
     src = os.path.join(SIM_DIR, "enc2_model.c")
-    if not os.path.exists(SIM_SO) or os.path.getmtime(SIM_SO) < os.path.getmtime(src):
+    srcs = [src, os.path.join(SIM_DIR, "enc2_round.h")]
+    if not os.path.exists(SIM_SO) or os.path.getmtime(SIM_SO) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-o", SIM_SO, src])
     L = C.CDLL(SIM_SO)
     for f in (L.enc2_model_lz4, L.enc2_model_snappy):

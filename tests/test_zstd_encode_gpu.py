@@ -239,6 +239,33 @@ def test_twenty_chunks_through_seven_turns_of_a_three_slot_budget(eng):
     assert _guards_intact(out, ooff, caps) is None
 
 
+def test_five_chunks_of_two_pieces_at_a_budget_below_one_slot(eng):
+    """a budget of one byte is one slot: five slices of one chunk each, every frame (with its checksum) what the same call writes at the
+    default budget, and read back by the batch decoder"""
+    import oracle
+    from cramjam_amd import batch
+    e, N = eng
+    L = N.lib()
+    default = 1024 * (262400 + 65536)
+    chunks = [oracle.synth_v1(70000, i) for i in range(5)]
+    caps = [E.bound(len(c), 1) for c in chunks]
+    res0, out0, ooff = _device_call(e, N, 1, chunks, caps)
+    assert L.cj_debug_zstd_enc_slot_budget(1) == default              # (the setter returns the previous value)
+    try:
+        res, out, ooff1 = _device_call(e, N, 1, chunks, caps)
+    finally:
+        assert L.cj_debug_zstd_enc_slot_budget(0) == 1                # 0: back to the default
+    assert L.cj_debug_zstd_enc_slot_budget(0) == default
+    assert ooff1 == ooff
+    frames = []
+    for i in range(5):
+        assert int(res[i]) == int(res0[i]) > 0, i
+        frames.append(out[ooff[i]:ooff[i] + int(res[i])].tobytes())
+        assert frames[i] == out0[ooff[i]:ooff[i] + int(res0[i])].tobytes(), i
+    assert [bytes(o) for o in batch.zstd_decompress_many(frames)[1]] == chunks
+    assert _guards_intact(out, ooff, caps) is None
+
+
 def test_empty_batches_and_bad_arguments(eng):
     e, N = eng
     L = N.lib()

@@ -120,6 +120,26 @@ def test_slot_budget_of_three_slots_over_ten_streams(eng):
     assert list(res2) == list(res) and (out2 == out).all()
 
 
+def test_five_frames_at_a_budget_below_one_slot(eng):
+    """a budget of one byte is one slot: five slices of one frame each — the five accepted frames whose content is nearest 70 KB —
+    every output what the same call writes at the default budget"""
+    e, N = eng
+    L = N.lib()
+    default = 4096 * (131072 + 32)
+    part = sorted((c for c in _shuffled() if c.accepted and not c.name.startswith("mut_")), key=lambda c: (abs(c.cap - 70000), c.name))[:5]
+    assert all(60000 < c.cap < 140000 for c in part)
+    caps = [c.cap for c in part]
+    res0, out0, _ = _device_call(e, N, [c.stream for c in part], caps)
+    assert L.cj_debug_zstd_slot_budget(1) == default                  # (the setter returns the previous value)
+    try:
+        res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
+    finally:
+        assert L.cj_debug_zstd_slot_budget(0) == 1                    # 0: back to the default
+    assert L.cj_debug_zstd_slot_budget(0) == default
+    _check(part, 0, res, out, ooff, caps)
+    assert list(res) == list(res0) and (out == out0).all()
+
+
 def test_size_query_then_the_public_calls(eng):
     e, N = eng
     from cramjam_amd import batch

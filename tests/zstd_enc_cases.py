@@ -33,7 +33,7 @@ def lib():
     """the model and the host build in one library (built by __graft_entry__.build() or here)"""
     if "lib" not in _cache:
         so = os.path.join(SIM, "libsim_zstd_encode.so")
-        srcs = [os.path.join(SIM, f) for f in ("sim_zstd_encode.cpp", "sim_wave.hpp", "zstd_enc_model.c", "enc2_model.c", "deflate_enc_model.c")]
+        srcs = [os.path.join(SIM, f) for f in ("sim_zstd_encode.cpp", "sim_wave.hpp", "zstd_enc_model.c", "enc2_round.h", "deflate_enc_model.c")]
         srcs += [os.path.join(ROOT, "cramjam_amd", "csrc", f) for f in ("zstd_enc_wave.hpp", "zstd_fse_enc.h", "deflate_enc_wave.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             build_lib(so)
@@ -63,7 +63,7 @@ def lib():
 def build_lib(so=None, extra=()):
     so = so or os.path.join(SIM, "libsim_zstd_encode.so")
     objs = []
-    for src in ("zstd_enc_model.c", "deflate_enc_model.c"):      # (the first includes enc2_model.c: the matcher's round)
+    for src in ("zstd_enc_model.c", "deflate_enc_model.c"):      # (both include enc2_round.h: the matcher's round)
         objs.append(so + "." + src + ".o")
         subprocess.check_call(["gcc", "-O2", "-g", "-fPIC", "-Wall", "-Wno-unused-function", "-c", "-o", objs[-1], os.path.join(SIM, src)] + list(extra))
     build_sim(["sim_zstd_encode.cpp"] + objs, so, extra=extra)
@@ -357,6 +357,7 @@ def write_cases_file(path):
     """the file a stand-alone build of tests/hostsim/sim_zstd_encode.cpp (-DSIM_MAIN) runs: every case x flag at capacities the bound,
     exact, exact - 1 and 0, the alignments in turn, with the model's verdict and bytes.  Format: u32 count, then per case u32 flags, n, cap,
     input misalignment, output misalignment | i64 expected result | the input | the expected frame (result > 0).  Returns the count.
+    (Both models include the matcher's round, tests/hostsim/enc2_round.h, from their own directory.)
         python -c "import sys; sys.path.insert(0, 'tests'); import zstd_enc_cases as E; print(E.write_cases_file('cases.bin'))"
         gcc -O1 -g -fsanitize=address,undefined -c -o zmodel.o tests/hostsim/zstd_enc_model.c
         gcc -O1 -g -fsanitize=address,undefined -c -o dmodel.o tests/hostsim/deflate_enc_model.c
