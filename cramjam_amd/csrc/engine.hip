@@ -40,6 +40,9 @@ namespace {
 #endif
 constexpr uint32_t kWgsPerCu = CJ_L2_WGS_PER_CU;       // persistent workgroups of the LDS decoder per CU (tuning variants change it together with CJ_L2_WINDOW)
 
+// persistent workgroups of a batch on windows of `win` bytes: two per CU on 64 KiB windows, four / eight on the small ones
+uint32_t lds_grid(const cj_engine* e, uint32_t win) { return (win >= 65536u ? kWgsPerCu : cj::lz4_lds2_wgs_per_cu(win)) * (uint32_t)e->n_cu; }
+
 // scratch of the workgroup decoders (per-chunk verdicts, the chunk counter, record tables), shared by every call on the
 // engine: a call takes a turn at it (cj::ScratchTurn) before it overwrites them
 int lds_scratch(cj_engine* e, cj::ScratchTurn& turn, const cj::BatchArgs& a, hipStream_t s, bool with_sync) {
@@ -50,7 +53,10 @@ int lds_scratch(cj_engine* e, cj::ScratchTurn& turn, const cj::BatchArgs& a, hip
         (rc = turn.reserve(e->d_lanelist, list_bytes)) != 0) return rc;
     HIP_TRY(hipMemsetAsync(e->d_lanelist.p, 0, 256 + cj::kClaimBytes, s), CJ_E_NO_DEVICE);        // words [64 ..): the decoders' chunk counters
     if (e->n_cu == 0) HIP_TRY(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device), CJ_E_NO_DEVICE);
-    if (!e->d_tab.reserve(cj::lz4_lds2_tab_bytes(kWgsPerCu * (uint32_t)e->n_cu))) return CJ_E_OOM;
+    // the record tables: one slot per workgroup of the largest grid that any of the three windows launches
+    size_t tab_bytes = 0;
+    for (const uint32_t win : {65536u, 32768u, 16384u}) tab_bytes = std::max(tab_bytes, cj::lz4_lds2_tab_bytes(lds_grid(e, win), win));
+    if (!e->d_tab.reserve(tab_bytes)) return CJ_E_OOM;
     return 0;
 }
 
@@ -156,7 +162,7 @@ int launch_decode(cj_engine* e, cj_codec codec, const cj::BatchArgs& a_in, hipSt
         if (brc != 0) return brc;
     }
     uint32_t* lists = (uint32_t*)e->d_lanelist.p;
-    const uint32_t grid = (win >= 65536u ? kWgsPerCu : cj::lz4_lds2_wgs_per_cu(win)) * (uint32_t)e->n_cu;          // persistent workgroups: two per CU on 64 KiB windows
+    const uint32_t grid = lds_grid(e, win);
     if (fused) {
         cj::launch_lz4_decode_fused(a, e->d_pmeta.p, e->d_tab.p, lists + 64, grid, s, codec, win);
     } else {

@@ -745,7 +745,7 @@ __device__ __forceinline__ bool fused_parse(uint32_t a_in, uint32_t iend, uint32
                             if ((c[u].x & c[u].y) == 0xFFFFFFFFu || op > cap || !G::check(sq, op2, cap, fin) || idx >= total_seq) bad = true;
                             else {
                                 const uint32_t w = sq.mlen == 0u ? 0u : (sq.offset | (sq.mlen << 16));
-                                table2[idx] = make_uint2(c[u].x, (op & 0xffffu) | (w << 16));         // 8-byte record (lds2_body)
+                                table2[idx] = make_uint2(c[u].x, (op & 0xffffu) | (w << 16));         // 8-byte record (Lds2::Recs)
                                 near += (w != 0u && sq.offset < kNear) ? 1u : 0u;
                                 if (fin) { atomicAdd(&s_tot[17], 1u); s_tot[18] = op2; s_tot[19] = idx + 1u; }
                             }
@@ -805,7 +805,7 @@ __device__ __forceinline__ bool fused_parse(uint32_t a_in, uint32_t iend, uint32
                 if (!walk_step_carry<G>(rd, rd8, q, iend, sq, c4, true) || !G::check(sq, op2, cap, fin) || idx >= total_seq) bad = true;
                 else {
                     const uint32_t w = sq.mlen == 0u ? 0u : ((sq.offset & 0xffffu) | (sq.mlen << 16));       // (a Snappy stream may END with a copy)
-                    table2[idx] = make_uint2(sq.lit_at | (sq.lit << 16), (op & 0xffffu) | (w << 16));      // 8-byte record (lds2_body)
+                    table2[idx] = make_uint2(sq.lit_at | (sq.lit << 16), (op & 0xffffu) | (w << 16));      // 8-byte record (Lds2::Recs)
                     near += (w != 0u && sq.offset < kNear) ? 1u : 0u;
                     op = op2;
                     if (fin) { final_op = op; saw_last = true; q = kPosEnd; }
