@@ -733,13 +733,18 @@ int cj_memcpy_d2d(cj_engine* e, void* d, const void* s, size_t n) {
     if (!e) return CJ_E_BAD_ARG;
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
     if (n) HIP_TRY(hipMemcpy(d, s, n, hipMemcpyDeviceToDevice), CJ_E_NO_DEVICE);
+    if (n) HIP_TRY(hipStreamSynchronize(nullptr), CJ_E_NO_DEVICE);      // (as cj_memset_dev)
     return 0;
 }
 
+// hipMemset of device memory returns before the bytes are set, and the engine's stream is non-blocking: it does not wait for the
+// null stream.  A batch enqueued right behind the call could write its output first and have it overwritten with `v`.  So the
+// helper waits, like its siblings: when it returns the bytes are set.
 int cj_memset_dev(cj_engine* e, void* d, int v, size_t n) {
     if (!e) return CJ_E_BAD_ARG;
     HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
     if (n) HIP_TRY(hipMemset(d, v, n), CJ_E_NO_DEVICE);
+    if (n) HIP_TRY(hipStreamSynchronize(nullptr), CJ_E_NO_DEVICE);
     return 0;
 }
 

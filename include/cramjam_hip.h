@@ -615,7 +615,8 @@ CJ_API int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n_ch
 CJ_API int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n_chunks, const uint8_t* const* in_ptrs, const size_t* in_lens,
                                      int64_t* result);
 
-/* Thin device-memory helpers so C / ctypes callers need no HIP binding of their own. */
+/* Thin device-memory helpers so C / ctypes callers need no HIP binding of their own.  Each returns when its bytes are in place
+ * (cj_memset_dev and cj_memcpy_d2d wait for the null stream: an engine's stream is non-blocking and would not). */
 CJ_API void* cj_device_alloc(cj_engine* e, size_t bytes);
 CJ_API void  cj_device_free(cj_engine* e, void* p);
 CJ_API int   cj_memcpy_h2d(cj_engine* e, void* dst_dev, const void* src_host, size_t bytes);

@@ -28,10 +28,11 @@ extern "C" long long sim_deflate_decode(int wrap, int size, const unsigned char*
 
 #ifdef SIM_MAIN
 // per case u32 wrap, size, n, cap, mis | i64 expected result | stream | expected bytes (decode mode, result > 0)
+// (a second argument `device`: the device-load mode, and the stream comes with the neighbour bytes of its first and last dword)
 int main(int argc, char** argv) {
     return cj::sim_cases_main(argc, argv, 5, [](FILE* f, const uint32_t* h, int64_t want, long long& got) {
         const size_t nexp = (!h[1] && want > 0) ? (size_t)want : 0;
-        cj::SimBlock in(f, h[2], h[4]), exp(f, nexp), out(nullptr, h[3]);
+        cj::SimBlock in(f, h[2], h[4], cj::sim_ring), exp(f, nexp), out(nullptr, h[3]);
         if (!in.ok || !exp.ok) return 2;
         got = sim_deflate_decode((int)h[0], (int)h[1], in.p, h[2], out.p, h[3]);
         return (int)(got != want || (nexp && memcmp(out.p, exp.p, nexp) != 0));

@@ -14,10 +14,11 @@ extern "C" long long sim_lz4_dict_decode(const unsigned char* in, unsigned int n
 
 #ifdef SIM_MAIN
 // per case u32 n, cap, dict_len, mis_in, mis_dict | i64 expected result | stream | dictionary | expected bytes
+// (a second argument `device`: the device-load mode, and the stream comes with the neighbour bytes of its first and last dword)
 int main(int argc, char** argv) {
     return cj::sim_cases_main(argc, argv, 5, [](FILE* f, const uint32_t* h, int64_t want, long long& got) {
         const size_t nexp = want > 0 ? (size_t)want : 0;
-        cj::SimBlock in(f, h[0], h[3]), d(f, h[2], h[4]), exp(f, nexp), out(nullptr, h[1]);
+        cj::SimBlock in(f, h[0], h[3], cj::sim_ring), d(f, h[2], h[4]), exp(f, nexp), out(nullptr, h[1]);
         if (!in.ok || !d.ok || !exp.ok) return 2;
         got = sim_lz4_dict_decode(in.p, h[0], out.p, h[1], d.p, h[2]);
         return (int)(got != want || (nexp && memcmp(out.p, exp.p, nexp) != 0));

@@ -16,6 +16,7 @@ extern "C" void standin_arena(unsigned char* dst) { memcpy(dst, A, 256); }
 // a, b, c: offsets are relative to the op's own range (wave_copy's source: to the arena)
 extern "C" long long standin(int op, long a, long b, long c) {
     for (int i = 0; i < 256; i++) A[i] = (uint8_t)i;
+    sim_device_loads = false;
     sim_in.set(A + IN, IN_N); sim_src2.set(A + SRC2, SRC2_N); sim_out.set(A + OUT, OUT_N); sim_lds.set(A + LDS, LDS_N); sim_rec.set(A + REC, REC_N);
     return sim_run([&]() -> long long {
         switch (op) {
@@ -41,6 +42,8 @@ extern "C" long long standin(int op, long a, long b, long c) {
         case 19: { LaneU64 x = {}; x[(uint32_t)a] = 7u; return (long long)x.v[a & 63]; }
         case 20: { LaneU32 x, before; for (uint32_t l = 0; l < 64u; l++) x[l] = l + 1u; const uint32_t t = lane_excl_add(x, before); return (long long)t << 32 | before[(uint32_t)a]; }
         case 21: return rec_ld((const Rec*)(A + REC + a), (uint32_t)b).d;      // a: bytes from the range's start, b: the record's index
+        // the device-load mode: a stream of b bytes that begins a (0..3) bytes behind the dword boundary A + IN; c: the position relative to it
+        case 22: { InWindow w; w.base = A + IN; w.iend = (uint32_t)(a + b); w.anchor(0); sim_device_loads = true; return w.fetch32((uint32_t)c); }
         }
         return -1;
     });

@@ -8,8 +8,10 @@
 //     sim_rec     the encoder's record slot (its rec_ld)
 // A violation is sim_fail(): it leaves the decoder for the sim_run() that called it, which returns SIM_BOUNDS (-9999, no CJ_E_* code),
 // so that a test fails by name and the process lives.  Bytes that the register window would load from beyond the stream read as 0xEE,
-// so that a decision taken on them shows; sim_new_block() gives LDS and slots as heap blocks of exactly their size filled with 0xA5,
-// as they are with whatever ran before.  A CJ_LANES body runs for lanes 0..63 one after another: the contract's rule (no body reads
+// so that a decision taken on them shows — or, with sim_set_device_loads(1), as the device's InWindow::load_row (cj_common.hpp) shows them:
+// the memory's own bytes inside any dword that starts below iend (the up to 3 bytes below a misaligned stream and the up to 3 behind
+// its end are its neighbours'), 0 in every dword behind.  The caller then owns those bytes (tests/test_neighbours_model.py).
+// sim_new_block() gives LDS and slots as heap blocks of exactly their size filled with 0xA5, as they are with whatever ran before.  A CJ_LANES body runs for lanes 0..63 one after another: the contract's rule (no body reads
 // what another lane wrote in the same body) is what makes that the wavefront's result.
 #pragma once
 #include <setjmp.h>
@@ -34,6 +36,9 @@ struct SimRange {
 static SimRange sim_in, sim_out, sim_src2, sim_lds, sim_rec;
 static jmp_buf sim_jmp;
 static bool sim_armed = false;
+static bool sim_device_loads = false;        // what InWindow reads outside the stream: false 0xEE, true what load_row loads
+static bool sim_ring = false;                // SIM_MAIN: the cases file holds each stream with the neighbour bytes of its edge dwords
+extern "C" __attribute__((used, weak, visibility("default"))) void sim_set_device_loads(int on) { sim_device_loads = on != 0; }
 
 [[noreturn]] static void sim_fail() {
     if (!sim_armed) { fprintf(stderr, "sim_fail() outside sim_run()\n"); abort(); }      // (an entry point's mistake, not a decoder's)
@@ -68,6 +73,10 @@ struct InWindow {
     uint32_t fetch32(uint32_t pos) const {
         if (pos - wpos > 507u) sim_fail();                              // the register window's precondition
         uint32_t v = 0;
+        if (sim_device_loads) {                                         // base is a dword boundary: the dword of byte p starts at p & ~3
+            for (uint32_t k = 0; k < 4; k++) v |= (uint32_t)(((pos + k) & ~3u) < iend ? base[pos + k] : 0) << (8 * k);
+            return v;
+        }
         for (uint32_t k = 0; k < 4; k++) v |= (uint32_t)(base + pos + k >= sim_in.lo && pos + k < iend ? base[pos + k] : 0xEE) << (8 * k);
         return v;
     }
@@ -121,11 +130,17 @@ static uint32_t lane_excl_add(LaneU32& x, LaneU32& before) {
 
 // ---- SIM_MAIN: a stand-alone program over a file of cases, the form a sanitizer build takes ------------------------------------------
 // A heap block of exactly mis + n bytes, so that a sanitizer sees each edge; p = its byte mis.  With a file, bytes [mis, mis + n) are
-// read from it (ok: they were there).
+// read from it (ok: they were there).  ring: the block is the dwords the stream touches and nothing more — mis & 3 bytes in front and
+// the bytes up to the next dword boundary behind, all read from the file: what load_row may load, and a sanitizer sees one byte more.
 struct SimBlock {
     uint8_t *mem, *p;
     bool ok;
-    SimBlock(FILE* f, size_t n, size_t mis = 0) : mem((uint8_t*)malloc(mis + n ? mis + n : 1)), p(mem + mis), ok(!f || n == 0 || fread(p, 1, n, f) == n) {}
+    SimBlock(FILE* f, size_t n, size_t mis = 0, bool ring = false) {
+        const size_t front = ring ? (mis & 3u) : mis, all = ring ? (front + n + 3u) & ~(size_t)3u : front + n;
+        mem = (uint8_t*)malloc(all ? all : 1);
+        p = mem + front;
+        ok = ring ? (all == 0 || fread(mem, 1, all, f) == all) : (!f || n == 0 || fread(p, 1, n, f) == n);
+    }
     SimBlock(const SimBlock&) = delete;
     ~SimBlock() { free(mem); }
 };
@@ -134,6 +149,7 @@ struct SimBlock {
 template <class F>
 static int sim_cases_main(int argc, char** argv, uint32_t nhdr, F&& one) {
     FILE* f = argc < 2 ? nullptr : fopen(argv[1], "rb");
+    sim_ring = sim_device_loads = argc > 2 && strcmp(argv[2], "device") == 0;
     uint32_t count = 0, bad = 0, h[8];
     if (!f || nhdr > 8u || fread(&count, 4, 1, f) != 1) return 2;
     for (uint32_t c = 0; c < count; c++) {

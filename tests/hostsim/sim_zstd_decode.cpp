@@ -29,10 +29,11 @@ extern "C" unsigned int sim_zstd_lds_bytes(void) { return (unsigned int)sizeof(c
 
 #ifdef SIM_MAIN
 // per case u32 size, n, cap, mis | i64 expected result | stream | expected bytes (decode mode, result > 0)
+// (a second argument `device`: the device-load mode, and the stream comes with the neighbour bytes of its first and last dword)
 int main(int argc, char** argv) {
     return cj::sim_cases_main(argc, argv, 4, [](FILE* f, const uint32_t* h, int64_t want, long long& got) {
         const size_t nexp = (!h[0] && want > 0) ? (size_t)want : 0;
-        cj::SimBlock in(f, h[1], h[3]), exp(f, nexp), out(nullptr, h[2]);
+        cj::SimBlock in(f, h[1], h[3], cj::sim_ring), exp(f, nexp), out(nullptr, h[2]);
         if (!in.ok || !exp.ok) return 2;
         got = sim_zstd_decode((int)h[0], in.p, h[1], out.p, h[2]);
         return (int)(got != want || (nexp && memcmp(out.p, exp.p, nexp) != 0));
