@@ -129,7 +129,12 @@ BENCH_SYMBOLS = {
     "cj_debug_big_parse": (C.c_int64, [_int, _u32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "cj_bench_compare": (_int, [_vp, _vp, _vp, C.c_uint64, _u32, C.c_uint64, _u32, _vp, _vp]),
     "cj_debug_big_scratch_bytes": (C.c_uint64, [_vp]),
-    "cj_debug_xxh32_device": (_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "cj_debug_scratch_count": (_int, []),
+    "cj_debug_scratch_name": (C.c_char_p, [_int]),
+    "cj_debug_scratch_carries_state": (_int, [_int]),
+    "cj_debug_scratch_fill": (_int, [_vp, _u32, _vp]),
+    "cj_debug_scratch_peek": (_int, [_vp, _int, C.c_uint64, _vp, _sz]),
+    "cj_debug_xxh32_device":(_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "cj_debug_blosc_filter": (_int, [_vp, _int, _u32, _u32, _vp, _vp, C.c_uint64, C.c_uint64, _sz, _vp]),
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),

@@ -188,7 +188,48 @@ struct cj_engine {                 // (members are destroyed last to first: the 
 };
 
 namespace cj {
-constexpr size_t kGridChunks = (size_t)1 << 22;      // chunks per launch of a wavefront-per-chunk kernel: a grid stays below 2^32 threads
+// Every DevBuf and PinnedBuf of cj_engine, once (tests/test_scratch_contents_model.py holds this list to the struct above and to the table
+// of DESIGN.md §5.10b): its name, the member, the mutex its users hold (kOwnMu: `mu` alone; else the Scratch, whose `free` event its last
+// user recorded), and whether it CARRIES STATE between calls by design — such a buffer is not scratch and is never filled.  The
+// cj_debug_scratch_* exports (engine.hip) walk this one table, so what they name, fill and read back cannot disagree.
+enum BufOwner { kOwnMu, kOwnScratch, kOwnFb, kOwnDictStage, kOwnDeflateSlots, kOwnZstdSlots, kOwnZstdEncSlots };
+struct EngineBuf {
+    const char* name;
+    DevBuf cj_engine::* dev;       // one of the two is set
+    PinnedBuf cj_engine::* pin;
+    BufOwner owner;
+    bool carries_state;
+};
+#define CJ_DEV(m, own) {#m, &cj_engine::m, nullptr, own, false}
+#define CJ_PIN(m, own, state) {#m, nullptr, &cj_engine::m, own, state}
+inline constexpr EngineBuf kEngineBufs[] = {
+    CJ_DEV(d_in, kOwnMu), CJ_DEV(d_out, kOwnMu), CJ_DEV(d_meta, kOwnMu),
+    CJ_DEV(d_sync, kOwnScratch), CJ_DEV(d_pmeta, kOwnScratch), CJ_DEV(d_lanelist, kOwnScratch),
+    CJ_PIN(h_in, kOwnMu, false), CJ_PIN(h_out, kOwnMu, false), CJ_PIN(h_res, kOwnMu, false),
+    CJ_DEV(d_frame, kOwnMu), CJ_DEV(d_tab, kOwnScratch),
+    CJ_DEV(d_biglist, kOwnScratch), CJ_DEV(d_bigrecs, kOwnScratch), CJ_DEV(d_bigmisc, kOwnScratch), CJ_DEV(d_bigslabtab, kOwnScratch),
+    CJ_PIN(h_count, kOwnScratch, true),       // plan_big (engine.hip) reads the counts that EARLIER calls posted here
+    CJ_DEV(d_big, kOwnMu), CJ_DEV(d_bigtab, kOwnMu),
+    CJ_DEV(d_fb, kOwnFb), CJ_PIN(h_fb, kOwnFb, false),
+    CJ_DEV(d_dict_stage, kOwnDictStage), CJ_DEV(d_dict, kOwnMu),
+    CJ_DEV(d_deflate_slots, kOwnDeflateSlots), CJ_DEV(d_zstd_slots, kOwnZstdSlots), CJ_DEV(d_zstd_enc_slots, kOwnZstdEncSlots),
+};
+#undef CJ_DEV
+#undef CJ_PIN
+constexpr int kEngineBufCount = (int)(sizeof(kEngineBufs) / sizeof(kEngineBufs[0]));
+inline Scratch* buf_scratch(cj_engine* e, BufOwner o) {
+    switch (o) {
+    case kOwnScratch: return &e->scratch;
+    case kOwnFb: return &e->fb;
+    case kOwnDictStage: return &e->dict_stage;
+    case kOwnDeflateSlots: return &e->deflate_slots;
+    case kOwnZstdSlots: return &e->zstd_slots;
+    case kOwnZstdEncSlots: return &e->zstd_enc_slots;
+    default: return nullptr;
+    }
+}
+
+constexpr size_t kGridChunks = (size_t)1 << 22;     // chunks per launch of a wavefront-per-chunk kernel: a grid stays below 2^32 threads
 cj_engine* default_engine();     // lazily created on device 0 (tuning builds: $CJ_DEVICE); nullptr when no device is usable
 // submit one batch on stream s (slices very large decode batches); 0 or CJ_E_*
 int launch(cj_engine* e, cj_codec codec, cj_op op, const BatchArgs& a, hipStream_t s);

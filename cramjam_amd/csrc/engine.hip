@@ -755,3 +755,131 @@ extern "C" uint64_t cj_debug_big_scratch_bytes(cj_engine* e) {
     std::lock_guard<std::mutex> lock(e->scratch.mu);
     return (uint64_t)e->d_biglist.cap + e->d_bigrecs.cap + e->d_bigmisc.cap + e->d_bigslabtab.cap;
 }
+
+// ---- tests: what the engine's buffers HOLD between calls (tests/test_scratch_contents_gpu.py) --------------------------
+// Every word a kernel or the host reads from the engine's scratch has to be written earlier in the same call; these exports put a known
+// pattern into every buffer of cj::kEngineBufs that is not a state carrier, so that a reader in front of its writer shows in a result.
+namespace {
+
+// word w of a buffer filled with `pattern` (>= 2); tests/test_scratch_contents_gpu.py computes the same
+__host__ __device__ inline uint32_t fill_word(uint64_t w, uint32_t pattern) {
+    uint32_t h = (uint32_t)w * 0x9E3779B1u ^ (uint32_t)(w >> 32) * 0x85EBCA77u ^ pattern * 0xC2B2AE3Du;
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    return h;
+}
+
+__global__ __launch_bounds__(256) void fill_words_kernel(uint8_t* p, uint64_t bytes, uint32_t pattern) {
+    const uint64_t words = (bytes + 3u) / 4u;
+    for (uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x; w < words; w += (uint64_t)gridDim.x * 256u) {
+        const uint32_t h = fill_word(w, pattern);
+        if (4u * w + 4u <= bytes) reinterpret_cast<uint32_t*>(p)[w] = h;
+        else for (uint64_t b = 4u * w; b < bytes; b++) p[b] = (uint8_t)(h >> (8u * (b & 3u)));       // (a capacity that is no multiple of 4)
+    }
+}
+
+void fill_host(uint8_t* p, size_t bytes, uint32_t pattern) {
+    if (pattern < 2) { std::memset(p, pattern ? 0xFF : 0x00, bytes); return; }
+    for (size_t w = 0; 4 * w < bytes; w++) {
+        const uint32_t h = fill_word(w, pattern);
+        std::memcpy(p + 4 * w, &h, std::min<size_t>(4, bytes - 4 * w));      // (little-endian hosts: byte b of a word = h >> 8 b, as on the device)
+    }
+}
+
+// enqueue on s; the caller waits
+int fill_device(void* p, size_t bytes, uint32_t pattern, hipStream_t s) {
+    if (pattern < 2) { HIP_TRY(hipMemsetAsync(p, pattern ? 0xFF : 0x00, bytes, s), CJ_E_NO_DEVICE); return 0; }
+    const uint64_t words = (bytes + 3) / 4;
+    hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)std::min<uint64_t>((words + 255) / 256, 16384)), dim3(256), 0, s, (uint8_t*)p, (uint64_t)bytes, pattern);
+    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
+    return 0;
+}
+
+// the buffers of one owner (its mutex held by the caller): wait for the scratch's last user, fill, and wait until the bytes are set — the
+// engine's stream is non-blocking, a batch enqueued right behind the call must find them (the comment at cj_memset_dev)
+int fill_owned(cj_engine* e, cj::BufOwner owner, uint32_t pattern, uint64_t* filled) {
+    if (cj::Scratch* sc = cj::buf_scratch(e, owner)) {
+        if (sc->free) HIP_TRY(hipEventSynchronize(sc->free), CJ_E_NO_DEVICE);
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);            // (the calls under `mu` alone wait for their own work before they return)
+    }
+    for (int i = 0; i < cj::kEngineBufCount; i++) {
+        const cj::EngineBuf& b = cj::kEngineBufs[i];
+        if (b.owner != owner || b.carries_state) continue;
+        if (b.dev) {
+            const cj::DevBuf& d = e->*(b.dev);
+            if (!d.p || !d.cap) continue;
+            const int rc = fill_device(d.p, d.cap, pattern, e->stream);
+            if (rc != 0) return rc;
+            filled[i] = d.cap;
+        } else {
+            const cj::PinnedBuf& h = e->*(b.pin);
+            if (!h.p || !h.cap) continue;
+            fill_host(h.p, h.cap, pattern);
+            filled[i] = h.cap;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), CJ_E_NO_DEVICE);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cj_debug_scratch_count(void) { return cj::kEngineBufCount; }
+
+const char* cj_debug_scratch_name(int i) { return i >= 0 && i < cj::kEngineBufCount ? cj::kEngineBufs[i].name : nullptr; }
+
+int cj_debug_scratch_carries_state(int i) { return i >= 0 && i < cj::kEngineBufCount ? (cj::kEngineBufs[i].carries_state ? 1 : 0) : -1; }
+
+int cj_debug_scratch_fill(cj_engine* e, uint32_t pattern, uint64_t* filled) {
+    if (!filled) return CJ_E_BAD_ARG;
+    if (!e) e = cj::default_engine();
+    if (!e) return CJ_E_NO_DEVICE;
+    for (int i = 0; i < cj::kEngineBufCount; i++) filled[i] = 0;
+    // the LOCK ORDER of cj_engine.hpp: mu -> fb -> {scratch, zstd_slots, deflate_slots} one after another; dict_stage and zstd_enc_slots under mu alone
+    std::lock_guard<std::mutex> lock(e->mu);
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    if (!e->stream.create()) return CJ_E_NO_DEVICE;
+    int rc = fill_owned(e, cj::kOwnMu, pattern, filled);
+    if (rc != 0) return rc;
+    // (the host vector of the batch rows: lay_out and the frame paths assign() it before they read it)
+    uint8_t* hm = reinterpret_cast<uint8_t*>(e->h_meta.data());
+    fill_host(hm, e->h_meta.size() * 8, pattern);
+    {
+        std::lock_guard<std::mutex> fb(e->fb.mu);
+        for (const cj::BufOwner inner : {cj::kOwnScratch, cj::kOwnZstdSlots, cj::kOwnDeflateSlots}) {
+            std::lock_guard<std::mutex> in(cj::buf_scratch(e, inner)->mu);
+            if ((rc = fill_owned(e, inner, pattern, filled)) != 0) return rc;
+        }
+        if ((rc = fill_owned(e, cj::kOwnFb, pattern, filled)) != 0) return rc;
+    }
+    for (const cj::BufOwner alone : {cj::kOwnDictStage, cj::kOwnZstdEncSlots}) {
+        std::lock_guard<std::mutex> in(cj::buf_scratch(e, alone)->mu);
+        if ((rc = fill_owned(e, alone, pattern, filled)) != 0) return rc;
+    }
+    return 0;
+}
+
+int cj_debug_scratch_peek(cj_engine* e, int i, uint64_t off, void* out, size_t n) {
+    if (i < 0 || i >= cj::kEngineBufCount || (n && !out)) return CJ_E_BAD_ARG;
+    if (!e) e = cj::default_engine();
+    if (!e) return CJ_E_NO_DEVICE;
+    const cj::EngineBuf& b = cj::kEngineBufs[i];
+    std::lock_guard<std::mutex> lock(e->mu);
+    HIP_TRY(hipSetDevice(e->device), CJ_E_NO_DEVICE);
+    cj::Scratch* sc = cj::buf_scratch(e, b.owner);
+    std::unique_lock<std::mutex> in;
+    if (sc) {
+        in = std::unique_lock<std::mutex>(sc->mu);
+        if (sc->free) HIP_TRY(hipEventSynchronize(sc->free), CJ_E_NO_DEVICE);
+    }
+    const size_t cap = b.dev ? (e->*(b.dev)).cap : (e->*(b.pin)).cap;
+    if (off > cap || n > cap - off) return CJ_E_BAD_ARG;
+    if (n == 0) return 0;
+    if (b.dev) HIP_TRY(hipMemcpy(out, (const uint8_t*)(e->*(b.dev)).p + off, n, hipMemcpyDeviceToHost), CJ_E_NO_DEVICE);
+    else std::memcpy(out, (e->*(b.pin)).p + off, n);
+    return 0;
+}
+
+}  // extern "C"

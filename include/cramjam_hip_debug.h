@@ -27,6 +27,20 @@ CJ_API int64_t cj_debug_big_parse(int codec, uint32_t flags, const uint8_t* in, 
 /* bytes of device scratch the engine holds for CJ_FLAG_BIG_CHUNKS batches (list, record areas, summaries, the slab decoder's tables) */
 CJ_API uint64_t cj_debug_big_scratch_bytes(cj_engine* e);
 
+/* What the engine's buffers hold between calls (tests/test_scratch_contents_gpu.py).  The list is every DevBuf and
+ * PinnedBuf member of cj_engine, by index; e == NULL names the default engine, the one behind the single-buffer and frame calls.
+ * _name: the member's name ("d_pmeta"), NULL outside [0, count).  _carries_state: 1 for a buffer that carries state between calls by
+ * design ("h_count": the big-chunk counts earlier calls posted) and is therefore never filled, 0 for scratch, -1 outside the list.
+ * _fill: every listed buffer that is not a state carrier, over its whole capacity, and the host vector of the batch rows — pattern 0: 0x00
+ * bytes, 1: 0xFF bytes, >= 2: a hash of (word index, pattern) in every 32-bit word; it takes the engine's mutexes in their documented order,
+ * waits for each scratch's last user, changes no pointer and no capacity, and returns once the bytes are set.  filled[i] (count entries) =
+ * the bytes written to buffer i, 0 for one that is not allocated or carries state.  _peek: n bytes of buffer i from offset off, to the host. */
+CJ_API int cj_debug_scratch_count(void);
+CJ_API const char* cj_debug_scratch_name(int i);
+CJ_API int cj_debug_scratch_carries_state(int i);
+CJ_API int cj_debug_scratch_fill(cj_engine* e, uint32_t pattern, uint64_t* filled);
+CJ_API int cj_debug_scratch_peek(cj_engine* e, int i, uint64_t off, void* out, size_t n);
+
 /* XXH32 (seed 0) of n device streams d_base + d_off[i] .. + d_len[i] into d_out[i] by the frame batches' one-wavefront-per-stream kernel;
  * synchronous (tests hold it to the reference algorithm at every alignment) */
 CJ_API int cj_debug_xxh32_device(cj_engine* e, const uint8_t* d_base, const uint64_t* d_off, const uint64_t* d_len, uint32_t* d_out, size_t n);
