@@ -266,6 +266,9 @@ class Engine:
         check(lib().cj_memcpy_d2h(self.h, out.ctypes.data, dptr, out.nbytes))
         return out
 
+    def memset(self, dptr, value, nbytes):
+        check(lib().cj_memset_dev(self.h, dptr, value, nbytes))
+
     def sync(self):
         check(lib().cj_engine_sync(self.h))
 

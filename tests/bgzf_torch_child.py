@@ -13,24 +13,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import bgzf_model as M  # noqa: E402
+import device_batch as DB  # noqa: E402
 import deflate_cases as D  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
-
-
-def pack(chunks):
-    ln = np.array([len(c) for c in chunks], np.int64)
-    off = np.concatenate([[0], np.cumsum((ln + 31) & ~15)[:-1]]).astype(np.int64)
-    buf = np.zeros(int(off[-1] + ln[-1]) + 64, np.uint8)
-    for k, c in enumerate(chunks):
-        buf[int(off[k]):int(off[k]) + len(c)] = np.frombuffer(c, np.uint8)
-    return buf, off, ln
 
 
 def round_trip(give_result):
     text = D.words(150000, 91)
     chunks = [text[:n] for n in (0, 1, 4000, 65280, 65281, 150000)]
     n = len(chunks)
-    buf, off, ln = pack(chunks)
+    buf, off, ln = DB.pack(chunks, mis=0, dtype=np.int64)
     cap = np.array([batch.bgzf_compress_bound(int(x)) for x in ln], np.int64)
     ooff = np.concatenate([[0], np.cumsum(cap)[:-1]]).astype(np.int64)
     side = torch.cuda.Stream()
@@ -58,7 +50,7 @@ def round_trip(give_result):
 def model_cases():
     names = [k for k in M.cases()][::3]
     streams = [M.cases()[k][1] for k in names]
-    buf, off, ln = pack(streams)
+    buf, off, ln = DB.pack(streams, mis=0, dtype=np.int64)
     sizes = np.array([M.sizes(s) for s in streams], np.int64)
     cap = np.maximum(sizes, 0)
     ooff = np.concatenate([[0], np.cumsum(cap + 16)[:-1]]).astype(np.int64)

@@ -6,9 +6,8 @@ import json
 import os
 import subprocess
 
-import numpy as np
-
 import blosc_model as M
+import device_batch as DB
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _doc = None
@@ -82,12 +81,15 @@ def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
 
 
-def pack(chunks, pad=16):
+def pack(chunks):
     """the chunks in one array, 16-byte aligned with a gap behind each: (blob, offsets, lengths)"""
-    off, run = [], 0
-    for c in chunks:
-        off.append(run); run += (len(c) + pad - 1) // pad * pad + pad
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    return blob, np.array(off, np.uint64), np.array([len(c) for c in chunks], np.uint64)
+    return DB.pack(chunks, mis=0)
+
+
+def device_batch(e, N, chunks, caps, slots, flags, guard=0):
+    """cj_blosc_batch_device (decode) in the harness's guarded run (tests/device_batch.py); slot i lies `guard` bytes behind slot
+    i - 1's end, the whole output is filled with 0xA5 first: (results, the output bytes, the slots' offsets)"""
+    blob, off, ln = pack(chunks)
+    ooff, total = DB.out_slots(caps, guard=guard, slots=slots, tail=max(guard, 64) - guard)
+    call = lambda i, o, l, out, oo, oc, r: N.check(N.lib().cj_blosc_batch_device(e.h, 0, i, o, l, out, oo, oc, r, len(chunks), None, flags, None))
+    return DB.run(e, call, blob, off, ln, ooff, caps, total) + (ooff,)

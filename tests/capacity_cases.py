@@ -267,3 +267,38 @@ def big_cases(codec):
     if codec == "lz4":
         return [_case(s, s["bytes"], c, *_lz4_raw(s["bytes"], c)) for c in s["caps"]]
     return [_case(s, varint(c) + s["elements"], c, *oracle.snappy_decompress(varint(c) + s["elements"], c)) for c in s["caps"]]
+
+
+def _paths():
+    """every LZ4 / Snappy decoder path of a device-resident batch as (flags, window) test parameters: one wavefront / one lane per
+    chunk, the workgroup decoder behind the parse kernel and with the parse inside it, the default pipeline, the 32 KiB and 16 KiB
+    windows with each placement of the parse"""
+    import pytest
+    from cramjam_amd import _native as N
+    WAVE, LANE, LDS = N.FLAG_FORCE_WAVE_PER_CHUNK, N.FLAG_FORCE_LANE_PER_CHUNK, N.FLAG_FORCE_LDS_PER_CHUNK
+    PK, FUSED, LE32, LE16 = N.FLAG_FORCE_PARSE_KERNEL, N.FLAG_FORCE_FUSED_PARSE, N.FLAG_CHUNKS_LE_32K, N.FLAG_CHUNKS_LE_16K
+    return [pytest.param(WAVE, 65536, id="wave-per-chunk"), pytest.param(LANE, 65536, id="lane-per-chunk"),
+            pytest.param(LDS | PK, 65536, id="lds+parse-kernel"), pytest.param(LDS | FUSED, 65536, id="lds+fused-parse"), pytest.param(0, 65536, id="default"),
+            pytest.param(LE32, 32768, id="le32k"), pytest.param(LE32 | PK, 32768, id="le32k+parse-kernel"), pytest.param(LE32 | FUSED, 32768, id="le32k+fused-parse"),
+            pytest.param(LE16, 16384, id="le16k"), pytest.param(LE16 | PK, 16384, id="le16k+parse-kernel"), pytest.param(LE16 | FUSED, 16384, id="le16k+fused-parse")]
+
+
+PATHS = _paths()
+
+
+def lz4_bodies(win):
+    return LZ4_BODIES if win >= 65536 else LZ4_BODIES[:2]              # (the body with the 300-byte runs: 64 KiB window only)
+
+
+def run_and_check(eng, codec, flags, key, cases, dictionary=None):
+    """one device-resident decode batch over a case list on the harness (tests/device_batch.py): the oracle's result and bytes, both
+    guards intact — accepted or refused —, [result, cap) untouched where the chunk was accepted; returns (results, output, slot offsets)"""
+    import device_batch as DB
+    from cramjam_amd import _native as N
+    n = len(cases)
+    if dictionary is None:
+        call = lambda i, o, l, out, oo, oc, r: eng.batch_device(codec, N.OP_DECOMPRESS, flags, n, i, o, l, out, oo, oc, r)
+    else:
+        call = lambda i, o, l, out, oo, oc, r, d: N.check(N.lib().cj_dict_batch_device(eng.h, codec, N.OP_DECOMPRESS, flags, n, i, o, l, out, oo, oc, r, d, len(dictionary), None))
+    tag = lambda i, got: (key, hex(flags), cases[i]["stream"], "cap", cases[i]["cap"], "U", cases[i]["U"], "got", got, "want", cases[i]["result"])
+    return DB.run_cases(eng, key, cases, call, tag, dictionary=dictionary)

@@ -480,3 +480,15 @@ def sim_decode(wrap, s, cap, mis=0, size=False):
     out = (C.c_ubyte * max(cap, 1))()
     r = L.sim_deflate_decode(wrap, 1 if size else 0, at, len(s), out, cap)
     return r, (bytes(out[:r]) if r > 0 and not size else b"")
+
+
+def device_call(e, N, wrap, chunks, caps, sizes=False):
+    """cj_deflate_batch_device (sizes: cj_deflate_batch_sizes_device) in the harness's guarded run (tests/device_batch.py): chunks at
+    every misalignment, 64 guard bytes around every slot, the output filled with 0xA5 first: (results, output, offsets)"""
+    import device_batch as DB
+    n, L = len(chunks), N.lib()
+    if sizes:
+        call = lambda i, o, l, out, oo, oc, r: N.check(L.cj_deflate_batch_sizes_device(e.h, wrap, 0, n, i, o, l, r, None))
+    else:
+        call = lambda i, o, l, out, oo, oc, r: N.check(L.cj_deflate_batch_device(e.h, wrap, N.OP_DECOMPRESS, 0, n, i, o, l, out, oo, oc, r, None))
+    return DB.run_chunks(e, call, chunks, caps)

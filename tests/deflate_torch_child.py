@@ -10,22 +10,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import deflate_cases as D  # noqa: E402
+import device_batch as DB  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
-
-
-def _pack(blobs, gap=16):
-    ln = np.array([len(b) for b in blobs], np.int64)
-    off = np.concatenate([[0], np.cumsum((ln + gap + 15) & ~15)[:-1]]).astype(np.int64)
-    buf = np.zeros(int(off[-1] + ln[-1]) + 64, np.uint8)
-    for k, b in enumerate(blobs):
-        buf[int(off[k]):int(off[k]) + len(b)] = np.frombuffer(b, np.uint8)
-    return buf, off, ln
 
 
 def calls(wrap):
     cs = D.cases(wrap)
     name = D.WRAP_NAME[wrap]
-    buf, off, ln = _pack([c["bytes"] for c in cs])
+    buf, off, ln = DB.pack([c["bytes"] for c in cs], mis=0, dtype=np.int64)
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
         t_in = torch.from_numpy(buf).cuda()

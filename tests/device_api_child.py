@@ -7,17 +7,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import device_batch as DB  # noqa: E402  (beside this script)
 import oracle  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
-
-
-def _pack(blobs, pad):
-    ln = np.array([len(b) for b in blobs], np.uint64)
-    off = np.concatenate([[0], np.cumsum((ln + pad + 15) & ~np.uint64(15))[:-1]]).astype(np.uint64)
-    buf = np.zeros(int(off[-1] + ln[-1]) + 64, np.uint8)
-    for k, b in enumerate(blobs):
-        buf[int(off[k]):int(off[k]) + len(b)] = np.frombuffer(b, np.uint8)
-    return buf, off, ln
 
 
 def test_24k_chunks_from_torch_tensors_decode_to_the_oracles_bytes(codec):
@@ -25,7 +17,7 @@ def test_24k_chunks_from_torch_tensors_decode_to_the_oracles_bytes(codec):
     raws = [oracle.synth_v1(65536 if i % 7 else 40000 + 13 * i, 900 + i) for i in range(U)]
     comp = [(oracle.lz4_compress_raw(r)[1] if codec == "lz4" else oracle.snappy_compress(r)[1]) for r in raws]
     blobs = [comp[i % U] for i in range(n)]
-    buf, off, ln = _pack(blobs, 3)
+    buf, off, ln = DB.pack(blobs, after=[bytes(3)] * n, mis=0, gap=0)      # 16-byte aligned, 3 bytes and more between chunks
     dev = torch.device("cuda:0")
     t_in = torch.from_numpy(buf).to(dev)
     cap = np.array([len(raws[i % U]) for i in range(n)], np.uint64)
@@ -62,7 +54,7 @@ def test_compress_from_torch_tensors_round_trips_through_the_oracle(codec):
     from cramjam_amd import _native as N
     raws = [oracle.synth_v1(65536, 50 + i) for i in range(40)] + [b"", b"abc", bytes(70000)]
     n = len(raws)
-    buf, off, ln = _pack(raws, 0)
+    buf, off, ln = DB.pack(raws, mis=0, gap=0)
     L = N.lib()
     cap = np.array([L.cj_lz4_block_compress_bound(len(r), 1) if codec == "lz4" else L.cj_snappy_raw_max_compress_len(len(r)) for r in raws], np.uint64)
     out_off = np.concatenate([[0], np.cumsum(cap + 8)[:-1]]).astype(np.uint64)

@@ -8,23 +8,15 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import device_batch as DB  # noqa: E402  (beside this script)
 import cramjam_amd as cj  # noqa: E402
 from cramjam_amd import _native as N  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
 
 
-def _pack(blobs, pad):
-    ln = np.array([len(b) for b in blobs], np.uint64)
-    off = np.concatenate([[0], np.cumsum((ln + pad + 15) & ~np.uint64(15))[:-1]]).astype(np.uint64) + np.uint64(pad)
-    buf = np.zeros(int(off[-1] + ln[-1]) + 64, np.uint8)
-    for k, b in enumerate(blobs):
-        buf[int(off[k]):int(off[k]) + len(b)] = np.frombuffer(b, np.uint8)
-    return buf, off, ln
-
-
 def run(device_fn, host_fn, inputs, caps, stream):
     dev = torch.device("cuda:0")
-    buf, off, ln = _pack(inputs, 5)
+    buf, off, ln = DB.pack(inputs, mis=lambda i: 5, gap=0)       # every input 5 bytes off a granule
     cap = np.array(caps, np.uint64)
     out_off = np.concatenate([[0], np.cumsum(cap + 16)[:-1]]).astype(np.uint64)
     t_in = torch.from_numpy(buf).to(dev)

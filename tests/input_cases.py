@@ -2,7 +2,7 @@
 sibling (tests/capacity_cases.py, whose bodies, block writers and `render` it uses) on the input side.  Three families, one chunk per case:
 
   A  where the input ends: in_len cut at every value of [0, 40) and [len - 40, len] and at -2 .. +23 around the token of eight chosen
-     sequences, each cut twice: `after` (the bytes packed behind in_len, see _layout in tests/test_capacity_gpu.py) is once the stream's
+     sequences, each cut twice: `after` (the bytes packed behind in_len, see pack in tests/device_batch.py) is once the stream's
      own continuation and once 0xFF bytes — a length-extension chain read past the end runs on, an offset read there is 65 535;
   B  the offset at its edges: 0, small values, the match start ms and the values around it, 65 535 (Snappy: in every copy form that holds
      the value, and above 65 535 in the 4-byte form); with a dictionary ms + 1 .. ms + its length + 1; the Snappy preamble's forms;

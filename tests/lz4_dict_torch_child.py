@@ -9,23 +9,15 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
+import device_batch as DB  # noqa: E402
 import lz4_dict_model as D  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
-
-
-def _pack(blobs, gap=16):
-    ln = np.array([len(b) for b in blobs], np.int64)
-    off = np.concatenate([[0], np.cumsum((ln + gap + 15) & ~15)[:-1]]).astype(np.int64)
-    buf = np.zeros(int(off[-1] + ln[-1]) + 64, np.uint8)
-    for k, b in enumerate(blobs):
-        buf[int(off[k]):int(off[k]) + len(b)] = np.frombuffer(b, np.uint8)
-    return buf, off, ln
 
 
 def dictionary_calls():
     dl = 65536
     cs = D.cases(dl)
-    buf, off, ln = _pack([c["bytes"] for c in cs])
+    buf, off, ln = DB.pack([c["bytes"] for c in cs], mis=0, dtype=np.int64)
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
         t_dict = torch.from_numpy(np.frombuffer(D.dictionary(dl), np.uint8).copy()).cuda()
@@ -53,7 +45,7 @@ def dictionary_calls():
             assert want[0] == sz[i] and out[int(ooff[i]):int(ooff[i]) + int(sz[i])].tobytes() == want[1], c["name"]
     # compress on the same stream, then decode what was written: a round trip that never leaves HBM
     raws = [D.words(s, 80 + k) for k, s in enumerate((0, 13, 300, 4096, 16384, 65536, 65537))]
-    buf, off, ln = _pack(raws)
+    buf, off, ln = DB.pack(raws, mis=0, dtype=np.int64)
     bound = np.array([len(r) + len(r) // 255 + 16 + 4 for r in raws], np.int64)
     coff = np.concatenate([[0], np.cumsum(bound)[:-1]]).astype(np.int64)
     with torch.cuda.stream(side):

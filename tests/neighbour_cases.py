@@ -14,6 +14,7 @@ Every blob keeps 64 bytes of margin at both ends: a read a few bytes outside a c
 come from zlib (live), libzstd (recorded: tests/golden/golden_neighbours.json), the Python models and the encoders' C models — never
 from a GPU path.  No GPU needed to import this."""
 import functools
+import hashlib
 import json
 import os
 import zlib
@@ -21,6 +22,7 @@ import zlib
 import numpy as np
 
 import deflate_cases as DF
+import device_batch as DB
 
 M = 64                                             # ring bytes on each side, and the blob's margin
 RINGS = ("zero", "ff", "own", "packed")
@@ -370,3 +372,50 @@ def encoder_expected(codec):
 def encoder_cases(codec):
     """encoder_inputs() as cases: result = the length of the model's stream, out = its bytes, cap = the codec's bound"""
     return [dict(c, cap=cap, result=len(w), out=w, sha=None) for c, (cap, w) in zip(encoder_inputs(), encoder_expected(codec))]
+
+
+# ---- what the GPU suites that run these cases share (tests/test_neighbours_gpu.py, tests/test_scratch_contents_gpu.py) -----------------
+sha = lambda b: hashlib.sha256(bytes(b)).hexdigest()
+
+
+def tag(key, ring, c, got):
+    return key, ring, c["base"], "k", c.get("k"), "len", len(c["bytes"]), "cap", c["cap"], "got", int(got), "want", c["result"]
+
+
+def device(e, key, cases, ring, call, packed=None, dictionary=None, more=0):
+    """one device batch on the harness (tests/device_batch.py): call(d_in, in_off, in_len, d_out, out_off, out_cap, result[, d_dict])
+    over the cases packed under `ring` (packed: a (blob, offsets) made elsewhere; more: bytes added to every in_len), then every
+    assertion of tests/test_neighbours_gpu.py's head; returns (results, output, slot offsets)"""
+    blob, off = packed if packed is not None else case_layout(key, cases, ring)[:2]
+    assert not alignment_coverage(cases, off), (key, ring, alignment_coverage(cases, off))
+    return DB.run_cases(e, key, cases, call, lambda i, got: tag(key, ring, cases[i], got), packed=(blob, off), more=more, dictionary=dictionary,
+                        with_input=True, what="a guard byte or a byte behind the result changed")
+
+
+def shuffled(cases, seed=20):
+    return [cases[i] for i in np.random.default_rng(seed).permutation(len(cases))]
+
+
+def host_check(key, cases, res, outs):
+    for c, r, o in zip(cases, res, outs):
+        assert r == c["result"], tag(key, "host", c, r)
+        assert len(o) == max(r, 0) and (r <= 0 or ((bytes(o) == c["out"]) if c["out"] is not None else (sha(o) == c["sha"]))), ("bytes", tag(key, "host", c, r))
+
+
+def bgzf_decode_cases():
+    """a refused BGZF stream is refused by the walk or for its capacity before a byte is written, or by a member's decoder, which may
+    have written inside the slot"""
+    return [dict(c, written=0 if c["size"] < 0 or c["size"] > c["cap"] else c["cap"]) for c in bgzf_cases()]
+
+
+def encode_call(eng, codec, n):
+    from cramjam_amd import _native as N
+    L = N.lib()
+    if codec in ("lz4", "snappy"):
+        return lambda i, o, l, out, oo, oc, r: eng.batch_device(N.CODEC_LZ4_BLOCK if codec == "lz4" else N.CODEC_SNAPPY_RAW, N.OP_COMPRESS, 0, n, i, o, l, out, oo, oc, r)
+    if codec == "lz4_dict":
+        return lambda i, o, l, out, oo, oc, r, d: N.check(L.cj_dict_batch_device(eng.h, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, 0, n, i, o, l, out, oo, oc, r, d, DICT_LEN, None))
+    if codec.startswith("deflate"):
+        wrap = ENCODERS.index(codec) - 3
+        return lambda i, o, l, out, oo, oc, r: N.check(L.cj_deflate_compress_batch_device(eng.h, wrap, 0, n, i, o, l, out, oo, oc, r, None))
+    return lambda i, o, l, out, oo, oc, r: N.check(L.cj_zstd_compress_batch_device(eng.h, N.ZSTD_FRAMES, 0, n, i, o, l, out, oo, oc, r, None))

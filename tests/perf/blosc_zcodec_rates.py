@@ -22,6 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import blosc_zcodec_model as Z  # noqa: E402
+import device_batch as DB  # noqa: E402
 import make_golden_blosc as G  # noqa: E402
 from cramjam_amd import _native as N  # noqa: E402
 from cramjam_amd import batch  # noqa: E402
@@ -52,14 +53,6 @@ def stats(ms):
     return dict(median_ms=round(statistics.median(ms), 4), min_ms=round(min(ms), 4), max_ms=round(max(ms), 4), runs=len(ms))
 
 
-def pack(chunks):
-    off, run, parts = [], 0, []
-    for c in chunks:
-        pad = -len(c) % 16 + 16
-        off.append(run); parts += [np.frombuffer(c, np.uint8), np.zeros(pad, np.uint8)]; run += len(c) + pad
-    return np.concatenate(parts + [np.zeros(64, np.uint8)]), np.asarray(off), np.asarray([len(c) for c in chunks])
-
-
 def one_batch(side, lib, label, plains, recipe, repeat):
     """plains: the unique plain chunks (bytes); the batch is them `repeat` times over"""
     dev = "cuda"
@@ -72,7 +65,7 @@ def one_batch(side, lib, label, plains, recipe, repeat):
     chunks = [G.mint(lib, p, recipe) for p in plains]
     zstd = recipe["cname"] == "zstd"
     assert all(Z.fmt_of(c) == (Z.FORMAT_ZSTD if zstd else Z.FORMAT_ZLIB) for c in chunks)
-    blob, coff, clen = pack(chunks * repeat)
+    blob, coff, clen = DB.pack(chunks * repeat, mis=0, dtype=np.int64)
     res = torch.empty(n, dtype=torch.int64, device=dev)
     with torch.cuda.stream(side):
         comp = torch.from_numpy(blob).to(dev)

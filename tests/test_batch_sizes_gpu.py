@@ -7,10 +7,10 @@ queued frame batch.  The checks run in ONE child process (tests/batch_sizes_chil
 
 Measured with this test's inputs (MI355X): see DESIGN.md 5.9 for the rates."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +18,4 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 def test_decoded_size_queries_from_torch_tensors():
     pytest.importorskip("torch")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "batch_sizes_child.py")], capture_output=True, text=True, timeout=1500)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0 and "batch sizes: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(HERE, "batch_sizes_child.py"), "batch sizes: ok", 1500)

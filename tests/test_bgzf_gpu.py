@@ -5,17 +5,15 @@ pinned to the DEFLATE encoder's bytes; capacities, turns of a shrunken slot budg
 import gzip
 import os
 import struct
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import bgzf_model as M
 import deflate_cases as D
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
-G = 64          # canary bytes on both sides of every output slot
 SLOT = 65312    # bytes of one member slot of the compress scratch (cj_debug_bgzf_slot_budget counts in these)
 SIZES = (0, 1, 65279, 65280, 65281, 130560, 200001)
 
@@ -28,44 +26,10 @@ def eng():
 
 
 def _device_call(e, N, op, chunks, caps):
-    """cj_bgzf_batch_device over chunks packed in HBM at every misalignment; slot i lies at least G bytes behind slot i - 1's end, at
-    every misalignment too, and the whole output is filled with 0xA5 first: (results, output, offsets)"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for i, c in enumerate(caps):
-        run += (7 * i) % 16
-        ooff.append(run); run += int(c) + G
-    total = run + 64
-    metas = [np.array(a, np.uint64) for a in (off, [len(c) for c in chunks], ooff, caps)]
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * n) for _ in range(5)]
-    L = N.lib()
-    try:
-        e.h2d(d_in, blob)
-        N.check(L.cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        e.sync()
-        N.check(L.cj_bgzf_batch_device(e.h, 0, op, 0, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * n, "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
-
-
-def _canaries_intact(out, ooff, caps):
-    for i, (lo, cap) in enumerate(zip(ooff, caps)):
-        if not ((out[lo - G:lo] == 0xA5).all() and (out[lo + int(cap):lo + int(cap) + G] == 0xA5).all()):
-            return i
-    return None
+    """cj_bgzf_batch_device in the harness's guarded run (tests/device_batch.py): chunks at every misalignment, slot i at least G bytes
+    behind slot i - 1's end, at every misalignment too, the output filled with 0xA5 first: (results, output, offsets)"""
+    n, L = len(chunks), N.lib()
+    return DB.run_chunks(e, lambda i, o, l, out, oo, oc, r: N.check(L.cj_bgzf_batch_device(e.h, 0, op, 0, n, i, o, l, out, oo, oc, r, None)), chunks, caps, out_mis=DB.out_mis)
 
 
 # ---- decode -------------------------------------------------------------------------------------------------------------------------
@@ -138,7 +102,7 @@ def test_device_batch_of_a_thousand_streams_with_canaries(eng):
             assert out[ooff[i]:ooff[i] + r].tobytes() == o, i
         if refused:                     # by the walk or for its capacity: the whole slot is untouched
             assert (out[ooff[i]:ooff[i] + cap] == 0xA5).all(), i
-    assert _canaries_intact(out, ooff, caps) is None
+    assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_sizes_and_decode_without_output_lens():
@@ -221,7 +185,7 @@ def test_capacities_bound_exact_and_one_less(eng):
                 assert got[i] == res[i] and out[ooff[i]:ooff[i] + res[i]].tobytes() == s, (i, caps[i], int(got[i]))
             else:
                 assert got[i] == M.OUT_TOO_SMALL and (out[ooff[i]:ooff[i] + caps[i]] == 0xA5).all(), (i, caps[i], int(got[i]))
-        assert _canaries_intact(out, ooff, caps) is None
+        assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_streams_across_turns_at_capacities_below_the_bound(eng):
@@ -241,7 +205,7 @@ def test_streams_across_turns_at_capacities_below_the_bound(eng):
                     assert got[i] == r and out[ooff[i]:ooff[i] + r].tobytes() == s, (i, caps[i], int(got[i]))
                 else:
                     assert got[i] == M.OUT_TOO_SMALL and (out[ooff[i]:ooff[i] + caps[i]] == 0xA5).all(), (i, caps[i], int(got[i]))
-            assert _canaries_intact(out, ooff, caps) is None
+            assert DB.guards_intact(out, ooff, caps) is None
     finally:
         assert L.cj_debug_bgzf_slot_budget(prev) == 2 * SLOT
 
@@ -304,6 +268,4 @@ def test_an_input_above_the_limit_lands_in_its_own_result(eng):
 def test_device_entries_on_torch_tensors():
     """bgzf_compress_many_device, bgzf_sizes_device and bgzf_decompress_many_device on torch tensors on a side stream, in a child that
     imports torch BEFORE cramjam_amd"""
-    r = subprocess.run([sys.executable, os.path.join(D.ROOT, "tests", "bgzf_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "bgzf torch: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(D.ROOT, "tests", "bgzf_torch_child.py"), "bgzf torch: ok", 600)

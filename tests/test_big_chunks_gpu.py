@@ -3,11 +3,13 @@ CJ_FLAG_BIG_CHUNKS: 32-lane segmented parse into records (csrc/big_chunks.hip) +
 with them — against the oracle: valid chunks of every shape bit-exactly, damaged chunks with the oracle's verdict and bytes,
 small and big chunks mixed in one batch.  Reference behaviour: one call of /root/reference/src/lz4.rs:78-95 (decompress_block) /
 src/snappy.rs:52-60 (decompress_raw) per chunk; a batch is many of them at once."""
+import contextlib
 import random
 
 import numpy as np
 import pytest
 
+import device_batch as DB
 import oracle
 from cramjam_amd import _native as N
 
@@ -37,12 +39,7 @@ def _run(eng, codec, blobs, caps, flags):
     for k, b in enumerate(blobs): packed[int(in_off[k]):int(in_off[k]) + len(b)] = np.frombuffer(b, np.uint8)
     out_cap = np.array(caps, np.uint64); out_off = np.concatenate([[0], np.cumsum(out_cap + 5)[:-1]]).astype(np.uint64)
     total = int(out_off[-1] + out_cap[-1]) + 64
-    d_in = eng.alloc(packed.nbytes); d_out = eng.alloc(total); d_meta = eng.alloc(5 * n * 8)
-    eng.h2d(d_in, packed); eng.h2d(d_meta, np.concatenate([in_off, in_len, out_off, out_cap])); eng.h2d(d_out, np.full(total, 0xAB, np.uint8))
-    eng.batch_device(codec, DEC, flags, n, d_in, d_meta, d_meta + 8 * n, d_out, d_meta + 16 * n, d_meta + 24 * n, d_meta + 32 * n)
-    eng.sync()
-    res = eng.d2h(d_meta + 32 * n, 8 * n, "int64"); out = eng.d2h(d_out, total)
-    for p in (d_in, d_out, d_meta): eng.free(p)
+    res, out = DB.run(eng, lambda *a: eng.batch_device(codec, DEC, flags, n, *a), packed, in_off, in_len, out_off, out_cap, total, fill=0xAB)
     return res, out, out_off
 
 
@@ -208,20 +205,17 @@ def test_more_big_chunks_in_one_call_than_one_group_holds(eng, codec):
     assert not bad, (len(bad), bad[:8])
 
 
+@contextlib.contextmanager
 def _device_batch(eng, codec, blobs, caps):
-    """the arrays of a device batch, uploaded; returns (submit, fetch, free)"""
+    """the arrays of a device batch packed without a gap, uploaded by the harness (tests/device_batch.py): (submit, fetch)"""
     n = len(blobs)
     in_len = np.array([len(b) for b in blobs], np.uint64)
     in_off = np.concatenate([[0], np.cumsum(in_len)[:-1]]).astype(np.uint64)
     packed = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
     out_cap = np.array(caps, np.uint64); out_off = np.concatenate([[0], np.cumsum(out_cap)[:-1]]).astype(np.uint64)
     total = int(out_off[-1] + out_cap[-1]) + 64
-    d_in = eng.alloc(packed.nbytes); d_out = eng.alloc(total); d_meta = eng.alloc(5 * n * 8)
-    eng.h2d(d_in, packed); eng.h2d(d_meta, np.concatenate([in_off, in_len, out_off, out_cap]))
-    submit = lambda flags: eng.batch_device(codec, DEC, flags, n, d_in, d_meta, d_meta + 8 * n, d_out, d_meta + 16 * n, d_meta + 24 * n, d_meta + 32 * n)
-    fetch = lambda: (eng.d2h(d_meta + 32 * n, 8 * n, "int64"), eng.d2h(d_out, total), out_off)
-    free = lambda: [eng.free(p) for p in (d_in, d_out, d_meta)]
-    return submit, fetch, free
+    with DB.device_batch(eng, packed, in_off, in_len, out_off, out_cap, total) as b:
+        yield (lambda flags: eng.batch_device(codec, DEC, flags, n, *b.args)), (lambda: b.read() + (out_off,))
 
 
 def test_reservation_follows_the_counts_the_engine_has_seen():
@@ -233,23 +227,21 @@ def test_reservation_follows_the_counts_the_engine_has_seen():
         small = oracle.synth_v1(4096, 1); big = oracle.synth_v1(S, 2)
         raws = [small] * 8191 + [big]
         blobs = [oracle.lz4_compress_raw(r)[1] for r in (small, big)]
-        submit, fetch, free = _device_batch(e, LZ4, [blobs[0]] * 8191 + [blobs[1]], [len(r) for r in raws])
-        submit(N.FLAG_BIG_CHUNKS); e.sync()
-        res, out, off = fetch()
-        assert [int(x) for x in res] == [len(r) for r in raws]
-        assert out[int(off[8191]):int(off[8191]) + S].tobytes() == big
-        assert 0 < L.cj_debug_big_scratch_bytes(e.h) < 64 << 20, L.cj_debug_big_scratch_bytes(e.h)
-        free()
-        # the same engine now meets 300 big chunks: the first such batch is planned for one (the rest take the wavefront kernel), the ones behind it for 300
-        raws = [big, small] * 300
-        submit, fetch, free = _device_batch(e, LZ4, [blobs[1], blobs[0]] * 300, [len(r) for r in raws])
-        for _ in range(3):
+        with _device_batch(e, LZ4, [blobs[0]] * 8191 + [blobs[1]], [len(r) for r in raws]) as (submit, fetch):
             submit(N.FLAG_BIG_CHUNKS); e.sync()
             res, out, off = fetch()
             assert [int(x) for x in res] == [len(r) for r in raws]
-            assert all(out[int(off[i]):int(off[i]) + len(r)].tobytes() == r for i, r in enumerate(raws))
-        assert 300 << 20 <= L.cj_debug_big_scratch_bytes(e.h) < 1000 << 20, L.cj_debug_big_scratch_bytes(e.h)
-        free()
+            assert out[int(off[8191]):int(off[8191]) + S].tobytes() == big
+            assert 0 < L.cj_debug_big_scratch_bytes(e.h) < 64 << 20, L.cj_debug_big_scratch_bytes(e.h)
+        # the same engine now meets 300 big chunks: the first such batch is planned for one (the rest take the wavefront kernel), the ones behind it for 300
+        raws = [big, small] * 300
+        with _device_batch(e, LZ4, [blobs[1], blobs[0]] * 300, [len(r) for r in raws]) as (submit, fetch):
+            for _ in range(3):
+                submit(N.FLAG_BIG_CHUNKS); e.sync()
+                res, out, off = fetch()
+                assert [int(x) for x in res] == [len(r) for r in raws]
+                assert all(out[int(off[i]):int(off[i]) + len(r)].tobytes() == r for i, r in enumerate(raws))
+            assert 300 << 20 <= L.cj_debug_big_scratch_bytes(e.h) < 1000 << 20, L.cj_debug_big_scratch_bytes(e.h)
     finally:
         e.close()
 
@@ -263,19 +255,18 @@ def test_a_flagged_call_only_enqueues_once_the_engine_has_seen_a_count():
         big = oracle.synth_v1(S, 3)
         blob = oracle.lz4_compress_raw(big)[1]
         n = 9000                                                  # more than one group's worth of chunks: the case that used to synchronise
-        submit, fetch, free = _device_batch(e, LZ4, [blob] * n, [S] * n)
-        submit(N.FLAG_BIG_CHUNKS); e.sync()                       # the engine sees its first count (and allocates): this call may wait
-        submit(N.FLAG_BIG_CHUNKS); e.sync()                       # planned for 9 000 now
-        t0 = time.perf_counter(); submit(N.FLAG_BIG_CHUNKS); e.sync(); one = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        for _ in range(6): submit(N.FLAG_BIG_CHUNKS)
-        queued = time.perf_counter() - t0
-        e.sync()
-        drained = time.perf_counter() - t0
-        res, out, off = fetch()
-        assert (res == S).all() and out[int(off[n - 1]):int(off[n - 1]) + S].tobytes() == big
-        assert drained > 3 * one and queued < 0.5 * drained, (one, queued, drained)      # six batches were still running when the sixth submit returned
-        free()
+        with _device_batch(e, LZ4, [blob] * n, [S] * n) as (submit, fetch):
+            submit(N.FLAG_BIG_CHUNKS); e.sync()                   # the engine sees its first count (and allocates): this call may wait
+            submit(N.FLAG_BIG_CHUNKS); e.sync()                   # planned for 9 000 now
+            t0 = time.perf_counter(); submit(N.FLAG_BIG_CHUNKS); e.sync(); one = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            for _ in range(6): submit(N.FLAG_BIG_CHUNKS)
+            queued = time.perf_counter() - t0
+            e.sync()
+            drained = time.perf_counter() - t0
+            res, out, off = fetch()
+            assert (res == S).all() and out[int(off[n - 1]):int(off[n - 1]) + S].tobytes() == big
+            assert drained > 3 * one and queued < 0.5 * drained, (one, queued, drained)  # six batches were still running when the sixth submit returned
     finally:
         e.close()
 

@@ -9,6 +9,7 @@ import pytest
 
 import blosc_cases as K
 import blosc_model as M
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 
@@ -53,10 +54,7 @@ def test_fixtures_host_batch_one_call():
 
 def _torch_child(what):
     """the checks on torch tensors run in a child that imports torch BEFORE cramjam_amd (tests/device_api_child.py says why)"""
-    import subprocess
-    r = subprocess.run([sys.executable, os.path.join(K.ROOT, "tests", "blosc_torch_child.py"), what], capture_output=True, text=True, timeout=900)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and what + ": ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(K.ROOT, "tests", "blosc_torch_child.py"), what + ": ok", 900, what)
 
 
 def test_fixtures_device_batch_on_a_side_stream():
@@ -80,18 +78,8 @@ def test_malformed_chunks_between_intact_neighbours(eng):
     slots = (caps + 15) // 16 * 16 + 2 * G
     ooff = (np.concatenate([[0], np.cumsum(slots)[:-1]]) + G).astype(np.uint64)
     total = int(slots.sum())
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    e.h2d(d_in, blob)
-    N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-    d_meta = [e.alloc(8 * len(chunks)) for _ in range(5)]
-    for p, a in zip(d_meta, (off, ln, ooff, caps)):
-        e.h2d(p, a)
-    N.check(N.lib().cj_blosc_batch_device(e.h, 0, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], len(chunks), None, 0, None))
-    e.sync()
-    res = e.d2h(d_meta[4], 8 * len(chunks), "int64")
-    out = e.d2h(d_out, total)
-    for p in [d_in, d_out] + d_meta:
-        e.free(p)
+    call = lambda i, o, l, out, oo, oc, r: N.check(N.lib().cj_blosc_batch_device(e.h, 0, i, o, l, out, oo, oc, r, len(chunks), None, 0, None))
+    res, out = DB.run(e, call, blob, off, ln, ooff, caps, total)
     for i, (cls, x) in enumerate(expect):
         lo, cap = int(ooff[i]), int(caps[i])
         if cls == "ok":
@@ -179,19 +167,9 @@ def _compress_on_device(e, N, bufs, ts, filt, clevel, codec):
     slots = (caps + 15) // 16 * 16 + 2 * G
     ooff = (np.concatenate([[0], np.cumsum(slots)[:-1]]) + G).astype(np.uint64)
     total = int(slots.sum())
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * len(bufs)) for _ in range(5)]
-    e.h2d(d_in, blob)
-    N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-    for p, a in zip(d_meta, (off, ln, ooff, caps)):
-        e.h2d(p, a)
     params = N.BloscParams(ts, filt, clevel, codec, 0)
-    N.check(N.lib().cj_blosc_batch_device(e.h, 1, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], len(bufs), C.byref(params), 0, None))
-    e.sync()
-    res = e.d2h(d_meta[4], 8 * len(bufs), "int64")
-    out = e.d2h(d_out, total)
-    for p in [d_in, d_out] + d_meta:
-        e.free(p)
+    call = lambda i, o, l, out, oo, oc, r: N.check(N.lib().cj_blosc_batch_device(e.h, 1, i, o, l, out, oo, oc, r, len(bufs), C.byref(params), 0, None))
+    res, out = DB.run(e, call, blob, off, ln, ooff, caps, total)
     chunks = []
     for i in range(len(bufs)):
         lo, r = int(ooff[i]), int(res[i])

@@ -4,8 +4,6 @@ malformed and hand-made chunks between intact neighbours of another format, the 
 streams, and the default reading, which still refuses both formats.  Fixtures only: the verdict classes and sha256 recorded in
 tests/golden/golden_blosc_zcodecs.json, neither the model nor libzstd nor libblosc."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import pytest
 import blosc_cases as K
 import blosc_model as M
 import blosc_zcodec_model as Z
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 
@@ -25,28 +24,6 @@ def eng():
     from cramjam_amd import _native as N
     from cramjam_amd.batch import _engine
     return _engine(0), N
-
-
-def _device_batch(e, N, chunks, caps, slots, flags, guard=0):
-    """cj_blosc_batch_device over chunks packed in HBM; slot i lies `guard` bytes behind slot i - 1's end, the whole output is filled
-    with 0xA5 first: (results, the output bytes, the slots' offsets)"""
-    blob, off, ln = K.pack(chunks)
-    caps, slots = np.asarray(caps, np.uint64), np.asarray(slots, np.uint64)
-    ooff = (np.concatenate([[0], np.cumsum(slots + guard)[:-1]]) + guard).astype(np.uint64)
-    total = int(ooff[-1] + slots[-1]) + max(guard, 64)
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * len(chunks)) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, (off, ln, ooff, caps)):
-            e.h2d(p, a)
-        N.check(N.lib().cj_blosc_batch_device(e.h, 0, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], len(chunks), None, flags, None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * len(chunks), "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
 
 
 def test_fixtures_single_chunk_with_the_flags():
@@ -77,9 +54,7 @@ def test_fixtures_host_batch_with_the_flags():
 
 def test_fixtures_device_batch_on_a_side_stream():
     """the device-resident entries on torch tensors, in a child that imports torch BEFORE cramjam_amd (tests/device_api_child.py says why)"""
-    r = subprocess.run([sys.executable, os.path.join(K.ROOT, "tests", "blosc_zcodecs_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "fixtures: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(K.ROOT, "tests", "blosc_zcodecs_torch_child.py"), "fixtures: ok", 600)
 
 
 def _four_formats():
@@ -105,7 +80,7 @@ def test_one_batch_interleaves_the_four_formats_into_packed_slots(eng):
     assert {f for _v, f in vf} == {None, 0, 1, 3, 4}
     vs = [v for v, _f in vf]
     sizes = [v["nbytes"] for v in vs]
-    res, out, ooff = _device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, ALL)       # slot = nbytes: no gap, whatever the alignment
+    res, out, ooff = K.device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, ALL)       # slot = nbytes: no gap, whatever the alignment
     assert [int(o) for o in ooff] == [sum(sizes[:i]) for i in range(len(vs))]
     for i, v in enumerate(vs):
         lo = int(ooff[i])
@@ -120,7 +95,7 @@ def test_the_same_batch_with_the_zlib_flag_alone(eng):
     vf = _four_formats()
     vs = [v for v, _f in vf]
     sizes = [v["nbytes"] for v in vs]
-    res, out, ooff = _device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, Z.FLAG_ZLIB)
+    res, out, ooff = K.device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, Z.FLAG_ZLIB)
     refused = 0
     for i, (v, f) in enumerate(vf):
         lo = int(ooff[i])
@@ -153,7 +128,7 @@ def test_malformed_and_hand_made_chunks_between_intact_neighbours_of_another_for
     G = 64
     caps = [cap for _x, cap in expect]
     slots = [(c + 15) // 16 * 16 for c in caps]
-    res, out, ooff = _device_batch(e, N, chunks, caps, slots, ALL, guard=G)
+    res, out, ooff = K.device_batch(e, N, chunks, caps, slots, ALL, guard=G)
     for i, (x, cap) in enumerate(expect):
         lo = int(ooff[i])
         cls = x.get("verdict", "ok")
@@ -177,12 +152,12 @@ def test_zstd_slot_slices_fall_inside_a_chunks_streams(eng):
     assert len(vs) >= 4 and sum(len(Z.parse(v["bytes"])[1]) for v in vs) >= 16
     sizes = [v["nbytes"] for v in vs]
     chunks = [v["bytes"] for v in vs]
-    whole = _device_batch(e, N, chunks, sizes, sizes, Z.FLAG_ZSTD)
+    whole = K.device_batch(e, N, chunks, sizes, sizes, Z.FLAG_ZSTD)
     L = N.lib()
     slot = 131072 + 32                                                 # kZsSlotBytes
     prev = L.cj_debug_zstd_slot_budget(3 * slot)
     try:
-        sliced = _device_batch(e, N, chunks, sizes, sizes, Z.FLAG_ZSTD)
+        sliced = K.device_batch(e, N, chunks, sizes, sizes, Z.FLAG_ZSTD)
     finally:
         assert L.cj_debug_zstd_slot_budget(prev) == 3 * slot
     assert list(whole[0]) == list(sliced[0]) == sizes and (whole[1] == sliced[1]).all()

@@ -2,8 +2,6 @@
 decode entry, one batch that mixes them with the LZ4 fixtures into slots packed without a gap, malformed and hand-written streams
 between intact neighbours, and the default reading, which still refuses them."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -11,6 +9,7 @@ import pytest
 import blosc_cases as K
 import blosc_model as M
 import blosclz_model as Z
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 
@@ -20,28 +19,6 @@ def eng():
     from cramjam_amd import _native as N
     from cramjam_amd.batch import _engine
     return _engine(0), N
-
-
-def _device_batch(e, N, chunks, caps, slots, flags, guard=0):
-    """cj_blosc_batch_device over chunks packed in HBM; slot i lies `guard` bytes behind slot i - 1's end, the whole output is filled
-    with 0xA5 first: (results, the output bytes, the slots' offsets)"""
-    blob, off, ln = K.pack(chunks)
-    caps, slots = np.asarray(caps, np.uint64), np.asarray(slots, np.uint64)
-    ooff = (np.concatenate([[0], np.cumsum(slots + guard)[:-1]]) + guard).astype(np.uint64)
-    total = int(ooff[-1] + slots[-1]) + max(guard, 64)
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * len(chunks)) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, (off, ln, ooff, caps)):
-            e.h2d(p, a)
-        N.check(N.lib().cj_blosc_batch_device(e.h, 0, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], len(chunks), None, flags, None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * len(chunks), "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
 
 
 def test_fixtures_single_chunk_with_the_flag():
@@ -72,9 +49,7 @@ def test_fixtures_host_batch_with_the_flag():
 
 def test_fixtures_device_batch_on_a_side_stream():
     """the device-resident entries on torch tensors, in a child that imports torch BEFORE cramjam_amd (tests/device_api_child.py says why)"""
-    r = subprocess.run([sys.executable, os.path.join(K.ROOT, "tests", "blosclz_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "fixtures: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(K.ROOT, "tests", "blosclz_torch_child.py"), "fixtures: ok", 600)
 
 
 def test_one_batch_mixes_lz4_and_blosclz_chunks_into_packed_slots(eng):
@@ -85,7 +60,7 @@ def test_one_batch_mixes_lz4_and_blosclz_chunks_into_packed_slots(eng):
         vs += lz4[k:k + 1] + blz[k:k + 1]
     assert len(vs) == len(lz4) + len(blz)
     sizes = [v["nbytes"] for v in vs]
-    res, out, ooff = _device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, Z.FLAG)       # slot = nbytes: no gap, whatever the alignment
+    res, out, ooff = K.device_batch(e, N, [v["bytes"] for v in vs], sizes, sizes, Z.FLAG)       # slot = nbytes: no gap, whatever the alignment
     assert [int(o) for o in ooff] == [sum(sizes[:i]) for i in range(len(vs))]
     for i, v in enumerate(vs):
         lo = int(ooff[i])
@@ -124,7 +99,7 @@ def test_malformed_and_hand_written_streams_between_intact_neighbours(eng):
     G = 64
     caps = [x[2] for x in expect]
     slots = [(c + 15) // 16 * 16 for c in caps]
-    res, out, ooff = _device_batch(e, N, chunks, caps, slots, Z.FLAG, guard=G)
+    res, out, ooff = K.device_batch(e, N, chunks, caps, slots, Z.FLAG, guard=G)
     for i, (cls, x, cap) in enumerate(expect):
         lo = int(ooff[i])
         if isinstance(x, dict):                                      # an intact neighbour

@@ -3,24 +3,23 @@ oracle) through every LZ4 and Snappy decoder path of a device-resident batch: on
 behind the parse kernel and with the parse inside it, the default pipeline below and above CJ_FUSED_MAX_CHUNKS, the 32 KiB and 16 KiB
 windows with each placement of the parse, big chunks, the LZ4 size prefix, the shared dictionary.
 
-Slots as in tests/test_lz4_dict_gpu.py: inputs packed at every misalignment, 64 guard bytes of 0xA5 on both sides of every output slot, the
+Slots by tests/device_batch.py: inputs packed at every misalignment, 64 guard bytes of 0xA5 on both sides of every output slot, the
 whole output filled before the call.  For every chunk: the oracle's result (LZ4: any refusal is CJ_E_CORRUPT; Snappy and the size prefix:
 the oracle's code), the oracle's bytes in [0, result), both guards intact — accepted or refused —, and [result, cap) untouched where the
 chunk was accepted (a refused chunk may have written inside its own slot)."""
 import ctypes as C
 import functools
 
-import numpy as np
 import pytest
 
 import capacity_cases as K
 import lz4_dict_model as D
 import test_spec_parse_model as M
+from capacity_cases import PATHS
 from cramjam_amd import _native as N
 
 pytestmark = pytest.mark.gpu
 LZ4, SN, DEC = N.CODEC_LZ4_BLOCK, N.CODEC_SNAPPY_RAW, N.OP_DECOMPRESS
-G = 64                                            # guard bytes around every output slot
 PROFILE = 0x1000                                  # CJ_FLAG_DEBUG_PROFILE: the debug counters count
 WAVE, LANE, LDS = N.FLAG_FORCE_WAVE_PER_CHUNK, N.FLAG_FORCE_LANE_PER_CHUNK, N.FLAG_FORCE_LDS_PER_CHUNK
 PK, FUSED = N.FLAG_FORCE_PARSE_KERNEL, N.FLAG_FORCE_FUSED_PARSE
@@ -33,96 +32,16 @@ def eng():
     e.close()
 
 
-_layouts = {}
-
-
-def _layout(key, cases):
-    """the host side of one batch, built once per case list: packed input, the four descriptor rows, the offsets, and the mask of the
-    output bytes that must still be 0xA5 after the call (everything but [0, result) of an accepted and [0, cap) of a refused chunk).
-    A case may carry `after` (tests/input_cases.py): bytes packed right behind its in_len, inside its own slot — what a read past the
-    input's end sees; at least 16 zero bytes of the slot still follow them, so the next case's bytes never serve as `after`."""
-    if key not in _layouts:
-        n = len(cases)
-        off, run = np.zeros(n, np.uint64), 0
-        for i, c in enumerate(cases):
-            m = (5 * i) % 16
-            off[i] = run + m; run += (m + len(c["bytes"]) + len(c.get("after", b"")) + 15) // 16 * 16 + 16
-        blob = np.zeros(run + 64, np.uint8)
-        for o, c in zip(off, cases):
-            b = c["bytes"] + c.get("after", b"")
-            blob[int(o):int(o) + len(b)] = np.frombuffer(b, np.uint8)
-        caps = np.array([c["cap"] for c in cases], np.uint64)
-        ooff = (G + np.concatenate([[0], np.cumsum(caps + np.uint64(G))[:-1]])).astype(np.uint64)
-        total = int(ooff[-1] + caps[-1]) + G + 64
-        keep = np.ones(total, bool)
-        for lo, c in zip(ooff, cases):
-            keep[int(lo):int(lo) + (c["result"] if c["result"] >= 0 else c["cap"])] = False
-        lens = np.array([len(c["bytes"]) for c in cases], np.uint64)
-        _layouts[key] = (blob, [off, lens, ooff, caps], total, keep, np.array([c["result"] for c in cases], np.int64))
-    return _layouts[key]
-
-
-def _run_and_check(eng, codec, flags, key, cases, dictionary=None):
-    blob, rows, total, keep, want = _layout(key, cases)
-    n = len(cases)
-    d_in, d_out, d_meta = eng.alloc(blob.nbytes), eng.alloc(total), eng.alloc(5 * 8 * n)
-    d_dict = eng.alloc(len(dictionary) + 32) if dictionary is not None else None
-    try:
-        eng.h2d(d_in, blob)
-        eng.h2d(d_meta, np.concatenate(rows + [np.zeros(n, np.uint64)]))
-        N.check(N.lib().cj_memset_dev(eng.h, d_out, 0xA5, total))
-        m = [d_meta + 8 * n * k for k in range(5)]
-        if dictionary is None:
-            eng.batch_device(codec, DEC, flags, n, d_in, m[0], m[1], d_out, m[2], m[3], m[4])
-        else:
-            eng.h2d(d_dict + 3, np.frombuffer(dictionary, np.uint8))             # (3 bytes off a granule)
-            N.check(N.lib().cj_dict_batch_device(eng.h, codec, DEC, flags, n, d_in, m[0], m[1], d_out, m[2], m[3], m[4], d_dict + 3, len(dictionary), None))
-        eng.sync()
-        res, out = eng.d2h(m[4], 8 * n, "int64"), eng.d2h(d_out, total)
-    finally:
-        for p in (d_in, d_out, d_meta, d_dict):
-            if p is not None: eng.free(p)
-    _check(key, flags, cases, res, out)
-    return res
-
-
-def _check(key, flags, cases, res, out):
-    _, rows, total, keep, want = _layout(key, cases)
-    tag = lambda i: (key, hex(flags), cases[i]["stream"], "cap", cases[i]["cap"], "U", cases[i]["U"], "got", int(res[i]), "want", int(want[i]))
-    bad = np.nonzero(res != want)[0]
-    assert len(bad) == 0, (len(bad), [tag(i) for i in bad[:6]])
-    ooff = rows[2]
-    dirty = np.nonzero(out[keep] != 0xA5)[0]
-    if len(dirty):                                 # which chunk's neighbourhood: the first byte that changed
-        at = int(np.nonzero(keep)[0][dirty[0]])
-        i = max(int(np.searchsorted(ooff, at, side="right")) - 1, 0)
-        assert False, ("a byte outside [0, result) changed", at - int(ooff[i]), len(dirty), tag(i))
-    for i in np.nonzero(want > 0)[0]:
-        lo = int(ooff[i])
-        assert out[lo:lo + int(want[i])].tobytes() == cases[i]["out"], ("bytes", tag(i))
-
-
-def _lz4_bodies(win):
-    return K.LZ4_BODIES if win >= 65536 else K.LZ4_BODIES[:2]          # (the body with the 300-byte runs: 64 KiB window only)
-
-
-LE32, LE16 = N.FLAG_CHUNKS_LE_32K, N.FLAG_CHUNKS_LE_16K
-PATHS = [pytest.param(WAVE, 65536, id="wave-per-chunk"), pytest.param(LANE, 65536, id="lane-per-chunk"),
-         pytest.param(LDS | PK, 65536, id="lds+parse-kernel"), pytest.param(LDS | FUSED, 65536, id="lds+fused-parse"), pytest.param(0, 65536, id="default"),
-         pytest.param(LE32, 32768, id="le32k"), pytest.param(LE32 | PK, 32768, id="le32k+parse-kernel"), pytest.param(LE32 | FUSED, 32768, id="le32k+fused-parse"),
-         pytest.param(LE16, 16384, id="le16k"), pytest.param(LE16 | PK, 16384, id="le16k+parse-kernel"), pytest.param(LE16 | FUSED, 16384, id="le16k+fused-parse")]
-
-
 @pytest.mark.parametrize("flags,win", PATHS)
 def test_lz4_capacity_sweep(eng, flags, win):
-    for body in _lz4_bodies(win):
-        _run_and_check(eng, LZ4, flags, ("lz4", body), K.lz4_cases(body))
+    for body in K.lz4_bodies(win):
+        K.run_and_check(eng, LZ4, flags, ("lz4", body), K.lz4_cases(body))
 
 
 @pytest.mark.parametrize("flags,win", PATHS)
 def test_snappy_declared_length_and_capacity_sweep(eng, flags, win):
     for body in K.SNAPPY_BODIES:
-        _run_and_check(eng, SN, flags, ("snappy", body), K.snappy_cases(body))
+        K.run_and_check(eng, SN, flags, ("snappy", body), K.snappy_cases(body))
 
 
 @pytest.mark.parametrize("codec", [LZ4, SN])
@@ -131,14 +50,14 @@ def test_default_pipeline_above_the_one_kernel_limit(eng, codec):
     cs = K.lz4_cases("b") if codec == LZ4 else K.snappy_cases("b")
     n = 16384 + 41
     assert len(cs) < n
-    _run_and_check(eng, codec, 0, ("above", codec), [cs[i % len(cs)] for i in range(n)])
+    K.run_and_check(eng, codec, 0, ("above", codec), [cs[i % len(cs)] for i in range(n)])
 
 
 @pytest.mark.parametrize("codec", [LZ4, SN])
 def test_big_chunks_capacity_sweep(eng, codec):
     """the ~100 KiB streams under CJ_FLAG_BIG_CHUNKS: around U and around 32 768, 65 536 (below it the chunk takes the small-chunk path: intended)
     and 98 304 (the slabs' boundaries)"""
-    _run_and_check(eng, codec, N.FLAG_BIG_CHUNKS, ("big", codec), K.big_cases("lz4" if codec == LZ4 else "snappy"))
+    K.run_and_check(eng, codec, N.FLAG_BIG_CHUNKS, ("big", codec), K.big_cases("lz4" if codec == LZ4 else "snappy"))
 
 
 @pytest.mark.parametrize("flags", [pytest.param(WAVE, id="wave-per-chunk"), pytest.param(LDS | FUSED, id="lds+fused-parse")])
@@ -147,7 +66,7 @@ def test_lz4_size_prefix_sweep(eng, flags):
     for body in K.LZ4_BODIES[:2]:
         cs = K.lz4_prefix_cases(body)
         assert {-4, -5, -6, -7} <= {c["result"] for c in cs}
-        _run_and_check(eng, LZ4, flags | N.FLAG_LZ4_SIZE_PREFIX, ("prefix", body), cs)
+        K.run_and_check(eng, LZ4, flags | N.FLAG_LZ4_SIZE_PREFIX, ("prefix", body), cs)
 
 
 def test_lz4_dictionary_capacity_sweep(eng):
@@ -155,7 +74,7 @@ def test_lz4_dictionary_capacity_sweep(eng):
     for body in K.LZ4_BODIES:
         cs = K.lz4_dict_cases(body)
         assert sum(c["result"] >= 0 for c in cs) >= 150
-        _run_and_check(eng, LZ4, 0, ("dict", body), cs, dictionary=D.dictionary(4096))
+        K.run_and_check(eng, LZ4, 0, ("dict", body), cs, dictionary=D.dictionary(4096))
 
 
 @functools.lru_cache(maxsize=None)
@@ -197,7 +116,7 @@ def test_accepted_chunks_are_decoded_by_the_workgroup_decoder(eng, codec):
         reached = sum(_reaches_the_in_kernel_checks(codec, c) for c in cs)
         assert accepted >= 150 and reached >= accepted + 3000
         assert L.cj_debug_fused_parse_paths(paths, 1) == 0 and L.cj_debug_lds_phase_cycles(cyc, 1) == 0
-        _run_and_check(eng, codec, LDS | FUSED | PROFILE, ("lz4" if codec == LZ4 else "snappy", body), cs)
+        K.run_and_check(eng, codec, LDS | FUSED | PROFILE, ("lz4" if codec == LZ4 else "snappy", body), cs)
         assert L.cj_debug_fused_parse_paths(paths, 0) == 0 and L.cj_debug_lds_phase_cycles(cyc, 0) == 0
         assert sum(paths) == reached, (body, list(paths), reached)
         assert cyc[5] == accepted, (body, cyc[5], accepted)

@@ -5,17 +5,15 @@ streams decoded on the device behind the encoder on the same stream without a wa
 exact - 1 and 0 and batches of 1, 3 and 5 through both entries; a batch of 20 through several turns at a shrunken slot budget; the argument checks; torch
 tensors on a side stream; two engines on one device."""
 import os
-import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
 import deflate_enc_cases as E
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
-G = 64          # guard bytes around every output slot
 _want = {}
 
 
@@ -34,56 +32,22 @@ def eng():
 
 
 def _device_call(e, N, wrap, chunks, caps, decode=False, in_lens=None):
-    """cj_deflate_compress_batch_device over chunks packed in HBM at every misalignment; slot i lies at least G bytes behind slot i - 1's
-    end, at every misalignment too, and the whole output is filled with 0xA5 first: (results, output, offsets).  decode: the streams
-    are then decoded by cj_deflate_batch_device on the same stream, with the encoder's device results as its in_len and no wait in
-    between: (.., decoded results, decoded output, its offsets) are appended"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for i, c in enumerate(caps):
-        run += (7 * i) % 16
-        ooff.append(run); run += int(c) + G
-    total = run + 64
-    lens = [len(c) for c in chunks] if in_lens is None else in_lens
-    doff, drun = [], G
-    for c in chunks:
-        doff.append(drun); drun += len(c) + G
-    metas = [np.array(a, np.uint64) for a in (off, lens, ooff, caps, doff, [len(c) for c in chunks])]
-    d_in, d_out, d_dec = e.alloc(blob.nbytes), e.alloc(total), e.alloc(drun + 64)
-    d_meta = [e.alloc(8 * n) for _ in range(8)]
-    L = N.lib()
-    try:
-        e.h2d(d_in, blob)
-        N.check(L.cj_memset_dev(e.h, d_out, 0xA5, total))
-        N.check(L.cj_memset_dev(e.h, d_dec, 0xA5, drun + 64))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        e.sync()
-        N.check(L.cj_deflate_compress_batch_device(e.h, wrap, 0, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[6], None))
-        if decode:          # in_len = the encoder's results, still on the device
-            N.check(L.cj_deflate_batch_device(e.h, wrap, N.OP_DECOMPRESS, 0, n, d_out, d_meta[2], d_meta[6], d_dec, d_meta[4], d_meta[5], d_meta[7], None))
-        e.sync()
-        got = (e.d2h(d_meta[6], 8 * n, "int64"), e.d2h(d_out, total), ooff)
+    """cj_deflate_compress_batch_device in the harness's guarded run (tests/device_batch.py): chunks at every misalignment, slot i at
+    least G bytes behind slot i - 1's end, at every misalignment too, the output filled with 0xA5 first: (results, output, offsets).
+    decode: the streams are then decoded by cj_deflate_batch_device on the same stream, with the encoder's device results as its
+    in_len and no wait in between: (.., decoded results, decoded output, its offsets) are appended"""
+    n, L = len(chunks), N.lib()
+    blob, off, lens = DB.pack(chunks)
+    ooff, total = DB.out_slots(caps, mis=DB.out_mis)
+    with DB.device_batch(e, blob, off, lens if in_lens is None else in_lens, ooff, caps, total) as b:
+        d_out, out_off, res = b.args[3], b.args[4], b.args[6]
         if decode:
-            got += (e.d2h(d_meta[7], 8 * n, "int64"), e.d2h(d_dec, drun + 64), doff)
-        return got
-    finally:
-        for p in [d_in, d_out, d_dec] + d_meta:
-            e.free(p)
-
-
-def _guards_intact(out, ooff, caps):
-    for i, (lo, cap) in enumerate(zip(ooff, caps)):
-        if not ((out[lo - G:lo] == 0xA5).all() and (out[lo + int(cap):lo + int(cap) + G] == 0xA5).all()):
-            return i
-    return None
+            d_dec, dec_off, dec_cap, dres, doff, dtotal = b.output([len(c) for c in chunks])
+        N.check(L.cj_deflate_compress_batch_device(e.h, wrap, 0, n, *b.args, None))
+        if decode:          # in_len = the encoder's results, still on the device
+            N.check(L.cj_deflate_batch_device(e.h, wrap, N.OP_DECOMPRESS, 0, n, d_out, out_off, res, d_dec, dec_off, dec_cap, dres, None))
+        got = b.read() + ([int(o) for o in ooff],)
+        return got + (b.read_row(dres), e.d2h(d_dec, dtotal), doff) if decode else got
 
 
 @pytest.mark.parametrize("wrap", E.WRAPS)
@@ -100,7 +64,7 @@ def test_device_batch_emits_the_models_bytes_and_the_decoder_reads_them(eng, wra
         assert got == s, (k, next(j for j in range(r) if got[j] != s[j]))
         assert zlib.decompress(got, E.WBITS[wrap]) == chunks[i], k
         assert dres[i] == len(chunks[i]) and dout[doff[i]:doff[i] + len(chunks[i])].tobytes() == chunks[i], (k, int(dres[i]))
-    assert _guards_intact(out, ooff, caps) is None and _guards_intact(dout, doff, [len(c) for c in chunks]) is None
+    assert DB.guards_intact(out, ooff, caps) is None and DB.guards_intact(dout, doff, [len(c) for c in chunks]) is None
 
 
 @pytest.mark.parametrize("wrap", E.WRAPS)
@@ -117,7 +81,7 @@ def test_capacities_exact_one_less_and_zero(eng, wrap):
                 assert res[i] == exact[i] and out[ooff[i]:ooff[i] + exact[i]].tobytes() == want(k, wrap)[1], (k, caps[i], int(res[i]))
             else:
                 assert res[i] == E.OUT_TOO_SMALL, (k, caps[i], int(res[i]))
-        assert _guards_intact(out, ooff, caps) is None
+        assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_batches_of_one_three_and_five_with_mixed_lengths(eng):
@@ -130,7 +94,7 @@ def test_batches_of_one_three_and_five_with_mixed_lengths(eng):
             res, out, ooff = _device_call(e, N, wrap, chunks, caps)
             for i, k in enumerate(part):
                 assert (int(res[i]), out[ooff[i]:ooff[i] + max(int(res[i]), 0)].tobytes()) == want(k, wrap), (k, wrap)
-            assert _guards_intact(out, ooff, caps) is None
+            assert DB.guards_intact(out, ooff, caps) is None
 
 
 def _host_call(e, N, wrap, chunks, caps):
@@ -138,19 +102,11 @@ def _host_call(e, N, wrap, chunks, caps):
     behind slot i - 1's end at every misalignment too, the whole output filled with 0xA5 first: (results, output, offsets)"""
     import ctypes as C
     n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for i, c in enumerate(caps):
-        run += (7 * i) % 16
-        ooff.append(run); run += int(c) + G
-    out = np.full(run + 64, 0xA5, np.uint8)
-    ins = (C.c_void_p * n)(*[blob.ctypes.data + o for o in off])
+    blob, off, _ = DB.pack(chunks)
+    ooff, total = DB.out_slots(caps, mis=DB.out_mis)
+    ooff = [int(o) for o in ooff]
+    out = np.full(total, 0xA5, np.uint8)
+    ins = (C.c_void_p * n)(*[blob.ctypes.data + int(o) for o in off])
     lens = (C.c_size_t * n)(*[len(c) for c in chunks])
     outs = (C.c_void_p * n)(*[out.ctypes.data + o for o in ooff])
     ocaps = (C.c_size_t * n)(*[int(c) for c in caps])
@@ -174,7 +130,7 @@ def test_host_entry_emits_the_models_bytes_at_every_capacity(eng, wrap):
                 assert res[i] == exact[i] and out[ooff[i]:ooff[i] + exact[i]].tobytes() == want(k, wrap)[1], (k, caps[i], int(res[i]))
             else:
                 assert res[i] == E.OUT_TOO_SMALL, (k, caps[i], int(res[i]))
-        assert _guards_intact(out, ooff, caps) is None
+        assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_host_batches_of_one_three_and_five_with_mixed_lengths(eng):
@@ -187,7 +143,7 @@ def test_host_batches_of_one_three_and_five_with_mixed_lengths(eng):
             res, out, ooff = _host_call(e, N, wrap, chunks, caps)
             for i, k in enumerate(part):
                 assert (int(res[i]), out[ooff[i]:ooff[i] + max(int(res[i]), 0)].tobytes()) == want(k, wrap), (k, wrap)
-            assert _guards_intact(out, ooff, caps) is None
+            assert DB.guards_intact(out, ooff, caps) is None
 
 
 @pytest.mark.parametrize("wrap", E.WRAPS)
@@ -232,7 +188,7 @@ def test_twenty_chunks_through_several_turns_of_a_shrunken_slot_budget(eng):
         assert L.cj_debug_deflate_slot_budget(prev) == 3 * 262400
     for i, k in enumerate(names):
         assert (int(res[i]), out[ooff[i]:ooff[i] + int(res[i])].tobytes()) == want(k, E.GZIP), k
-    assert _guards_intact(out, ooff, caps) is None
+    assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_five_chunks_of_two_pieces_at_a_budget_below_one_slot(eng):
@@ -255,7 +211,7 @@ def test_five_chunks_of_two_pieces_at_a_budget_below_one_slot(eng):
         assert int(res[i]) == int(res0[i]) > 0, i
         assert out[ooff[i]:ooff[i] + int(res[i])].tobytes() == out0[ooff[i]:ooff[i] + int(res0[i])].tobytes(), i
         assert zlib.decompress(out[ooff[i]:ooff[i] + int(res[i])].tobytes(), 31) == c, i
-    assert _guards_intact(out, ooff, caps) is None
+    assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_empty_batches_and_bad_arguments(eng):
@@ -284,6 +240,4 @@ def test_empty_batches_and_bad_arguments(eng):
 
 def test_device_entries_on_torch_tensors_on_a_side_stream():
     """deflate_compress_many_device on torch tensors with sync=False, then the decode, in a child that imports torch BEFORE cramjam_amd"""
-    r = subprocess.run([sys.executable, os.path.join(E.ROOT, "tests", "deflate_encode_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "deflate encode: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(E.ROOT, "tests", "deflate_encode_torch_child.py"), "deflate encode: ok", 600)

@@ -3,16 +3,14 @@ stream of tests/deflate_cases.py through the device and the host entry, bad chun
 every output slot; batches of 1, 3 and 5 chunks (idle wavefronts in the workgroup); the size query; capacities exact, exact - 1 and 0
 against zlib's verdict at that capacity; a stream of more than 1 MiB; the argument checks; torch tensors on a side stream."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import deflate_cases as D
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
-G = 64          # guard bytes around every output slot
 
 
 @pytest.fixture(scope="module")
@@ -20,48 +18,6 @@ def eng():
     from cramjam_amd import _native as N
     from cramjam_amd.batch import _engine
     return _engine(0), N
-
-
-def _device_call(e, N, wrap, chunks, caps, sizes=False):
-    """cj_deflate_batch_device (sizes: cj_deflate_batch_sizes_device) over chunks packed in HBM at every misalignment; slot i lies G bytes
-    behind slot i - 1's end and the whole output is filled with 0xA5 first: (results, output, offsets)"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for c in caps:
-        ooff.append(run); run += int(c) + G
-    total = run + 64
-    metas = [np.array(a, np.uint64) for a in (off, [len(c) for c in chunks], ooff, caps)]
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * n) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        if sizes:
-            N.check(N.lib().cj_deflate_batch_sizes_device(e.h, wrap, 0, n, d_in, d_meta[0], d_meta[1], d_meta[4], None))
-        else:
-            N.check(N.lib().cj_deflate_batch_device(e.h, wrap, N.OP_DECOMPRESS, 0, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * n, "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
-
-
-def _guards_intact(out, ooff, caps, res):
-    """nothing outside the slots (what a chunk left inside its slot behind its result, or with an error, does not matter)"""
-    for i, (lo, cap) in enumerate(zip(ooff, caps)):
-        if not ((out[lo - G:lo] == 0xA5).all() and (out[lo + int(cap):lo + int(cap) + G] == 0xA5).all()):
-            return i
-    return None
 
 
 def _shuffled(wrap):
@@ -76,12 +32,12 @@ def test_device_batch_over_all_fixtures(eng, wrap):
     assert sum(1 for c in cs if c["result"] < 0) >= 50 and sum(1 for c in cs if c["result"] >= 0) >= 50
     for part in (cs[:1], cs[1:4], cs[4:9], cs):                       # 1, 3 and 5 chunks: idle wavefronts in the last workgroup
         caps = [c["cap"] for c in part]
-        res, out, ooff = _device_call(e, N, wrap, [c["bytes"] for c in part], caps)
+        res, out, ooff = D.device_call(e, N, wrap, [c["bytes"] for c in part], caps)
         for i, c in enumerate(part):
             assert res[i] == c["result"], (c["name"], int(res[i]), c["result"])
             if c["result"] >= 0:
                 assert D.sha(out[ooff[i]:ooff[i] + c["result"]]) == c["sha256"], c["name"]
-        assert _guards_intact(out, ooff, caps, res) is None
+        assert DB.guards_intact(out, ooff, caps) is None
 
 
 @pytest.mark.parametrize("wrap", D.WRAPS)
@@ -108,7 +64,7 @@ def test_size_query_and_the_decode_laid_out_from_it(eng, wrap):
     chunks = [c["bytes"] for c in cs]
     want = [D.size_verdict(wrap, s) for s in chunks]
     assert batch.deflate_sizes(chunks, wrapper=D.WRAP_NAME[wrap]) == want
-    res, _, _ = _device_call(e, N, wrap, chunks, [0] * len(cs), sizes=True)
+    res, _, _ = D.device_call(e, N, wrap, chunks, [0] * len(cs), sizes=True)
     assert [int(r) for r in res] == want
     # the size query's errors are the decoder's, except checksum errors
     full = [D.verdict(wrap, s, None)[0] for s in chunks]
@@ -130,12 +86,12 @@ def test_capacities_exact_one_less_and_zero(eng, wrap):
     chunks = [c["bytes"] for c in cs]
     exact = [c["result"] if c["result"] >= 0 else c["cap"] for c in cs]
     for caps in (exact, [max(x - 1, 0) for x in exact], [0] * len(cs)):
-        res, out, ooff = _device_call(e, N, wrap, chunks, caps)
+        res, out, ooff = D.device_call(e, N, wrap, chunks, caps)
         for i, c in enumerate(cs):
             r, raw = D.verdict(wrap, c["bytes"], caps[i])
             assert res[i] == r, (c["name"], caps[i], int(res[i]), r)
             assert r < 0 or out[ooff[i]:ooff[i] + r].tobytes() == raw, (c["name"], caps[i])
-        assert _guards_intact(out, ooff, caps, res) is None
+        assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_a_stream_of_more_than_1_mib(eng):
@@ -146,9 +102,9 @@ def test_a_stream_of_more_than_1_mib(eng):
     assert len(raw) > 1 << 20
     for wrap in D.WRAPS:
         s = D.compress(raw, 6, 0, wrap)
-        res, out, ooff = _device_call(e, N, wrap, [s, s[:len(s) // 2], s], [len(raw), len(raw), len(raw) - 1])
+        res, out, ooff = D.device_call(e, N, wrap, [s, s[:len(s) // 2], s], [len(raw), len(raw), len(raw) - 1])
         assert list(res) == [len(raw), D.EOF, D.OUT_TOO_SMALL] and out[ooff[0]:ooff[0] + len(raw)].tobytes() == raw
-        assert _guards_intact(out, ooff, [len(raw), len(raw), len(raw) - 1], res) is None
+        assert DB.guards_intact(out, ooff, [len(raw), len(raw), len(raw) - 1]) is None
         assert batch.deflate_sizes([s], wrapper=D.WRAP_NAME[wrap]) == [len(raw)]
 
 
@@ -179,6 +135,4 @@ def test_empty_batches_and_bad_arguments(eng):
 
 def test_device_entries_on_torch_tensors_on_a_side_stream():
     """the device-resident calls on torch tensors with sync=False, in a child that imports torch BEFORE cramjam_amd (tests/device_api_child.py says why)"""
-    r = subprocess.run([sys.executable, os.path.join(D.ROOT, "tests", "deflate_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "deflate: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(D.ROOT, "tests", "deflate_torch_child.py"), "deflate: ok", 600)

@@ -10,7 +10,8 @@ import pytest
 
 import deflate_cases as D
 import deflate_synth as S
-from test_deflate_gpu import _device_call, _guards_intact, eng  # noqa: F401  (eng: the module's engine fixture)
+import device_batch as DB
+from test_deflate_gpu import eng  # noqa: F401  (the module's engine fixture)
 
 pytestmark = pytest.mark.gpu
 _cache = {}
@@ -46,7 +47,7 @@ def _check(part, caps, res, out, ooff, want=None):
         r, raw = want[i] if want is not None else (c["result"], c["out"])
         assert res[i] == r, (c["name"], int(caps[i]), int(res[i]), r)
         assert r < 0 or out[ooff[i]:ooff[i] + r].tobytes() == raw, (c["name"], int(caps[i]))
-    bad = _guards_intact(out, ooff, caps, res)
+    bad = DB.guards_intact(out, ooff, caps)
     assert bad is None, part[bad]["name"]
 
 
@@ -60,7 +61,7 @@ def test_device_batch_over_all_synthesized_and_other_encoders_streams(eng, wrap)
     assert sum(1 for k in range(0, len(cs) - 3, 4) if len({c["family"] for c in cs[k:k + 4]}) > 1) > 0.6 * (len(cs) // 4)
     for part in (cs[:1], cs[1:4], cs[4:9], cs):                       # 1, 3 and 5 chunks: idle wavefronts in the last workgroup
         caps = [c["cap"] for c in part]
-        res, out, ooff = _device_call(e, N, wrap, [c["bytes"] for c in part], caps)
+        res, out, ooff = D.device_call(e, N, wrap, [c["bytes"] for c in part], caps)
         _check(part, caps, res, out, ooff)
 
 
@@ -82,7 +83,7 @@ def test_capacities_one_less_and_zero(eng, wrap):
     chunks = [c["bytes"] for c in cs]
     exact = [c["result"] if c["result"] >= 0 else c["cap"] for c in cs]
     for caps in ([max(x - 1, 0) for x in exact], [0] * len(cs)):
-        res, out, ooff = _device_call(e, N, wrap, chunks, caps)
+        res, out, ooff = D.device_call(e, N, wrap, chunks, caps)
         _check(cs, caps, res, out, ooff, [D.verdict(wrap, c["bytes"], cap) for c, cap in zip(cs, caps)])
 
 
@@ -98,7 +99,7 @@ def test_cut_capacities(eng, wrap, family):
     part, caps = [t[0] for t in todo], [t[1] for t in todo]
     want = [D.verdict(wrap, c["bytes"], cap) for c, cap in todo]
     assert D.OUT_TOO_SMALL in {w[0] for w in want}
-    res, out, ooff = _device_call(e, N, wrap, [c["bytes"] for c in part], caps)
+    res, out, ooff = D.device_call(e, N, wrap, [c["bytes"] for c in part], caps)
     _check(part, caps, res, out, ooff, want)
     from cramjam_amd import batch
     res, outs = batch.deflate_decompress_many([c["bytes"] for c in part], output_lens=caps, wrapper=D.WRAP_NAME[wrap])
@@ -113,7 +114,7 @@ def test_size_query_device_and_host(eng, wrap):
     cs = _cases(wrap)
     chunks = [c["bytes"] for c in cs]
     want = [D.size_verdict(wrap, s) for s in chunks]
-    res, _, _ = _device_call(e, N, wrap, chunks, [0] * len(cs), sizes=True)
+    res, _, _ = D.device_call(e, N, wrap, chunks, [0] * len(cs), sizes=True)
     for c, r, w in zip(cs, res, want):
         assert int(r) == w, (c["name"], int(r), w)
     assert batch.deflate_sizes(chunks, wrapper=D.WRAP_NAME[wrap]) == want

@@ -4,10 +4,10 @@ torch tensors (any object with __cuda_array_interface__ or __dlpack__ works; the
 is compared with the oracle: 24 576 chunks decoded from tensors, compress round trips, DLPack-only objects, refusals.  The checks
 run in a child process (tests/device_api_child.py) that imports torch first."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,5 +15,4 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 def test_device_resident_batches_from_torch_tensors():
     pytest.importorskip("torch")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "device_api_child.py")], capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0 and "device api: ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(HERE, "device_api_child.py"), "device api: ok", 1200)

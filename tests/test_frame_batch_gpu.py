@@ -7,12 +7,11 @@ import json
 import os
 import random
 import struct
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import device_batch as DB
 import oracle
 import cramjam_amd as cj
 from cramjam_amd import _native as N
@@ -301,5 +300,4 @@ def test_compress_capacity_too_small_is_a_write_error_with_no_write():
 
 def test_device_resident_frame_batches_from_torch_tensors():
     pytest.importorskip("torch")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "frame_batch_child.py")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "frame batch device: ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(HERE, "frame_batch_child.py"), "frame batch device: ok", 900)

@@ -7,6 +7,7 @@ import zlib
 import numpy as np
 import pytest
 
+import device_batch as DB
 import zstd_cases as Z
 
 pytestmark = pytest.mark.gpu
@@ -27,35 +28,10 @@ def _raws():
 
 
 def _run(e, N, chunks, caps, call):
-    """call(n, d_in, in_off, in_len, d_out, out_off, out_cap, result) over chunks packed in HBM at every misalignment, the output
-    filled with 0xA5 first: (results, output)"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], 64
-    for c in caps:
-        ooff.append(run); run += int(c) + 64
-    total = run + 64
-    metas = [np.array(a, np.uint64) for a in (off, [len(c) for c in chunks], ooff, caps)]
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * n) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        N.check(N.lib().cj_memset_dev(e.h, d_meta[4], 0x11, 8 * n))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        N.check(call(n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4]))
-        e.sync()
-        return [int(r) for r in e.d2h(d_meta[4], 8 * n, "int64")], e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
+    """call(n, d_in, in_off, in_len, d_out, out_off, out_cap, result) in the harness's guarded run (tests/device_batch.py): chunks at
+    every misalignment, the output filled with 0xA5 first: (results, output, offsets)"""
+    res, out, ooff = DB.run_chunks(e, lambda *a: N.check(call(len(chunks), *a)), chunks, caps)
+    return [int(r) for r in res], out, ooff
 
 
 def _both(e, N, chunks, caps, call):

@@ -1,6 +1,6 @@
 """The input sweep on the GPU (tests/input_cases.py: where the input ends, the offset at its edges, the overlap grid; expected values from
 the CPU oracle) through every LZ4 and Snappy decoder path of a device-resident batch — the capacity sweep's paths and its harness
-(tests/test_capacity_gpu.py: inputs at every misalignment, 64 guard bytes of 0xA5 around every output slot, the whole output filled before
+(tests/device_batch.py: inputs at every misalignment, 64 guard bytes of 0xA5 around every output slot, the whole output filled before
 the call, the oracle's result and bytes, [result, cap) untouched where the chunk was accepted).  What lies behind a cut's in_len is the
 case's own `after`: the stream's continuation, or 0xFF bytes."""
 import ctypes as C
@@ -9,12 +9,15 @@ import numpy as np
 import pytest
 
 import capacity_cases as K
+import device_batch as DB
 import input_cases as I
 import lz4_dict_model as D
+from capacity_cases import PATHS, lz4_bodies as _lz4_bodies, run_and_check as _run_and_check
 from cramjam_amd import _native as N
-from test_capacity_gpu import FUSED, LDS, LZ4, PATHS, PROFILE, SN, _layout, _lz4_bodies, _run_and_check, eng  # noqa: F401  (eng: the module's engine fixture)
+from test_capacity_gpu import eng  # noqa: F401  (the module's engine fixture)
 
 pytestmark = pytest.mark.gpu
+LZ4, SN, LDS, FUSED, PROFILE = N.CODEC_LZ4_BLOCK, N.CODEC_SNAPPY_RAW, N.FLAG_FORCE_LDS_PER_CHUNK, N.FLAG_FORCE_FUSED_PARSE, 0x1000
 ABOVE = 16384 + 41                                 # chunks: above CJ_FUSED_MAX_CHUNKS
 
 
@@ -73,14 +76,14 @@ def test_dictionary_offsets_and_overlaps(eng):
 
 
 def _sizes(eng, codec, key, cases):
-    """cj_batch_sizes_device over the cases' inputs as _layout packs them (`after` behind every in_len)"""
-    blob, rows, _, _, want = _layout(key, cases)
+    """cj_batch_sizes_device over the cases' inputs as the harness packs them (`after` behind every in_len)"""
+    (blob, off, lens), want = DB.case_pack(key, cases), DB.case_slots(key, cases)[4]
     n = len(cases)
     d_in, d_meta = eng.alloc(blob.nbytes), eng.alloc(3 * 8 * n + 128)
     try:
         eng.h2d(d_in, blob)
         guard = np.full(8, 0x5A5A5A5A5A5A5A5A, np.uint64)
-        eng.h2d(d_meta, np.concatenate([rows[0], rows[1], guard, np.zeros(n, np.uint64), guard]))
+        eng.h2d(d_meta, np.concatenate([off, lens, guard, np.zeros(n, np.uint64), guard]))
         res = d_meta + 8 * (2 * n + 8)
         N.check(N.lib().cj_batch_sizes_device(eng.h, codec, 0, n, d_in, d_meta, d_meta + 8 * n, res, None))
         eng.sync()

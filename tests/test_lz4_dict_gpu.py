@@ -4,16 +4,15 @@ every output slot; the empty dictionary against the plain call; the size query; 
 (tests/hostsim/enc2_linked_model.c with hist = dictionary), the chunk that is too long, the sliced staging, and what the dictionary
 buys against liblz4 without one."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import device_batch as DB
 import lz4_dict_model as D
 
 pytestmark = pytest.mark.gpu
-G = 64          # guard bytes around every output slot
+G = DB.G
 
 
 @pytest.fixture(scope="module")
@@ -24,49 +23,20 @@ def eng():
 
 
 def _device_call(e, N, op, flags, chunks, caps, d, plain=False):
-    """cj_dict_batch_device (plain: cj_batch_device) over chunks packed in HBM at every misalignment, the dictionary 3 bytes off a
-    granule; slot i lies G bytes behind slot i - 1's end and the whole output is filled with 0xA5 first: (results, output, offsets)"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for c in caps:
-        ooff.append(run); run += int(c) + G
-    total = run + 64
-    metas = [np.array(a, np.uint64) for a in (off, [len(c) for c in chunks], ooff, caps)]
-    d_in, d_out, d_dict = e.alloc(blob.nbytes), e.alloc(total), e.alloc(len(d) + 32)
-    d_meta = [e.alloc(8 * n) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        if len(d):
-            e.h2d(d_dict + 3, np.frombuffer(d, np.uint8))
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        if plain:
-            N.check(N.lib().cj_batch_device(e.h, 0, op, flags, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], None))
-        else:
-            N.check(N.lib().cj_dict_batch_device(e.h, 0, op, flags, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4],
-                                                 d_dict + 3 if len(d) else None, len(d), None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * n, "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out, d_dict] + d_meta:
-            e.free(p)
+    """cj_dict_batch_device (plain: cj_batch_device) in the harness's guarded run (tests/device_batch.py): chunks at every misalignment,
+    the dictionary 3 bytes off a granule, G guard bytes around every slot, the output filled with 0xA5 first: (results, output, offsets)"""
+    n, L = len(chunks), N.lib()
+    if plain:
+        call = lambda i, o, l, out, oo, oc, r, dd: N.check(L.cj_batch_device(e.h, 0, op, flags, n, i, o, l, out, oo, oc, r, None))
+    else:
+        call = lambda i, o, l, out, oo, oc, r, dd: N.check(L.cj_dict_batch_device(e.h, 0, op, flags, n, i, o, l, out, oo, oc, r, dd if len(d) else None, len(d), None))
+    return DB.run_chunks(e, call, chunks, caps, dictionary=d)
 
 
 def _guards_intact(out, ooff, caps, res, may_write_inside):
     """nothing outside the slots; inside a slot nothing behind the bytes produced (a refused chunk may have written inside its slot)"""
-    for i, (lo, cap) in enumerate(zip(ooff, caps)):
-        used = int(res[i]) if res[i] >= 0 else (int(cap) if may_write_inside else 0)
-        if not ((out[lo - G:lo] == 0xA5).all() and (out[lo + used:lo + int(cap) + G] == 0xA5).all()):
-            return i
-    return None
+    bad = DB.first_dirty(out, DB.untouched(ooff, res, len(out), written=caps if may_write_inside else None), ooff)
+    return None if bad is None else bad[0]
 
 
 def test_device_batches_over_all_fixtures_one_batch_per_dictionary(eng):
@@ -266,6 +236,4 @@ def test_the_dictionary_beats_liblz4_without_one_in_every_size_class():
 
 def test_device_entries_on_torch_tensors_on_a_side_stream():
     """the device-resident calls with dictionary=<tensor>, in a child that imports torch BEFORE cramjam_amd (tests/device_api_child.py says why)"""
-    r = subprocess.run([sys.executable, os.path.join(D.ROOT, "tests", "lz4_dict_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "dictionary: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(D.ROOT, "tests", "lz4_dict_torch_child.py"), "dictionary: ok", 600)

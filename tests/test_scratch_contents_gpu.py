@@ -12,8 +12,8 @@ four preparations:
            runs reversed first, then in order
 
 After each fill the first and last 64 bytes of every filled buffer are read back (cj_debug_scratch_peek) and held to the pattern.
-The case lists and harnesses are the suite's own, by import (capacity_cases + test_capacity_gpu._run_and_check, neighbour_cases +
-test_neighbours_gpu._device / _host_check, the generators of test_large_gpu / test_frames_gpu / test_frame_batch_gpu): the expected
+The case lists and harnesses are the suite's own, by import (capacity_cases + its run_and_check on tests/device_batch.py, neighbour_cases +
+its device / host_check, the generators of test_large_gpu / test_frames_gpu / test_frame_batch_gpu): the expected
 values are the CPU oracle's, the models' or recorded reference verdicts, never an earlier GPU run's, and the harnesses' assertions —
 64 guard bytes of 0xA5 around every output slot, nothing written behind a result, the input read back unchanged — hold under every
 preparation.  On top of them all runs of one family must give identical results and identical bytes.
@@ -31,11 +31,9 @@ import pytest
 import capacity_cases as K
 import neighbour_cases as NC
 import oracle
-import test_capacity_gpu as TC
 import test_frame_batch_gpu as TFB
 import test_frames_gpu as TF
 import test_large_gpu as TL
-import test_neighbours_gpu as TN
 from cramjam_amd import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -103,52 +101,31 @@ def _fill_and_peek(h, pattern):
 
 
 # ---- one run of a batch: the suite's harness around it, then what it computed as a list of (result, crc of the bytes) per chunk -------------
-class _Recording:
-    """an engine whose device-to-host reads are kept: the harnesses read back the results and the whole output and return neither"""
-
-    def __init__(self, eng):
-        self._eng, self.reads = eng, []
-
-    def __getattr__(self, name):
-        return getattr(self._eng, name)
-
-    def d2h(self, dptr, nbytes, dtype="uint8"):
-        a = self._eng.d2h(dptr, nbytes, dtype)
-        self.reads.append(a)
-        return a
-
-
 def _sig(res, out, ooff, cases):
     crc = lambda i, r: zlib.crc32(out[int(ooff[i]):int(ooff[i]) + r].tobytes())
     return [(int(r), crc(i, int(r)) if r > 0 and not c.get("sized") else None) for i, (r, c) in enumerate(zip(res, cases))]
 
 
 def capacity_run(codec, flags):
-    """test_capacity_gpu._run_and_check: the oracle's result and bytes, both guards, nothing behind an accepted result"""
+    """capacity_cases.run_and_check: the oracle's result and bytes, both guards, nothing behind an accepted result"""
     def run(e, key, cases):
-        rec = _Recording(e)
-        TC._run_and_check(rec, codec, flags, key, cases)
-        res, out = rec.reads
-        return _sig(res, out, TC._layout(key, cases)[1][2], cases)
+        return _sig(*K.run_and_check(e, codec, flags, key, cases), cases)
     return run
 
 
 def device_run(call_of, dictionary=None):
-    """test_neighbours_gpu._device: the same, and the input read back unchanged.  call_of(e, n) -> the call over n chunks"""
+    """neighbour_cases.device: the same, and the input read back unchanged.  call_of(e, n) -> the call over n chunks"""
     def run(e, key, cases):
-        rec = _Recording(e)
-        TN._device(rec, key, cases, RING, call_of(e, len(cases)), dictionary=dictionary)
-        res, out, _ = rec.reads
-        return _sig(res, out, TN._out_slots(key, cases)[1], cases)
+        return _sig(*NC.device(e, key, cases, RING, call_of(e, len(cases)), dictionary=dictionary), cases)
     return run
 
 
 def host_run(call):
-    """a host entry (the library's own staging: d_in, d_out, d_meta, h_in, h_out, the host rows) held by test_neighbours_gpu._host_check.
+    """a host entry (the library's own staging: d_in, d_out, d_meta, h_in, h_out, the host rows) held by neighbour_cases.host_check.
     call(e, cases) -> (results, outputs)"""
     def run(e, key, cases):
         res, outs = call(e, cases)
-        TN._host_check(key, cases, res, outs)
+        NC.host_check(key, cases, res, outs)
         return [(int(r), zlib.crc32(bytes(o)) if r > 0 else None) for r, o in zip(res, outs)]
     return run
 
@@ -169,7 +146,7 @@ def family(name, default_engine=False):
 
 
 # d_pmeta, d_lanelist, d_tab, d_sync: the workgroup decoder behind the parse kernel and with the parse inside it, on every window
-LDS_PATHS = [p for p in TC.PATHS if p.id not in ("wave-per-chunk", "lane-per-chunk")]
+LDS_PATHS = [p for p in K.PATHS if p.id not in ("wave-per-chunk", "lane-per-chunk")]
 assert [p.id for p in LDS_PATHS] == ["lds+parse-kernel", "lds+fused-parse", "default", "le32k", "le32k+parse-kernel", "le32k+fused-parse", "le16k",
                                      "le16k+parse-kernel", "le16k+fused-parse"]
 for _p in LDS_PATHS:
@@ -275,8 +252,8 @@ def _blosc(which):
     L = N.lib()
     flags, cs = NC.blosc_cases(which)
     call_of = lambda e, n: lambda i, o, l, out, oo, oc, r: N.check(L.cj_blosc_batch_device(e.h, 0, i, o, l, out, oo, oc, r, n, None, flags, None))
-    # (the host entry takes each chunk's capacity from its own header: the cases whose capacity is that — test_neighbours_gpu's choice)
-    hs = TN._shuffled([c for c in cs if len(c["bytes"]) >= 16 and int.from_bytes(c["bytes"][4:8], "little") == c["cap"]])
+    # (the host entry takes each chunk's capacity from its own header: the cases whose capacity is that — the neighbour sweep's choice)
+    hs = NC.shuffled([c for c in cs if len(c["bytes"]) >= 16 and int.from_bytes(c["bytes"][4:8], "little") == c["cap"]])
     return [(("blosc", which), cs, device_run(call_of)),
             (("blosc", which, "host"), hs, host_run(lambda e, x: e.batch_host(0, DEC, flags, _raws(x), _caps(x), N.BLOSC, params=b"")))]
 
@@ -288,11 +265,11 @@ family("blosc-zcodecs")(lambda: _blosc("zcodecs"))
 @family("bgzf")
 def _bgzf():
     L = N.lib()
-    cs, sz = TN._bgzf_cases(), NC.bgzf_size_cases()
+    cs, sz = NC.bgzf_decode_cases(), NC.bgzf_size_cases()
     dec = lambda e, n: lambda i, o, l, out, oo, oc, r: N.check(L.cj_bgzf_batch_device(e.h, 0, DEC, 0, n, i, o, l, out, oo, oc, r, None))
     size = lambda e, n: lambda i, o, l, out, oo, oc, r: N.check(L.cj_bgzf_sizes_device(e.h, 0, 0, n, i, o, l, r, None))
     return [("bgzf", cs, device_run(dec)), ("bgzf-size", sz, device_run(size)),
-            (("bgzf", "host"), TN._shuffled(cs), host_run(lambda e, x: e.batch_host(0, DEC, 0, _raws(x), _caps(x), N.BGZF)))]
+            (("bgzf", "host"), NC.shuffled(cs), host_run(lambda e, x: e.batch_host(0, DEC, 0, _raws(x), _caps(x), N.BGZF)))]
 
 
 # d_dict_stage, d_dict: the shared dictionary, both directions, at the device and the host entry
@@ -304,15 +281,15 @@ def _dict():
     cs, en = NC.lz4_dict_cases(), NC.encoder_cases("lz4_dict")
     call = lambda op: lambda e, n: lambda i, o, l, out, oo, oc, r, dd: N.check(L.cj_dict_batch_device(e.h, LZ4, op, 0, n, i, o, l, out, oo, oc, r, dd, NC.DICT_LEN, None))
     host = lambda op: host_run(lambda e, x: e.batch_host(LZ4, op, 0, _raws(x), _caps(x), N.DICT, dictionary=d))
-    return [("lz4-dict", cs, device_run(call(DEC), d)), (("lz4-dict", "host"), TN._shuffled(cs), host(DEC)),
-            (("enc", "lz4_dict"), en, device_run(call(ENC), d)), (("enc", "lz4_dict", "host"), TN._shuffled(en), host(ENC))]
+    return [("lz4-dict", cs, device_run(call(DEC), d)), (("lz4-dict", "host"), NC.shuffled(cs), host(DEC)),
+            (("enc", "lz4_dict"), en, device_run(call(ENC), d)), (("enc", "lz4_dict", "host"), NC.shuffled(en), host(ENC))]
 
 
 # d_deflate_slots (the DEFLATE encoder, BGZF compress), d_zstd_enc_slots, and the LZ4 / Snappy block encoders (no scratch of their own: the staging)
 def _encoder(codec, kind, what, flags=0):
     cs = NC.encoder_cases(codec)
-    return [(("enc", codec), cs, device_run(lambda e, n: TN._encode_call(e, codec, n))),
-            (("enc", codec, "host"), TN._shuffled(cs), host_run(lambda e, x: e.batch_host(what, ENC, flags, _raws(x), _caps(x), kind)))]
+    return [(("enc", codec), cs, device_run(lambda e, n: NC.encode_call(e, codec, n))),
+            (("enc", codec, "host"), NC.shuffled(cs), host_run(lambda e, x: e.batch_host(what, ENC, flags, _raws(x), _caps(x), kind)))]
 
 
 for _w, _codec in enumerate(("deflate_raw", "deflate_zlib", "deflate_gzip")):
@@ -343,13 +320,13 @@ def _zstd():
     L = N.lib()
     cs = NC.zstd_cases()
     call = lambda e, n: lambda i, o, l, out, oo, oc, r: N.check(L.cj_zstd_batch_device(e.h, N.ZSTD_FRAMES, DEC, 0, n, i, o, l, out, oo, oc, r, None))
-    return [("zstd", cs, device_run(call)), (("zstd", "host"), TN._shuffled(cs), host_run(lambda e, x: e.batch_host(N.ZSTD_FRAMES, DEC, 0, _raws(x), _caps(x), N.ZSTD)))]
+    return [("zstd", cs, device_run(call)), (("zstd", "host"), NC.shuffled(cs), host_run(lambda e, x: e.batch_host(N.ZSTD_FRAMES, DEC, 0, _raws(x), _caps(x), N.ZSTD)))]
 
 
 # d_meta, h_meta, h_in, h_out once more: the block decoders' host entry (the engine picks the windows itself)
 @family("blocks-host-entry")
 def _blocks_host():
-    return [(("front", c, "host"), TN._shuffled(NC.front_cases(c)), host_run(lambda e, x, w=w: e.batch_host(w, DEC, 0, _raws(x), _caps(x))))
+    return [(("front", c, "host"), NC.shuffled(NC.front_cases(c)), host_run(lambda e, x, w=w: e.batch_host(w, DEC, 0, _raws(x), _caps(x))))
             for c, w in (("lz4", LZ4), ("snappy", SN))]
 
 

@@ -5,10 +5,10 @@ turn that did not wait for the previous user's event, or did not record its own,
 first one's are reading: the later modes' bytes then differ from the alone run's.  tests/test_scratch_streams_model.py (no GPU)
 holds the inputs, the expectations and the slice counts this test rests on."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+import device_batch as DB
 
 pytestmark = pytest.mark.gpu
 
@@ -21,9 +21,7 @@ TIMEOUT = 300
 
 
 def test_every_scratch_under_two_streams_and_two_threads():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "scratch_streams_child.py")], capture_output=True, text=True, timeout=TIMEOUT)
-    print(r.stdout[-6000:])
-    assert r.returncode == 0 and "scratch streams: ok, %d pairings" % len(NAMES) in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+    r = DB.run_child(os.path.join(HERE, "scratch_streams_child.py"), "scratch streams: ok, %d pairings" % len(NAMES), TIMEOUT)
     for name in NAMES:
         line = next(x for x in r.stdout.splitlines() if x.startswith(name + " ["))
         assert "alone, interleaved, threads ok" in line, line

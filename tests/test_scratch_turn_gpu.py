@@ -5,9 +5,12 @@ engine, each waited for, must give the same results and bytes; both are held to 
 fixtures, with guard bytes around every output slot.  Then B, A, B on the first engine: a turn that does not grow, and one that does
 not shrink.  Closing the engines runs their teardown.  Every input is a valid stream.  (Two caller streams and two host threads on one
 engine: tests/test_scratch_streams_gpu.py.)"""
+import contextlib
+
 import numpy as np
 import pytest
 
+import device_batch as DB
 import lz4_dict_model as D
 import oracle
 import scratch_streams_cases as S
@@ -15,52 +18,17 @@ from cramjam_amd import _native as N
 
 pytestmark = pytest.mark.gpu
 
-G = 64                  # guard bytes around every output slot
-FILL = 0xA5
+FILL = DB.FILL
 
 
-class Batch:
-    """a batch in HBM: the chunks 16 bytes apart, output slot i G bytes behind slot i - 1's end in a buffer filled with FILL, the four
-    metadata rows and the results on the device"""
-
-    def __init__(self, e, chunks, caps):
-        self.e, self.n, self.caps = e, len(chunks), caps
-        off, run = [], 0
-        for c in chunks:
-            off.append(run); run += (len(c) + 15) // 16 * 16 + 16
-        blob = np.zeros(run + 64, np.uint8)
-        for o, c in zip(off, chunks):
-            blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-        self.ooff, run = [], G
-        for c in caps:
-            self.ooff.append(run); run += int(c) + G
-        self.total = run + 64
-        self.ptrs = []
-        self.d_in, self.d_out = self._alloc(blob.nbytes), self._alloc(self.total)
-        e.h2d(self.d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, self.d_out, FILL, self.total))
-        self.meta = []
-        for row in (off, [len(c) for c in chunks], self.ooff, caps):
-            self.meta.append(self._alloc(8 * self.n))
-            e.h2d(self.meta[-1], np.array(row, np.uint64))
-        self.result = self._alloc(8 * self.n)
-        N.check(N.lib().cj_memset_dev(e.h, self.result, 0xEE, 8 * self.n))
-
-    def _alloc(self, nbytes):
-        self.ptrs.append(self.e.alloc(nbytes))
-        return self.ptrs[-1]
-
-    def args(self):
-        """in_base, in_off, in_len, out_base, out_off, out_cap, result"""
-        return (self.d_in, self.meta[0], self.meta[1], self.d_out, self.meta[2], self.meta[3], self.result)
-
-    def read(self):
-        return self.e.d2h(self.result, 8 * self.n, "int64"), self.e.d2h(self.d_out, self.total)
-
-    def free(self):
-        for p in self.ptrs:
-            self.e.free(p)
-        self.ptrs = []
+def _batch(stack, e, chunks, caps):
+    """a batch in HBM by the harness (tests/device_batch.py): the chunks 16 bytes apart, output slot i 64 bytes behind slot i - 1's end
+    in a buffer filled with FILL, the four metadata rows and the results on the device; freed when `stack` closes"""
+    blob, off, lens = DB.pack(chunks, mis=0)
+    ooff, total = DB.out_slots(caps)
+    b = stack.enter_context(DB.device_batch(e, blob, off, lens, ooff, caps, total))
+    b.ooff = [int(o) for o in ooff]
+    return b
 
 
 def _held_to(want, res, out, ooff):
@@ -88,7 +56,7 @@ class Blocks:
         return self.comp[:n], [256] * n, self.raws[:n]
 
     def enqueue(self, e, b):
-        N.check(N.lib().cj_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, self.flags, b.n, *b.args(), None))
+        N.check(N.lib().cj_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_DECOMPRESS, self.flags, b.n, *b.args, None))
 
 
 class Frames:
@@ -104,7 +72,7 @@ class Frames:
         return self.comp[:n], [len(r) for r in self.raws[:n]], self.raws[:n]
 
     def enqueue(self, e, b):
-        N.check(N.lib().cj_frame_batch_device(e.h, N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, b.n, *b.args(), None))
+        N.check(N.lib().cj_frame_batch_device(e.h, N.FORMAT_LZ4_FRAME, N.OP_DECOMPRESS, 0, b.n, *b.args, None))
 
 
 class Dict:
@@ -128,7 +96,7 @@ class Dict:
         if e not in self.d_dict:
             self.d_dict[e] = e.alloc(len(self.d))
             e.h2d(self.d_dict[e], np.frombuffer(self.d, np.uint8))
-        N.check(N.lib().cj_dict_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, 0, b.n, *b.args(), self.d_dict[e], len(self.d), None))
+        N.check(N.lib().cj_dict_batch_device(e.h, N.CODEC_LZ4_BLOCK, N.OP_COMPRESS, 0, b.n, *b.args, self.d_dict[e], len(self.d), None))
 
     def free(self):
         for e, p in self.d_dict.items():
@@ -150,7 +118,7 @@ class FromCall:
         return [r[0] for r in self.rows[:n]], [r[1] for r in self.rows[:n]], [r[2] for r in self.rows[:n]]
 
     def enqueue(self, e, b):
-        a = b.args()
+        a = b.args
         N.check(getattr(N.lib(), self.kind.device)(*self.kind.device_args(e.h, self.what, self.op, self.flags, b.n, a[0:3], a[3:6], a[6], None, None)))
 
     @staticmethod
@@ -198,41 +166,35 @@ def test_a_turn_that_grows_the_scratch_behind_one_in_flight(name):
     case = CASES[name]()
     a, b = case.chunks(case.A), case.chunks(case.B)
     first, second = N.Engine(0), N.Engine(0)
-    made = []
-
-    def batch(e, chunks):
-        made.append(Batch(e, chunks[0], chunks[1]))
-        return made[-1]
-
     try:
-        # A and B back to back, one wait
-        a1, b1 = batch(first, a), batch(first, b)
-        case.enqueue(first, a1)
-        case.enqueue(first, b1)
-        first.sync()
-        # ... and each waited for, on an engine of its own
-        a2, b2 = batch(second, a), batch(second, b)
-        case.enqueue(second, a2)
-        second.sync()
-        case.enqueue(second, b2)
-        second.sync()
-        ref = {}
-        for key, x, y, chunks in (("a", a1, a2, a), ("b", b1, b2, b)):
-            (rx, ox), (ry, oy) = x.read(), y.read()
-            assert (rx == ry).all() and (ox == oy).all(), key
-            getattr(case, "held_to", _held_to)(chunks[2], rx, ox, x.ooff)
-            ref[key] = (rx, ox)
-        # a turn that does not grow, then one that does not shrink
-        again = [("b", batch(first, b)), ("a", batch(first, a)), ("b", batch(first, b))]
-        for _, x in again:
-            case.enqueue(first, x)
-        first.sync()
-        for key, x in again:
-            r, o = x.read()
-            assert (r == ref[key][0]).all() and (o == ref[key][1]).all(), key
+        with contextlib.ExitStack() as stack:
+            batch = lambda e, chunks: _batch(stack, e, chunks[0], chunks[1])
+            # A and B back to back, one wait
+            a1, b1 = batch(first, a), batch(first, b)
+            case.enqueue(first, a1)
+            case.enqueue(first, b1)
+            first.sync()
+            # ... and each waited for, on an engine of its own
+            a2, b2 = batch(second, a), batch(second, b)
+            case.enqueue(second, a2)
+            second.sync()
+            case.enqueue(second, b2)
+            second.sync()
+            ref = {}
+            for key, x, y, chunks in (("a", a1, a2, a), ("b", b1, b2, b)):
+                (rx, ox), (ry, oy) = x.read(), y.read()
+                assert (rx == ry).all() and (ox == oy).all(), key
+                getattr(case, "held_to", _held_to)(chunks[2], rx, ox, x.ooff)
+                ref[key] = (rx, ox)
+            # a turn that does not grow, then one that does not shrink
+            again = [("b", batch(first, b)), ("a", batch(first, a)), ("b", batch(first, b))]
+            for _, x in again:
+                case.enqueue(first, x)
+            first.sync()
+            for key, x in again:
+                r, o = x.read()
+                assert (r == ref[key][0]).all() and (o == ref[key][1]).all(), key
     finally:
-        for x in made:
-            x.free()
         if hasattr(case, "free"):
             case.free()
         first.close()

@@ -4,17 +4,15 @@ at capacities exact, + 64, - 1 and 0 with 64 guard bytes of 0xA5 around every sl
 1, 3, 4, 5 and 257 chunks; the slot budget shrunk to 3 slots; the size query and the decode laid out from it; out= and devices=[0, 0];
 torch tensors on a side stream."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import device_batch as DB
 import zstd_cases as Z
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-G = 64
 
 
 @pytest.fixture(scope="module")
@@ -24,55 +22,9 @@ def eng():
     return _engine(0), N
 
 
-def _device_call(e, N, chunks, caps, sizes=False):
-    """cj_zstd_batch_device (sizes: cj_zstd_batch_sizes_device) over chunks packed in HBM at every misalignment; the output is filled
-    with 0xA5 first and slot i lies G bytes behind slot i - 1's end: (results, output, offsets)"""
-    n = len(chunks)
-    off, run = [], 0
-    for i, c in enumerate(chunks):
-        m = (5 * i) % 16
-        off.append(run + m); run += (m + len(c) + 15) // 16 * 16 + 16
-    blob = np.zeros(run + 64, np.uint8)
-    for o, c in zip(off, chunks):
-        blob[o:o + len(c)] = np.frombuffer(c, np.uint8)
-    ooff, run = [], G
-    for c in caps:
-        ooff.append(run); run += int(c) + G
-    total = run + 64
-    metas = [np.array(a, np.uint64) for a in (off, [len(c) for c in chunks], ooff, caps)]
-    d_in, d_out = e.alloc(blob.nbytes), e.alloc(total)
-    d_meta = [e.alloc(8 * n) for _ in range(5)]
-    try:
-        e.h2d(d_in, blob)
-        N.check(N.lib().cj_memset_dev(e.h, d_out, 0xA5, total))
-        for p, a in zip(d_meta, metas):
-            e.h2d(p, a)
-        if sizes:
-            N.check(N.lib().cj_zstd_batch_sizes_device(e.h, N.ZSTD_FRAMES, 0, n, d_in, d_meta[0], d_meta[1], d_meta[4], None))
-        else:
-            N.check(N.lib().cj_zstd_batch_device(e.h, N.ZSTD_FRAMES, N.OP_DECOMPRESS, 0, n, d_in, d_meta[0], d_meta[1], d_out, d_meta[2], d_meta[3], d_meta[4], None))
-        e.sync()
-        return e.d2h(d_meta[4], 8 * n, "int64"), e.d2h(d_out, total), ooff
-    finally:
-        for p in [d_in, d_out] + d_meta:
-            e.free(p)
-
-
 def _shuffled():
     cs = [c for c in Z.load_cases() if c.name not in Z.DIVERGES_FROM_ZSTD]
     return [cs[k] for k in np.random.default_rng(7).permutation(len(cs))]
-
-
-def _check(part, which, res, out, ooff, caps, sha=Z.sha):
-    for i, c in enumerate(part):
-        want = c.verdicts[which]
-        assert res[i] == want, (c.name, caps[i], int(res[i]), want)
-        lo, cap = ooff[i], int(caps[i])
-        assert (out[lo - G:lo] == 0xA5).all() and (out[lo + cap:lo + cap + G] == 0xA5).all(), c.name
-        if want >= 0:
-            assert (out[lo + want:lo + cap] == 0xA5).all(), c.name        # bytes between the result and the capacity stay untouched
-            if which == 0:
-                assert sha(out[lo:lo + want]) == c.sha, c.name
 
 
 @pytest.mark.parametrize("which", [0, 1, 2, 3])
@@ -80,8 +32,8 @@ def test_all_cases_in_one_batch_at_four_capacities(eng, which):
     e, N = eng
     cs = _shuffled()
     caps = [Z.capacities(c.cap)[which] for c in cs]
-    res, out, ooff = _device_call(e, N, [c.stream for c in cs], caps)
-    _check(cs, which, res, out, ooff, caps)
+    res, out, ooff = Z.device_call(e, N, [c.stream for c in cs], caps)
+    Z.check_batch(cs, which, res, out, ooff, caps)
 
 
 def test_all_cases_in_one_host_batch():
@@ -100,8 +52,8 @@ def test_batch_edges_of_four_wavefronts_per_workgroup(eng, n):
     ok, bad = [c for c in cs if c.accepted and c.cap < 8192], [c for c in cs if not c.accepted]
     part = [(bad if i % 3 == 1 else ok)[i % 50] for i in range(n)]          # refused chunks between accepted ones
     caps = [c.cap for c in part]
-    res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
-    _check(part, 0, res, out, ooff, caps)
+    res, out, ooff = Z.device_call(e, N, [c.stream for c in part], caps)
+    Z.check_batch(part, 0, res, out, ooff, caps)
 
 
 def test_slot_budget_of_three_slots_over_ten_streams(eng):
@@ -112,11 +64,11 @@ def test_slot_budget_of_three_slots_over_ten_streams(eng):
     slot = 131072 + 32
     prev = N.lib().cj_debug_zstd_slot_budget(3 * slot)
     try:
-        res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
+        res, out, ooff = Z.device_call(e, N, [c.stream for c in part], caps)
     finally:
         assert N.lib().cj_debug_zstd_slot_budget(prev) == 3 * slot
-    _check(part, 0, res, out, ooff, caps)
-    res2, out2, _ = _device_call(e, N, [c.stream for c in part], caps)
+    Z.check_batch(part, 0, res, out, ooff, caps)
+    res2, out2, _ = Z.device_call(e, N, [c.stream for c in part], caps)
     assert list(res2) == list(res) and (out2 == out).all()
 
 
@@ -129,14 +81,14 @@ def test_five_frames_at_a_budget_below_one_slot(eng):
     part = sorted((c for c in _shuffled() if c.accepted and not c.name.startswith("mut_")), key=lambda c: (abs(c.cap - 70000), c.name))[:5]
     assert all(60000 < c.cap < 140000 for c in part)
     caps = [c.cap for c in part]
-    res0, out0, _ = _device_call(e, N, [c.stream for c in part], caps)
+    res0, out0, _ = Z.device_call(e, N, [c.stream for c in part], caps)
     assert L.cj_debug_zstd_slot_budget(1) == default                  # (the setter returns the previous value)
     try:
-        res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
+        res, out, ooff = Z.device_call(e, N, [c.stream for c in part], caps)
     finally:
         assert L.cj_debug_zstd_slot_budget(0) == 1                    # 0: back to the default
     assert L.cj_debug_zstd_slot_budget(0) == default
-    _check(part, 0, res, out, ooff, caps)
+    Z.check_batch(part, 0, res, out, ooff, caps)
     assert list(res) == list(res0) and (out == out0).all()
 
 
@@ -145,7 +97,7 @@ def test_size_query_then_the_public_calls(eng):
     from cramjam_amd import batch
     cs = _shuffled()
     chunks = [c.stream for c in cs]
-    sizes, _, _ = _device_call(e, N, chunks, [0] * len(cs), sizes=True)
+    sizes, _, _ = Z.device_call(e, N, chunks, [0] * len(cs), sizes=True)
     assert batch.zstd_sizes(chunks) == [int(s) for s in sizes]
     for c, q in zip(cs, sizes):
         d = c.verdicts[1]
@@ -170,6 +122,4 @@ def test_size_query_then_the_public_calls(eng):
 
 def test_device_entries_on_torch_tensors_on_a_side_stream():
     """the device-resident calls on torch tensors with sync=False, in a child that imports torch BEFORE cramjam_amd"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "zstd_torch_child.py")], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "zstd: ok" in r.stdout, (r.stdout[-2500:], r.stderr[-3000:])
+    DB.run_child(os.path.join(ROOT, "tests", "zstd_torch_child.py"), "zstd: ok", 600)

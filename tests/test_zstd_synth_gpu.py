@@ -13,7 +13,7 @@ import pytest
 import zstd_cases as Z
 import zstd_synth as S
 from conftest import ROOT
-from test_zstd_gpu import _check, _device_call, eng  # noqa: F401  (eng: the module's engine fixture)
+from test_zstd_gpu import eng  # noqa: F401  (the module's engine fixture)
 
 pytestmark = pytest.mark.gpu
 _cache = []
@@ -52,8 +52,8 @@ def test_all_cases_and_flips_in_one_batch_at_four_capacities(eng, which):
     e, N = eng
     cs = _cases()
     caps = [Z.capacities(c.cap)[which] for c in cs]
-    res, out, ooff = _device_call(e, N, [c.stream for c in cs], caps)
-    _check(cs, which, res, out, ooff, caps, S.digest)
+    res, out, ooff = Z.device_call(e, N, [c.stream for c in cs], caps)
+    Z.check_batch(cs, which, res, out, ooff, caps, S.digest)
 
 
 def test_host_entry_and_size_query():
@@ -87,8 +87,8 @@ def test_batches_that_leave_wavefronts_idle(eng, n):
     for start in (0, 7, 100, 333):
         part = small[start:start + n]
         caps = [c.cap for c in part]
-        res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
-        _check(part, 0, res, out, ooff, caps, S.digest)
+        res, out, ooff = Z.device_call(e, N, [c.stream for c in part], caps)
+        Z.check_batch(part, 0, res, out, ooff, caps, S.digest)
 
 
 def test_slot_budget_of_three_slots_over_ten_huffman_cases(eng):
@@ -100,7 +100,7 @@ def test_slot_budget_of_three_slots_over_ten_huffman_cases(eng):
     slot = 131072 + 32
     prev = N.lib().cj_debug_zstd_slot_budget(3 * slot)
     try:
-        res, out, ooff = _device_call(e, N, [c.stream for c in part], caps)
+        res, out, ooff = Z.device_call(e, N, [c.stream for c in part], caps)
     finally:
         assert N.lib().cj_debug_zstd_slot_budget(prev) == 3 * slot
-    _check(part, 0, res, out, ooff, caps, S.digest)
+    Z.check_batch(part, 0, res, out, ooff, caps, S.digest)

@@ -682,3 +682,29 @@ def load_cases():
 
 def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
+
+
+def device_call(e, N, chunks, caps, sizes=False):
+    """cj_zstd_batch_device (sizes: cj_zstd_batch_sizes_device) in the harness's guarded run (tests/device_batch.py): chunks at every
+    misalignment, 64 guard bytes around every slot, the output filled with 0xA5 first: (results, output, offsets)"""
+    import device_batch as DB
+    n, L = len(chunks), N.lib()
+    if sizes:
+        call = lambda i, o, l, out, oo, oc, r: N.check(L.cj_zstd_batch_sizes_device(e.h, N.ZSTD_FRAMES, 0, n, i, o, l, r, None))
+    else:
+        call = lambda i, o, l, out, oo, oc, r: N.check(L.cj_zstd_batch_device(e.h, N.ZSTD_FRAMES, N.OP_DECOMPRESS, 0, n, i, o, l, out, oo, oc, r, None))
+    return DB.run_chunks(e, call, chunks, caps)
+
+
+def check_batch(part, which, res, out, ooff, caps, digest=sha):
+    """every chunk of a device_call against verdict `which`: the result, both guards, [result, cap) untouched, at the exact capacity the bytes' digest"""
+    from device_batch import G
+    for i, c in enumerate(part):
+        want = c.verdicts[which]
+        assert res[i] == want, (c.name, caps[i], int(res[i]), want)
+        lo, cap = ooff[i], int(caps[i])
+        assert (out[lo - G:lo] == 0xA5).all() and (out[lo + cap:lo + cap + G] == 0xA5).all(), c.name
+        if want >= 0:
+            assert (out[lo + want:lo + cap] == 0xA5).all(), c.name        # bytes between the result and the capacity stay untouched
+            if which == 0:
+                assert digest(out[lo:lo + want]) == c.sha, c.name
