@@ -1,5 +1,5 @@
 // deflate_wave.hpp — the DEFLATE decoder of one wavefront (RFC 1951 behind no wrapper, RFC 1950 zlib or RFC 1952 gzip): one stream per
-// wavefront, accept / reject rules of zlib's inflate.  Written like lz4_dict_wave.hpp: it names only
+// wavefront, accept / reject rules of zlib's inflate.  Written like lz4_wave.hpp: it names only
 //     InWindow, wave_copy, wave_match_copy, wave_order, CJ_LANES, lds_ld, lds_ld8, lds_add, lds_xor, out_ld8, LaneBytes
 // of the wave-decoder contract: wave_lanes.hpp + cj_common.hpp implement it for the device,
 // tests/hostsim/sim_wave.hpp, with every access bounds-checked, for the host (sim_deflate_decode.cpp), where

@@ -8,80 +8,13 @@
 // Shape: the sequence grammar is parsed wave-uniformly on the scalar unit out of a 512-byte register
 // window (v_readlane), the vector lanes only move bytes: literals HBM->HBM, matches from the
 // chunk's own freshly written output (same-wave L1-coherent), byte per lane, 16 B/lane on long runs.
+// The decoder itself is lz4_wave.hpp (lz4_wave_decode<false>: the text the host build runs too); here are its two kernels.
+#include "cj_engine.hpp"
 #include "lz4_lane_walk.hpp"
 #include "snappy_records.hpp"
+#include "lz4_wave.hpp"
 
 namespace cj {
-
-// Decode one block (wave-uniform arguments).  hist: bytes of valid output directly before `out` that matches may reach
-// into (0 for an independent block; min(position, 64 KiB) for a linked LZ4-frame block).  Returns the decoded size or
-// CJ_E_CORRUPT.
-__device__ __forceinline__ int64_t lz4_wave_decode(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t hist) {
-    if (cap == 0) return (n == 1 && in[0] == 0) ? 0 : (int64_t)CJ_E_CORRUPT;
-    if (n == 0) return CJ_E_CORRUPT;
-
-    InWindow w;
-    const uint32_t mis = window_open(w, in, n);
-    const uint32_t iend = w.iend;
-    uint32_t ip = mis;      // input position relative to w.base
-    uint32_t op = 0;        // output position
-    bool bad = false;
-
-    for (;;) {
-        w.ensure(ip);
-        const uint32_t t4 = w.fetch32(ip);
-        const uint32_t token = t4 & 0xffu;
-        ip += 1;
-        uint64_t lit = token >> 4;
-        if (lit == 15u) {
-            // variable-length literal count: bytes may not reach into the last 15 input bytes
-            if (ip + 15u >= iend) { bad = true; break; }
-            uint32_t b = (t4 >> 8) & 0xffu;
-            ip += 1; lit += b;
-            if (ip + 15u > iend) { bad = true; break; }
-            while (b == 255u) {
-                b = w.fetch32_any(ip) & 0xffu;
-                ip += 1; lit += b;
-                if (ip + 15u > iend) { bad = true; break; }
-            }
-            if (bad) break;
-        }
-        const uint32_t rem_out = cap - op, rem_in = iend - ip;
-        if ((uint64_t)rem_out < lit + 12u || (uint64_t)rem_in < lit + 8u) {
-            // must be the final sequence: consumes the input exactly, fits the output
-            if (rem_in != lit || rem_out < lit) { bad = true; break; }
-            wave_copy(out + op, w.base + ip, (uint32_t)lit);
-            op += (uint32_t)lit;
-            break;
-        }
-        wave_copy(out + op, w.base + ip, (uint32_t)lit);
-        ip += (uint32_t)lit; op += (uint32_t)lit;
-
-        const uint32_t o4 = w.fetch32_any(ip);
-        const uint32_t offset = o4 & 0xffffu;
-        ip += 2;
-        uint64_t mlen = token & 15u;
-        if (mlen == 15u) {
-            uint32_t b = (o4 >> 16) & 0xffu;
-            ip += 1; mlen += b;
-            if (ip + 4u > iend) { bad = true; break; }
-            while (b == 255u) {
-                b = w.fetch32_any(ip) & 0xffu;
-                ip += 1; mlen += b;
-                if (ip + 4u > iend) { bad = true; break; }
-            }
-            if (bad) break;
-        }
-        mlen += 4u;
-        if (offset == 0u || (uint64_t)offset > (uint64_t)op + hist) { bad = true; break; }
-        if ((uint64_t)(cap - op) < mlen + 5u) { bad = true; break; }   // last 5 bytes are literals
-        wave_order();
-        wave_match_copy(out + op, offset, (uint32_t)mlen);
-        wave_order();
-        op += (uint32_t)mlen;
-    }
-    return bad ? (int64_t)CJ_E_CORRUPT : (int64_t)op;
-}
 
 // route: nullptr = decode every chunk; else only chunks the parse stage flagged kRouteWave.
 __global__ __launch_bounds__(kBlockThreads) void lz4_decode_kernel(BatchArgs a, const ParseMeta* route) {
@@ -94,6 +27,7 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_decode_kernel(BatchArgs a, 
     uint64_t cap64 = a.out_cap[chunk];
     int64_t status = 0;
 
+    // (lz4_block_prologue's rules, lz4_lane_walk.hpp, written out: DESIGN.md §5.10a)
     if (a.flags & CJ_FLAG_LZ4_SIZE_PREFIX) {
         // lz4 crate decompress_to_buffer(src, None, buffer): u32-LE size prefix (reference src/lz4.rs:90,164)
         if (n64 < 4) { status = CJ_E_NO_PREFIX; }
@@ -113,7 +47,7 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_decode_kernel(BatchArgs a, 
     if (status == 0 && n64 > 0x7FFFFFF0ull) status = CJ_E_CORRUPT;
     if (status != 0) { if (lane_id() == 0) a.result[chunk] = status; return; }
 
-    const int64_t r = lz4_wave_decode(in, (uint32_t)n64, out, (uint32_t)cap64, 0u);
+    const int64_t r = lz4_wave_decode<false>(in, (uint32_t)n64, out, (uint32_t)cap64, nullptr, 0u);
     if (lane_id() == 0) a.result[chunk] = r;
 }
 
@@ -143,7 +77,7 @@ __global__ __launch_bounds__(64) void lz4_frame_chain_kernel(const uint8_t* in, 
             else { wave_copy(out + pos, src, sz); r = (int64_t)sz; }
         } else {
             const uint32_t cap = room < block_max ? (uint32_t)room : block_max;
-            r = lz4_wave_decode(src, sz, out + pos, cap, pos < 65536u ? (uint32_t)pos : 65536u);
+            r = lz4_wave_decode<false>(src, sz, out + pos, cap, nullptr, pos < 65536u ? (uint32_t)pos : 65536u);
         }
         if (lane_id() == 0) result[k] = r;
         if (r < 0) {
@@ -170,14 +104,12 @@ void launch_lz4_frame_chains(const uint8_t* in, const uint64_t* blk_off, const u
 
 void launch_lz4_decode(const BatchArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return;
-    dim3 grid((a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlockThreads);
-    hipLaunchKernelGGL(lz4_decode_kernel, grid, block, 0, s, a, (const ParseMeta*)nullptr);
+    hipLaunchKernelGGL(lz4_decode_kernel, wave_grid(a.n_chunks), dim3(kBlockThreads), 0, s, a, (const ParseMeta*)nullptr);
 }
 
 void launch_lz4_decode_routed(const BatchArgs& a, const void* meta, hipStream_t s) {
     if (a.n_chunks == 0) return;
-    dim3 grid((a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlockThreads);
-    hipLaunchKernelGGL(lz4_decode_kernel, grid, block, 0, s, a, (const ParseMeta*)meta);
+    hipLaunchKernelGGL(lz4_decode_kernel, wave_grid(a.n_chunks), dim3(kBlockThreads), 0, s, a, (const ParseMeta*)meta);
 }
 
 

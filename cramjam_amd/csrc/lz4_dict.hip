@@ -1,8 +1,8 @@
 // lz4_dict.hip — batches of LZ4 blocks against ONE dictionary shared by every chunk of the call (cj_dict_batch_device / _host,
 // cj_dict_batch_sizes_device / _host): what LZ4_loadDict + LZ4_compress_fast_continue write and
 // LZ4_decompress_safe_usingDict reads.  Only the last 65 536 bytes of the dictionary count; a dictionary of length 0 is the plain call.
-//   decompress   one wavefront per chunk, lz4_dict_wave.hpp: lz4_wave_decode's grammar, a match that begins before the block's start
-//                copies that part from the dictionary in global memory (at most 64 KiB, read by every wavefront: it lives in L2)
+//   decompress   one wavefront per chunk, lz4_wave.hpp's lz4_wave_decode<true>: the plain decoder's text, a match that begins before the
+//                block's start copies that part from the dictionary in global memory (at most 64 KiB, read by every wavefront: it lives in L2)
 //   sizes        the size walk (lz4_size_walk.hpp) with the dictionary's length, one wavefront per chunk through the register window
 //   compress     chunks of at most 65 536 bytes: `dictionary tail | chunk` staged contiguously per chunk in the engine's scratch, in
 //                slices within a fixed budget, then the linked-block encoder (lz4_encode.hip, kFlagLinkedEnc) with hist[i] = the tail's
@@ -11,7 +11,7 @@
 #include "cj_stage.hpp"
 #include "lz4_lane_walk.hpp"
 #include "lz4_size_walk.hpp"
-#include "lz4_dict_wave.hpp"
+#include "lz4_wave.hpp"
 
 
 namespace cj {
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(kBlockThreads) void lz4_dict_decode_kernel(BatchArg
     uint64_t cap64 = a.out_cap[chunk];
     const int64_t status = lz4_block_prologue(a.flags, in, n64, cap64);
     if (status != 0) { if (lane_id() == 0) a.result[chunk] = status; return; }
-    const int64_t r = lz4_dict_wave_decode(in, (uint32_t)n64, out, (uint32_t)cap64, dict_end, hist);
+    const int64_t r = lz4_wave_decode<true>(in, (uint32_t)n64, out, (uint32_t)cap64, dict_end, hist);
     if (lane_id() == 0) a.result[chunk] = r;
 }
 

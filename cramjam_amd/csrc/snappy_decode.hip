@@ -6,10 +6,12 @@
 // and one "corrupt" class for Literal/CopyRead/CopyWrite/Offset/HeaderMismatch.
 //
 // Same shape as lz4_decode.hip: tag grammar parsed wave-uniformly from the 512-byte register window,
-// lanes move bytes.
+// lanes move bytes.  The wavefront decoder itself is snappy_wave.hpp (the text the host build runs too).
+#include "cj_engine.hpp"
 #include "lz4_lane_walk.hpp"   // lane_copy / lane_match / ParseMeta route flags are codec independent
 #include "lane_stream.hpp"
 #include "snappy_records.hpp"
+#include "snappy_wave.hpp"
 
 namespace cj {
 
@@ -19,99 +21,13 @@ __global__ __launch_bounds__(kBlockThreads) void snappy_decode_kernel(BatchArgs 
     if (chunk >= a.n_chunks) return;
     if (route != nullptr && (route[chunk].in_skip & kRouteWave) == 0u) return;
     const uint8_t* in = a.in_base + a.in_off[chunk];
-    const uint64_t n64 = a.in_len[chunk];
-    uint8_t* out = a.out_base + a.out_off[chunk];
-    const uint64_t cap64 = a.out_cap[chunk];
-    int64_t status = 0;
-
-    if (n64 == 0) status = CJ_E_SNAPPY_EMPTY;
-    else if (n64 > 0xFFFFFFF0ull) status = CJ_E_SNAPPY_CORRUPT;
-    if (status != 0) { if (lane_id() == 0) a.result[chunk] = status; return; }
-
-    InWindow w;
-    const uint32_t mis = window_open(w, in, (uint32_t)n64);
-    const uint32_t iend = w.iend;
-    uint32_t ip = mis;
-
-    // preamble: snap bytes::read_varu64 (up to 10 bytes), then the u32 range check
-    uint64_t ulen = 0;
-    {
-        uint32_t shift = 0, i = 0;
-        bool done = false;
-        while (ip < iend && i < 10u) {
-            uint32_t b = w.fetch32_any(ip) & 0xffu;
-            ip += 1;
-            if (b < 0x80u) {
-                if (i == 9u && b > 1u) break;
-                ulen |= (uint64_t)b << shift;
-                done = true;
-                break;
-            }
-            ulen |= (uint64_t)(b & 0x7fu) << shift;
-            shift += 7; i += 1;
-        }
-        if (!done) status = CJ_E_SNAPPY_HEADER;
-        else if (ulen > 0xFFFFFFFFull) status = CJ_E_SNAPPY_TOO_BIG;
-        else if (ulen > cap64) status = CJ_E_SNAPPY_BUF_SMALL;
-    }
-    if (status != 0) { if (lane_id() == 0) a.result[chunk] = status; return; }
-
-    const uint32_t dn = (uint32_t)ulen;
-    uint32_t op = 0;
-    bool bad = false;
-
-    while (ip < iend) {
-        w.ensure(ip);
-        const uint32_t t4 = w.fetch32(ip);
-        const uint32_t tag = t4 & 0xffu;
-        ip += 1;
-        const uint32_t kind = tag & 3u;
-        if (kind == 0u) {
-            uint64_t len = (tag >> 2) + 1u;
-            if (len > 60u) {
-                const uint32_t nb = (uint32_t)len - 60u;        // 1..4 length bytes
-                if (iend - ip < nb) { bad = true; break; }
-                uint32_t v = w.fetch32_any(ip);
-                if (nb < 4u) v &= (1u << (8u * nb)) - 1u;
-                ip += nb;
-                len = (uint64_t)v + 1u;
-            }
-            if (len > (uint64_t)(iend - ip) || len > (uint64_t)(dn - op)) { bad = true; break; }
-            wave_copy(out + op, w.base + ip, (uint32_t)len);
-            ip += (uint32_t)len; op += (uint32_t)len;
-            continue;
-        }
-        uint32_t len, offset;
-        if (kind == 1u) {
-            if (iend - ip < 1u) { bad = true; break; }
-            len = 4u + ((tag >> 2) & 7u);
-            offset = ((tag >> 5) << 8) | ((t4 >> 8) & 0xffu);
-            ip += 1;
-        } else if (kind == 2u) {
-            if (iend - ip < 2u) { bad = true; break; }
-            len = 1u + (tag >> 2);
-            offset = (t4 >> 8) & 0xffffu;
-            ip += 2;
-        } else {
-            if (iend - ip < 4u) { bad = true; break; }
-            len = 1u + (tag >> 2);
-            offset = w.fetch32_any(ip);
-            ip += 4;
-        }
-        if (offset == 0u || offset > op) { bad = true; break; }
-        if (len > dn - op) { bad = true; break; }
-        wave_order();
-        wave_match_copy(out + op, offset, len);
-        wave_order();
-        op += len;
-    }
-    if (!bad && op != dn) bad = true;
-    if (lane_id() == 0) a.result[chunk] = bad ? (int64_t)CJ_E_SNAPPY_CORRUPT : (int64_t)dn;
+    const int64_t r = snappy_wave_decode(in, a.in_len[chunk], a.out_base + a.out_off[chunk], a.out_cap[chunk]);
+    if (lane_id() == 0) a.result[chunk] = r;
 }
 
 // ---------------------------------------------------------------------------------------------------
 // One LANE per chunk (large batches of short-element data; see lz4_decode_lanes.hip for the rationale).
-// Same accept/reject rules as the wave kernel above (snap 1.1.1 raw::Decoder::decompress).  Copies are
+// Same accept/reject rules as the wave decoder (snappy_wave.hpp) (snap 1.1.1 raw::Decoder::decompress).  Copies are
 // 16 B wild copies while 16 B of room remain before the DECODED length, exact bytes at the tail, so nothing
 // past the decoded length is written.
 // ---------------------------------------------------------------------------------------------------
@@ -196,8 +112,7 @@ __global__ __launch_bounds__(64) void snappy_decode_lanes_kernel(BatchArgs a) {
 
 void launch_snappy_decode(const BatchArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return;
-    dim3 grid((a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlockThreads);
-    hipLaunchKernelGGL(snappy_decode_kernel, grid, block, 0, s, a, (const ParseMeta*)nullptr);
+    hipLaunchKernelGGL(snappy_decode_kernel, wave_grid(a.n_chunks), dim3(kBlockThreads), 0, s, a, (const ParseMeta*)nullptr);
 }
 
 
@@ -376,8 +291,7 @@ void launch_snappy_parse(const BatchArgs& a, void* sync, void* meta, hipStream_t
 
 void launch_snappy_decode_routed(const BatchArgs& a, const void* meta, hipStream_t s) {
     if (a.n_chunks == 0) return;
-    dim3 grid((a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlockThreads);
-    hipLaunchKernelGGL(snappy_decode_kernel, grid, block, 0, s, a, (const ParseMeta*)meta);
+    hipLaunchKernelGGL(snappy_decode_kernel, wave_grid(a.n_chunks), dim3(kBlockThreads), 0, s, a, (const ParseMeta*)meta);
 }
 
 }  // namespace cj

@@ -1,5 +1,5 @@
 """LZ4 blocks written against a shared dictionary (LZ4_loadDict + LZ4_compress_fast_continue, read by LZ4_decompress_safe_usingDict):
-the Python model of the decode rules and of the size walk that cramjam_amd/csrc/lz4_dict_wave.hpp and lz4_size_walk.hpp implement,
+the Python model of the decode rules and of the size walk that cramjam_amd/csrc/lz4_wave.hpp (kDict = true) and lz4_size_walk.hpp implement,
 the seeded inputs of the fixtures, the hand-written edge streams, and the loader of tests/golden/golden_dict.json / .bin (minted by
 tests/golden/make_golden_dict.py from the system liblz4).  No GPU, no liblz4 needed to import it."""
 import ctypes as C

@@ -1,11 +1,11 @@
 """The input sweep on the CPU (tests/input_cases.py): the builder is deterministic and its streams mean what was meant; the shares that
 keep the sweep honest — how many cuts are accepted, which offsets are refused and why —, asserted from the oracle alone; and the host
-builds of the kernels' own code (tests/hostsim: the lane walker, the dictionary wavefront) on every LZ4 case that applies to them, with
-the oracle's result and bytes, the slot's surroundings untouched and no access outside the registered ranges — for the cuts of family A
+builds of the kernels' own code (tests/hostsim: the lane walker, the LZ4 wavefront decoder plain, linked and with a dictionary, the Snappy
+wavefront decoder) on every case that applies to them, with the oracle's result and bytes, the slot's surroundings untouched and no access outside the registered ranges — for the cuts of family A
 that includes every read behind in_len.
 
-The dictionary wavefront is loaded into this process without a sanitizer: its accessors (tests/hostsim/sim_wave.hpp) check every access
-and report SIM_BOUNDS.  The lane walker has no accessors of its own: it is built as a stand-alone program under
+The wavefront decoders are loaded into this process without a sanitizer: their accessors (tests/hostsim/sim_wave.hpp) check every access
+and report SIM_BOUNDS; as stand-alone programs they run the same cases under -fsanitize=address,undefined.  The lane walker has no accessors of its own: it is built as a stand-alone program under
 -fsanitize=address,undefined and run on a cases file in which every stream and every output slot is a heap block of exactly its size."""
 import ctypes as C
 import os
@@ -187,29 +187,98 @@ def _lz4_small_cases():
     return out + [c for w in WINDOWS for c in I.c_lz4_cases(w)]
 
 
-def test_dictionary_wavefront_host_build_on_every_lz4_case():
-    """lz4_dict_wave.hpp over sim_wave.hpp's checked accessors: without a dictionary (the plain call) on A, B and C, with one on B's and
-    C's dictionary cases.  The stream is registered as [0, in_len): a read of `after` is SIM_BOUNDS."""
+G = 64
+
+
+def _held(call, cases, hist=b""):
+    """every case through call(in, n, out, cap) at misalignment n % 4, the stream registered as [0, in_len) (a read of `after` is
+    SIM_BOUNDS): the case's result and bytes, 64 bytes of 0xA5 on both sides and [result, cap) untouched (hist: bytes that lie directly
+    in front of the output in place of the guard, and are unchanged afterwards); returns the number of runs"""
+    front = np.frombuffer(hist, np.uint8) if hist else np.full(G, 0xA5, np.uint8)
+    for n, c in enumerate(cases):
+        mis = n % 4
+        src = b"\0" * mis + c["bytes"] + c.get("after", b"")
+        buf = C.create_string_buffer(src, len(src) + 1)
+        out = np.full(len(front) + c["cap"] + G, 0xA5, np.uint8)
+        out[:len(front)] = front
+        r = call(C.addressof(buf) + mis, len(c["bytes"]), out.ctypes.data + len(front), c["cap"])
+        tag = (c["stream"], c.get("in_len"), c.get("kind"), c.get("off"), c.get("form"), c["cap"], r, c["result"])
+        assert r != SIM_BOUNDS, tag
+        assert r == c["result"] and (r <= 0 or out[len(front):len(front) + r].tobytes() == c["out"]), tag
+        keep = max(r, 0) if r >= 0 else c["cap"]
+        assert (out[:len(front)] == front).all() and (out[len(front) + keep:] == 0xA5).all(), tag
+    return len(cases)
+
+
+def _dict_cases():
+    return [c for b in K.LZ4_BODIES[:2] for c in I.b_dict_cases(b)] + I.c_dict_cases()
+
+
+def test_lz4_wavefront_host_build_on_every_lz4_case():
+    """lz4_wave.hpp over sim_wave.hpp's checked accessors: lz4_wave_decode<false>, the text of lz4_decode_kernel, with hist = 0 on A, B
+    and C; lz4_wave_decode<true>, lz4_dict_decode_kernel's, on B's and C's dictionary cases"""
     from test_lz4_dict_model import sim_lib
     L = sim_lib()
-    G = 64
     d = D.dictionary(I.DICT_LEN)
     dbuf = C.create_string_buffer(d, len(d))
-    runs = 0
-    for cases, dl in ((_lz4_small_cases(), 0), ([c for b in K.LZ4_BODIES[:2] for c in I.b_dict_cases(b)] + I.c_dict_cases(), len(d))):
-        for n, c in enumerate(cases):
-            mis = n % 4
-            src = b"\0" * mis + c["bytes"] + c.get("after", b"")
-            buf = C.create_string_buffer(src, len(src) + 1)
-            out = np.full(c["cap"] + 2 * G, 0xA5, np.uint8)
-            r = L.sim_lz4_dict_decode(C.addressof(buf) + mis, len(c["bytes"]), out.ctypes.data + G, c["cap"], C.addressof(dbuf), dl)
-            tag = (c["stream"], c.get("in_len"), c.get("kind"), c.get("off"), c["cap"], r, c["result"])
-            assert r != SIM_BOUNDS, tag
-            assert r == c["result"] and (r <= 0 or out[G:G + r].tobytes() == c["out"]), tag
-            keep = max(r, 0) if r >= 0 else c["cap"]
-            assert (out[:G] == 0xA5).all() and (out[G + keep:] == 0xA5).all(), tag
-            runs += 1
-    assert runs > 14000
+    plain = _lz4_small_cases()
+    runs = _held(lambda p, n, out, cap: L.sim_lz4_wave_decode(p, n, out, cap, 0), plain)
+    runs += _held(lambda p, n, out, cap: L.sim_lz4_dict_decode(p, n, out, cap, C.addressof(dbuf), len(d)), _dict_cases())
+    assert runs == len(plain) + len(_dict_cases()) and runs > 14000
+
+
+def test_lz4_wavefront_host_build_in_the_linked_form():
+    """lz4_frame_chain_kernel's call shape: lz4_wave_decode<false> with the dictionary's bytes directly in front of the output and
+    hist = DICT_LEN gives every dictionary case its own result and bytes, and leaves the history as it was"""
+    from test_lz4_dict_model import sim_lib
+    L = sim_lib()
+    d = D.dictionary(I.DICT_LEN)
+    assert len(d) == I.DICT_LEN == 4096
+    cases = _dict_cases()
+    assert _held(lambda p, n, out, cap: L.sim_lz4_wave_decode(p, n, out, cap, len(d)), cases, hist=d) == len(cases) > 0
+
+
+def snappy_sim_lib():
+    L = C.CDLL(build_sim("sim_snappy_wave.cpp", os.path.join(SIM_DIR, "libsim_snappy_wave.so")))
+    L.sim_snappy_wave_decode.restype = C.c_longlong
+    L.sim_snappy_wave_decode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint]
+    return L
+
+
+def _snappy_cases():
+    """every Snappy case of A, B and C that a chunk-sized decoder takes, and the preamble's forms"""
+    out = [c for b in K.SNAPPY_BODIES for c in I.a_snappy_cases(b)] + [c for b in K.SNAPPY_BODIES for c in I.b_snappy_cases(b)]
+    return out + [c for w in WINDOWS for c in I.c_snappy_cases(w)] + I.b_preamble_cases()
+
+
+def test_snappy_wavefront_host_build_on_every_snappy_case():
+    """snappy_wave.hpp, the text of snappy_decode_kernel, over sim_wave.hpp's checked accessors: the cuts, the offset edges in every copy
+    form, the overlap grid of the three windows and the preamble's forms, held as the GPU sweep holds the wave mode"""
+    L = snappy_sim_lib()
+    cases = _snappy_cases()
+    assert _held(L.sim_snappy_wave_decode, cases) == len(cases) > 3000
+
+
+def _ten_byte_preambles():
+    """the declared length in ten bytes whose last one is above 1 (bits that a u64 does not have: snap's Header error), in front of the
+    preamble cases' element stream; the oracle decides"""
+    c = next(c for c in I.b_preamble_cases() if c["form"] == "elements-alone")
+    head = bytes(((c["U"] >> (7 * i)) & 127) | 128 for i in range(9))
+    out = [dict(c, form="10-bytes-last-%d" % last, bytes=head + bytes([last]) + c["bytes"]) for last in (2, 3, 0x7F)]
+    for x in out:
+        x["result"], x["out"] = oracle.snappy_decompress(x["bytes"], x["cap"])
+        x["result"] = int(x["result"])
+    return out
+
+
+def test_snappy_wavefront_host_build_on_the_capacity_sweep_and_ten_byte_preambles():
+    """two rules that the input sweep's cases do not reach: a copy that would pass the declared length, where the declared length is the
+    capacity (tests/capacity_cases.py: a write behind it is SIM_BOUNDS), and the tenth preamble byte above 1"""
+    L = snappy_sim_lib()
+    ten = _ten_byte_preambles()
+    assert all(c["result"] < 0 for c in ten) and len({c["result"] for c in ten}) == 1
+    cases = [c for b in K.SNAPPY_BODIES for c in K.snappy_cases(b)] + ten
+    assert _held(L.sim_snappy_wave_decode, cases) == len(cases)
 
 
 def write_lane_cases(path, cases):
@@ -232,3 +301,30 @@ def test_lane_walker_stand_alone_under_sanitizers_on_every_lz4_case(tmp_path):
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "%d cases, 0 bad" % len(cases) in r.stdout
+
+
+def _run_cases_file(tmp_path, source, recs):
+    exe = build_sim(source, str(tmp_path / "sim_main"), main=True, sanitize=True)
+    path = str(tmp_path / "cases.bin")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(recs)) + b"".join(recs))
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "%d cases, 0 bad" % len(recs) in r.stdout
+
+
+def test_lz4_wavefront_stand_alone_under_sanitizers(tmp_path):
+    """tests/hostsim/sim_lz4_wave.cpp as a program of its own (SIM_MAIN) under AddressSanitizer and UBSan, every block a heap block of
+    exactly its size: the plain entry on every LZ4 case, the linked entry (the dictionary as history in front of the output) and the
+    dictionary entry on every dictionary case"""
+    d = D.dictionary(I.DICT_LEN)
+    rec = lambda n, c, dl, linked: struct.pack("<6Iq", len(c["bytes"]), c["cap"], dl, n % 4, 3, linked, c["result"]) + c["bytes"] + d[:dl] + c["out"]
+    recs = [rec(n, c, 0, 1) for n, c in enumerate(_lz4_small_cases())]
+    recs += [rec(n, c, len(d), linked) for linked in (1, 0) for n, c in enumerate(_dict_cases())]
+    _run_cases_file(tmp_path, "sim_lz4_wave.cpp", recs)
+
+
+def test_snappy_wavefront_stand_alone_under_sanitizers(tmp_path):
+    """tests/hostsim/sim_snappy_wave.cpp likewise, on every Snappy case"""
+    recs = [struct.pack("<3Iq", len(c["bytes"]), c["cap"], n % 4, c["result"]) + c["bytes"] + c["out"] for n, c in enumerate(_snappy_cases())]
+    _run_cases_file(tmp_path, "sim_snappy_wave.cpp", recs)

@@ -1,5 +1,5 @@
 """LZ4 blocks against a shared dictionary on the CPU: the model (tests/lz4_dict_model.py) against the fixtures the system liblz4
-minted and, where it loads, against LZ4_decompress_safe_usingDict itself; the kernel's own decoder (cramjam_amd/csrc/lz4_dict_wave.hpp)
+minted and, where it loads, against LZ4_decompress_safe_usingDict itself; the kernel's own decoder (cramjam_amd/csrc/lz4_wave.hpp, kDict = true)
 compiled for the host with bounds-checked copies; the encoder's model with the dictionary as its history; the argument checks that
 need no device.  No GPU."""
 import ctypes as C
@@ -111,14 +111,17 @@ def test_model_agrees_with_liblz4_on_the_fly():
 
 
 def sim_lib():
-    L = C.CDLL(build_sim("sim_lz4_dict_decode.cpp", os.path.join(SIM_DIR, "libsim_lz4_dict_decode.so")))
+    """tests/hostsim/sim_lz4_wave.cpp: lz4_wave_decode<true> (sim_lz4_dict_decode) and <false> (sim_lz4_wave_decode)"""
+    L = C.CDLL(build_sim("sim_lz4_wave.cpp", os.path.join(SIM_DIR, "libsim_lz4_wave.so")))
     L.sim_lz4_dict_decode.restype = C.c_longlong
     L.sim_lz4_dict_decode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint]
+    L.sim_lz4_wave_decode.restype = C.c_longlong
+    L.sim_lz4_wave_decode.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_uint]
     return L
 
 
 def test_kernels_block_decoder_on_the_host_agrees_with_the_model():
-    """cramjam_amd/csrc/lz4_dict_wave.hpp, the function the kernel runs, compiled for the host (tests/hostsim/sim_lz4_dict_decode.cpp:
+    """cramjam_amd/csrc/lz4_wave.hpp's lz4_wave_decode<true>, the function the kernel runs, compiled for the host (tests/hostsim/sim_lz4_wave.cpp:
     every copy bounds-checked, a violation is SIM_BOUNDS): every fixture stream at input alignments 0, 1 and 3 and dictionary alignments 0 and
     5 gives the model's verdict and bytes"""
     L = sim_lib()

@@ -67,7 +67,8 @@ def sims(tmp_path_factory):
     """every sim with the device-load mode on (and off again behind the module: tests/deflate_cases.py shares its library)"""
     import test_lz4_dict_model as TD
     d = tmp_path_factory.mktemp("neighbours")
-    S = {"deflate": DF.sim_lib(), "lz4_dict": TD.sim_lib()}
+    import test_input_sweep_model as TI
+    S = {"deflate": DF.sim_lib(), "lz4_dict": TD.sim_lib(), "snappy": TI.snappy_sim_lib()}      # (lz4_dict: sim_lz4_wave.cpp, both entries)
     for name in ("zstd", "blosclz"):
         S[name] = C.CDLL(build_sim("sim_%s_decode.cpp" % name, str(d / ("libsim_%s.so" % name))))
     S["zstd"].sim_zstd_decode.restype = C.c_longlong
@@ -77,7 +78,7 @@ def sims(tmp_path_factory):
     S["bgzf"] = C.CDLL(build_sim("sim_bgzf_grammar.cpp", str(d / "libsim_bgzf.so")))
     S["bgzf"].sim_bgzf_walk.restype = C.c_longlong
     S["bgzf"].sim_bgzf_walk.argtypes = [C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.POINTER(C.c_ulonglong)]
-    wave = [S[k] for k in ("deflate", "lz4_dict", "zstd", "blosclz")]
+    wave = [S[k] for k in ("deflate", "lz4_dict", "snappy", "zstd", "blosclz")]
     for L in wave:
         L.sim_set_device_loads(1)
     yield S
@@ -100,11 +101,11 @@ def _sanitized(tmp_path, source, recs):
     assert r.returncode == 0 and "%d cases, 0 bad" % len(recs) in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
 
 
-def _sweep(key, cases, call, record):
+def _sweep(key, cases, call, record, rings=NC.RINGS):
     """every case under every ring, in place; call(ptr, n, cap, out) -> result.  The reference's result and bytes (sha256 where the
     case records one); returns the sanitizer program's records, made by record(case, offset mod 16, block, expected bytes)"""
     recs, straddle, total = [], 0, 0
-    for ring in NC.RINGS:
+    for ring in rings:
         blob, off, _, _ = NC.case_layout(key, cases, ring)
         B = Blob(blob, off)
         for i, c in enumerate(cases):
@@ -159,8 +160,21 @@ def test_lz4_dictionary_decoder(sims, tmp_path):
     dbuf = (C.c_ubyte * (len(d) + 32))()
     dptr = C.addressof(dbuf) + (-C.addressof(dbuf)) % 16 + 3
     C.memmove(dptr, d, len(d))
-    rec = lambda c, mis, block, exp: struct.pack("<5Iq", len(c["bytes"]), c["cap"], len(d), mis & 3, 3, c["result"]) + block + d + exp
-    _sanitized(tmp_path, "sim_lz4_dict_decode.cpp", _sweep("lz4_dict", NC.lz4_dict_cases(), lambda p, n, cap, out: L.sim_lz4_dict_decode(p, n, out, cap, dptr, len(d)), rec))
+    rec = lambda c, mis, block, exp: struct.pack("<6Iq", len(c["bytes"]), c["cap"], len(d), mis & 3, 3, 0, c["result"]) + block + d + exp
+    _sanitized(tmp_path, "sim_lz4_wave.cpp", _sweep("lz4_dict", NC.lz4_dict_cases(), lambda p, n, cap, out: L.sim_lz4_dict_decode(p, n, out, cap, dptr, len(d)), rec))
+
+
+def test_plain_lz4_and_snappy_block_decoders_with_ff_in_front(sims, tmp_path):
+    """the block cases of the GPU's test_block_decoders_with_ff_in_front (the `own` cuts of the input sweep's family A, body a: 48 bytes
+    of 0xFF in front, the stream's continuation behind) through lz4_wave_decode<false> and snappy_wave_decode, in place and as the
+    sanitizer programs"""
+    L, Ls = sims["lz4_dict"], sims["snappy"]
+    rec = lambda c, mis, block, exp: struct.pack("<6Iq", len(c["bytes"]), c["cap"], 0, mis & 3, 0, 1, c["result"]) + block + exp
+    recs = _sweep(("front", "lz4"), NC.front_cases("lz4"), lambda p, n, cap, out: L.sim_lz4_wave_decode(p, n, out, cap, 0), rec, rings=("own",))
+    _sanitized(tmp_path, "sim_lz4_wave.cpp", recs)
+    rec = lambda c, mis, block, exp: struct.pack("<3Iq", len(c["bytes"]), c["cap"], mis & 3, c["result"]) + block + exp
+    recs = _sweep(("front", "snappy"), NC.front_cases("snappy"), lambda p, n, cap, out: Ls.sim_snappy_wave_decode(p, n, out, cap), rec, rings=("own",))
+    _sanitized(tmp_path, "sim_snappy_wave.cpp", recs)
 
 
 def test_bgzf_walk(sims, tmp_path):
