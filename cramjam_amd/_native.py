@@ -23,6 +23,8 @@ E_NO_DEVICE = -100
 E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
 E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
 E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -50, -51, -52, -53, -54
+E_ORC_HEADER, E_ORC_BLOCK = -60, -61
+ORC_ZLIB, ORC_SNAPPY, ORC_LZ4, ORC_ZSTD = 1, 2, 4, 5      # ORC's CompressionKind (cj_orc_batch_*)
 ZSTD_FRAMES = 0                    # cj_zstd_format (cj_zstd_batch_*)
 ZSTD_FLAG_CHECKSUM = 1             # cj_zstd_compress_batch_*: a Content_Checksum behind the last block
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
@@ -100,6 +102,11 @@ SYMBOLS = {
     "cj_bgzf_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_bgzf_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_bgzf_compress_bound": (_sz, [_sz]),
+    "cj_orc_batch_device": (_int, [_vp, _int, _int, _u32, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_orc_batch_host": (_int, [_vp, _int, _int, _u32, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_orc_sizes_device": (_int, [_vp, _int, _u32, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_orc_sizes_host": (_int, [_vp, _int, _u32, _u32, _sz, _vp, _vp, _vp]),
+    "cj_orc_compress_bound": (_sz, [_sz, _u32]),
     "cj_zstd_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_bound": (_sz, [_sz, _u32]),
@@ -139,6 +146,7 @@ BENCH_SYMBOLS = {
     "cj_debug_dict_stage_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_bgzf_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_orc_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_enc_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_grid_chunks": (C.c_uint64, [C.c_uint64]),

@@ -721,3 +721,132 @@ def zstd_compress_many_device(inp, in_off, in_len, out, out_off, out_cap, checks
     zstd_compress_bound(in_len[i], checksum) always suffices.  Enqueue-only with device-resident metadata, a result tensor and
     sync=False (a call that has to grow the engine's record and literal slots waits for their previous user)."""
     return _device_batch(N.ZSTD_COMPRESS, N.ZSTD_FRAMES, N.OP_COMPRESS, _zstd_flags(checksum), inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+# ---- ORC compression streams (cj_orc_batch_* / cj_orc_sizes_* / cj_orc_compress_bound; DESIGN.md 5.17): both directions -----------------
+# One entry is a whole stream of an ORC file as it lies there (a data stream, an index stream, a stripe footer, the file footer):
+# chunks behind 3-byte headers, each the codec's output for at most block_size raw bytes or those bytes as they are.  result[i] = the
+# decoded (the stream's) length or a negative CJ_E_* code: -60 from the walk over the headers (truncated), then the first chunk's in
+# stream order whose size query fails (the codec's code) or that holds more than block_size bytes (-61), then -6 when the sizes' sum
+# exceeds the capacity, then the first bad chunk's code in stream order.  No call here is enqueue-only: each waits for the stream once.
+_ORC_KIND = {"zlib": N.ORC_ZLIB, "snappy": N.ORC_SNAPPY, "lz4": N.ORC_LZ4, "zstd": N.ORC_ZSTD}
+
+
+def _orc_kind(codec):
+    try:
+        return _ORC_KIND[codec]
+    except (KeyError, TypeError):
+        raise ValueError("codec must be 'zlib', 'snappy', 'lz4' or 'zstd', not %r" % (codec,)) from None
+
+
+def _orc_host_ptrs(buffers, idx):
+    import numpy as np
+    arrs = [np.frombuffer(buffers[i], dtype=np.uint8) for i in idx]              # borrowed, not copied
+    k = len(arrs)
+    return arrs, k, (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs]), (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
+
+
+def _orc_run(kind, op, block_size, inputs, out_caps, devices, out):
+    """cj_orc_batch_host, sharded like _run; out: as in lz4_decompress_blocks"""
+    import numpy as np
+    n = len(inputs)
+    offsets, run = [], 0
+    for c in out_caps:
+        offsets.append(run); run += int(c)
+    own = out is None
+    if own:
+        out = np.empty(max(run, 1), np.uint8)
+    dst = np.frombuffer(out, dtype=np.uint8)
+    if dst.size < run:
+        raise ValueError("cramjam_amd.batch: out holds %d bytes, %d are needed" % (dst.size, run))
+
+    def work(dev, idx):
+        arrs, k, ptrs, lens = _orc_host_ptrs(inputs, idx)
+        optrs = (_C.c_void_p * max(k, 1))(*[dst.ctypes.data + offsets[i] for i in idx])
+        caps = (_C.c_size_t * max(k, 1))(*[int(out_caps[i]) for i in idx])
+        res = np.empty(k, np.int64)
+        N.check(N.lib().cj_orc_batch_host(_engine(dev).h, kind, op, 0, block_size, k, ptrs, lens, optrs, caps, res.ctypes.data))
+        return ([int(x) for x in res],)
+    res, = _shard(devices, n, work)
+    mv = memoryview(out).cast("B")
+    outs = [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
+    return res, ([bytes(o) for o in outs] if own else outs)
+
+
+def orc_stream_sizes(streams, codec, block_size=262144, devices=None):
+    """decoded sizes of many ORC compression streams held on the host (list of ints; negative = CJ_E_* code): the walk over the chunk
+    headers and the codec's size query over every compressed chunk — ORC states no decoded length.  For "snappy" the chunks' sizes are
+    their headers' claims, verified only by the decode."""
+    import numpy as np
+    kind = _orc_kind(codec)
+
+    def work(dev, idx):
+        arrs, k, ptrs, lens = _orc_host_ptrs(streams, idx)
+        res = np.empty(k, np.int64)
+        N.check(N.lib().cj_orc_sizes_host(_engine(dev).h, kind, 0, block_size, k, ptrs, lens, res.ctypes.data))
+        return ([int(x) for x in res],)
+    return _shard(devices, len(streams), work)[0]
+
+
+def orc_decompress_streams(streams, codec, block_size=262144, output_lens=None, devices=None, out=None):
+    """decode many ORC compression streams, chunk-parallel; returns (results, outputs) as lz4_decompress_blocks.  codec: "zlib", "snappy",
+    "lz4" or "zstd" (the file's PostScript.compression); block_size: its compressionBlockSize — no chunk may hold more.
+    output_lens=None: the sizes are asked for first (orc_stream_sizes; the input then crosses the link twice): a stream the query
+    rejects gets the query's code as its result and an empty output."""
+    kind = _orc_kind(codec)
+    run = lambda caps: _orc_run(kind, N.OP_DECOMPRESS, block_size, streams, caps, devices, out)
+    if output_lens is not None:
+        return run(output_lens)
+    return _sizes_first(orc_stream_sizes(streams, codec, block_size, devices), run)
+
+
+def orc_compress_bound(n, block_size=262144):
+    """the capacity a buffer of n bytes needs: n + 3 * ceil(n / block_size), every piece an original chunk — exact for incompressible
+    input, 0 for an empty buffer (an empty stream); also 0 above 0x7E000000 or for a block_size outside 1 .. 262 144.  No device."""
+    return N.lib().cj_orc_compress_bound(n, block_size)
+
+
+def orc_compress_streams(buffers, codec, block_size=262144, devices=None, out=None):
+    """one ORC compression stream per buffer — pieces of block_size bytes, each the codec's output or, where that is not shorter, the
+    original bytes: what orc_decompress_streams and every ORC reader read; returns (results, outputs) as lz4_compress_blocks.  out: as
+    in lz4_decompress_blocks; it has to hold sum(orc_compress_bound(len(buffer), block_size)) bytes."""
+    kind, L = _orc_kind(codec), N.lib()
+    caps = [L.cj_orc_compress_bound(memoryview(b).nbytes, block_size) for b in buffers]
+    return _orc_run(kind, N.OP_COMPRESS, block_size, buffers, caps, devices, out)
+
+
+def _orc_device(kind, op, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync):
+    call = _DeviceCall(stream, sync)
+    try:
+        vin = call.buffer(inp)
+        vout = call.buffer(out) if out is not None else None
+        eng = call.engine(device, *([vin, vout] if vout is not None else [vin]))
+        i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
+        if vout is None:                            # the size query
+            p_res = call.result(result)
+            N.check(N.lib().cj_orc_sizes_device(eng.h, kind, 0, block_size, call.n, *i, p_res, stream))
+        else:
+            o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
+            p_res = call.result(result)
+            N.check(N.lib().cj_orc_batch_device(eng.h, kind, op, 0, block_size, call.n, *i, *o, p_res, stream))
+        return call.finish(p_res, result)
+    finally:
+        call.close()
+
+
+def orc_decompress_streams_device(inp, in_off, in_len, out, out_off, out_cap, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of ORC compression streams (arguments as lz4_decompress_frames_device; the call waits for the
+    stream once, for the streams' chunk counts)."""
+    return _orc_device(_orc_kind(codec), N.OP_DECOMPRESS, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def orc_stream_sizes_device(inp, in_off, in_len, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
+    """Decoded sizes of a device-resident batch of ORC compression streams, as orc_stream_sizes.  NOT enqueue-only: the call waits for
+    the stream once, for the streams' chunk counts."""
+    return _orc_device(_orc_kind(codec), N.OP_DECOMPRESS, block_size, inp, in_off, in_len, None, None, None, result, device, stream, sync)
+
+
+def orc_compress_streams_device(inp, in_off, in_len, out, out_off, out_cap, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
+    """Compress a device-resident batch into ORC compression streams (arguments as lz4_compress_frames_device; the call waits for the
+    stream once, for the buffers' lengths and capacities); out_cap[i] must be at least orc_compress_bound(in_len[i], block_size)."""
+    return _orc_device(_orc_kind(codec), N.OP_COMPRESS, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)

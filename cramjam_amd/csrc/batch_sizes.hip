@@ -7,7 +7,7 @@
 //                              bytes; one wavefront per chunk through the 512-byte register window for longer ones.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock — they may sit in front of a decode on the same
 // stream, or run next to a frame batch that holds the engine's frame scratch.
-#include "cj_stage.hpp"
+#include "blosc_filters.hpp"      // (cj_stage.hpp; declares launch_block_sizes)
 #include "frame_grammar.hpp"
 #include "lane_stream.hpp"
 #include "lz4_size_walk.hpp"
@@ -215,6 +215,11 @@ int sizes_host(Query q, cj_engine* e, int what, uint32_t flags, size_t n, const 
 }
 
 }  // namespace
+
+int cj::launch_block_sizes(int codec, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
+    if (n == 0) return 0;
+    return sizes_launch(Query::Blocks, codec, 0u, n, in_base, in_off, in_len, result, s);
+}
 
 extern "C" {
 

@@ -41,7 +41,18 @@ void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
 int launch_zlib_decode(const BatchArgs& a, hipStream_t s);
 // ... for CJ_DEFLATE_GZIP: the members of BGZF streams (bgzf_batch.hip), one row each
 int launch_gzip_decode(const BatchArgs& a, hipStream_t s);
+// ... for CJ_DEFLATE_RAW: the compressed chunks of ORC streams with ZLIB (orc_batch.hip), one row each
+int launch_deflate_raw_decode(const BatchArgs& a, hipStream_t s);
 // zstd.hip: the decode of cj_zstd_batch_device — its own cj::ScratchTurn on e->zstd_slots, slices by the literal-slot budget
 int launch_zstd_decode(::cj_engine* e, const BatchArgs& a, hipStream_t s);
+
+// The size queries of the plain batches over rows of a container (orc_batch.hip: ORC states no chunk's decoded length): result[i] = the
+// decoded length or the code cj_*_batch_sizes_device gives; a row with in_len 0 reads nothing.  No scratch; 0 or CJ_E_*; enqueue only.
+// deflate.hip: deflate_launch for CJ_DEFLATE_RAW in size mode
+int launch_deflate_raw_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
+// batch_sizes.hip: codec = CJ_CODEC_LZ4_BLOCK (raw blocks: the size walk) or CJ_CODEC_SNAPPY_RAW (the header's length)
+int launch_block_sizes(int codec, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
+// zstd.hip: the decoder without stores
+int launch_zstd_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
 
 }  // namespace cj

@@ -144,12 +144,13 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 
 }  // namespace cj
 
-// LOCK ORDER of the engine's mutexes: mu -> fb -> {scratch, zstd_slots, deflate_slots}.  A host batch stages under `mu` and takes the
+// LOCK ORDER of the engine's mutexes: mu -> fb -> {scratch, zstd_slots, deflate_slots, zstd_enc_slots}.  A host batch stages under `mu` and takes the
 // scratches inside it.  A frame batch and a Blosc batch hold their `fb` turn while cj::launch takes `scratch` for their LZ4 / Snappy
 // blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
 // streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
-// members, once per turn of member slots.  The three inner ones are taken one after another, never one inside another, and no path
-// takes two of the graph's mutexes the other way round; `dict_stage` and `zstd_enc_slots` are taken alone or under `mu` only.  The three
+// members, once per turn of member slots; an ORC batch (orc_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`
+// (decompress), `deflate_slots` or `zstd_enc_slots` (compress, once per turn of chunk slots).  The inner ones are taken one after another,
+// never one inside another, and no path takes two of the graph's mutexes the other way round; `dict_stage` is taken alone or under `mu` only.  The three
 // slotted scratches (`zstd_slots`, `deflate_slots`, `zstd_enc_slots`) are taken in one place, cj::slot_slices below.  The table
 // of every entry's turns: DESIGN.md §2; two streams and two threads per scratch: tests/test_scratch_streams_gpu.py.
 struct cj_engine {                 // (members are destroyed last to first: the streams outlive every buffer and event)
@@ -173,7 +174,7 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     int big_next = 0;
     cj::DevBuf d_big, d_bigtab;    // large.hip: parse scratch / record tables of one large stream (under `mu`)
     int n_cu = 0;
-    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip, bgzf_batch.hip: batches of framed streams / Blosc chunks / BGZF streams — frame table, block rows and decode slots, its staging
+    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip, bgzf_batch.hip, orc_batch.hip: batches of framed streams / Blosc chunks / BGZF streams / ORC streams — frame table, block rows and decode slots, its staging
     cj::DevBuf d_fb;
     cj::PinnedBuf h_fb;
     cj::Scratch dict_stage;        // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows

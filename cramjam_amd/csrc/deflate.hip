@@ -72,6 +72,16 @@ int cj::launch_gzip_decode(const cj::BatchArgs& a, hipStream_t s) {
     return deflate_launch(CJ_DEFLATE_GZIP, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
 }
 
+int cj::launch_deflate_raw_decode(const cj::BatchArgs& a, hipStream_t s) {
+    if (a.n_chunks == 0) return 0;
+    return deflate_launch(CJ_DEFLATE_RAW, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
+}
+
+int cj::launch_deflate_raw_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
+    if (n == 0) return 0;
+    return deflate_launch(CJ_DEFLATE_RAW, true, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
+}
+
 extern "C" {
 
 int cj_deflate_batch_device(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,

@@ -66,6 +66,11 @@ int cj::launch_zstd_decode(cj_engine* e, const cj::BatchArgs& a, hipStream_t s) 
     return decode_device(e, a, s);
 }
 
+int cj::launch_zstd_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
+    if (n == 0) return 0;
+    return sizes_launch(n, in_base, in_off, in_len, result, s);
+}
+
 extern "C" {
 
 int cj_zstd_batch_device(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,

@@ -79,6 +79,9 @@ extern "C" {
 #define CJ_E_ZSTD_CHECKSUM      (-52) /* libzstd: checksum_wrong (the content checksum differs or is cut off) */
 #define CJ_E_ZSTD_SRC_SIZE      (-53) /* libzstd: srcSize_wrong (a truncated input, or bytes behind the last frame) */
 #define CJ_E_ZSTD_DICT          (-54) /* libzstd: dictionary_wrong (the frame names a dictionary; none is supported) */
+#define CJ_E_ORC_HEADER         (-60) /* ORC compression stream: fewer than 3 bytes are left where a chunk header must stand, or a chunk's
+                                         length runs past the stream's end */
+#define CJ_E_ORC_BLOCK          (-61) /* ORC compression stream: a chunk, original or compressed, holds more than block_size decoded bytes */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -470,6 +473,59 @@ CJ_API int cj_bgzf_sizes_device(cj_engine* e, int what, uint32_t flags, size_t n
 CJ_API int cj_bgzf_sizes_host(cj_engine* e, int what, uint32_t flags, size_t n_streams,
                               const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
 CJ_API size_t cj_bgzf_compress_bound(size_t n);
+
+/* Batches of ORC compression streams, both directions: the framing of every data stream, index stream, stripe footer
+ * and file footer of an ORC file with compression != NONE (ORC specification, "Compression").  A stream is zero or more chunks; a chunk
+ * is a 3-byte little-endian header h and h >> 1 bytes: with h & 1 the original bytes, else the codec's output for at most block_size
+ * (the file's compressionBlockSize) raw bytes.  Nothing states a chunk's decoded length; there is no magic, no checksum and no end
+ * marker.  One entry of these batches is a whole stream of any size; every chunk of every stream is decoded (encoded) by the codec's
+ * plain batch.  Finding the streams in a file (the protobuf footers) is the reader's.  The argument shape is cj_bgzf_batch_*'s with
+ * block_size behind flags; addressing, the 16-byte-granule rule, stream rules, e == NULL, n_streams == 0 and the null-pointer rules are
+ * cj_deflate_batch_*'s.
+ *   what        ORC's CompressionKind: 1 ZLIB (raw DEFLATE, no zlib header), 2 SNAPPY (Snappy raw with its varint length), 4 LZ4 (a
+ *               raw LZ4 block, no size prefix), 5 ZSTD (one Zstandard frame).  Anything else (NONE 0, LZO 3, BROTLI 6) is CJ_E_BAD_ARG.
+ *   flags       0; any bit set is CJ_E_BAD_ARG.       op   CJ_OP_DECOMPRESS or CJ_OP_COMPRESS; anything else is CJ_E_BAD_ARG.
+ *   block_size  1 .. 2^23 for decompress and sizes (a header's length field has 23 bits), 1 .. 262 144 for compress; outside these
+ *               CJ_E_BAD_ARG.  These checks come first and need no device.
+ *   decompress  result[i] = the decoded length or CJ_E_*.  First the walk over the headers: CJ_E_ORC_HEADER — fewer than 3 bytes are
+ *               left where a header must stand, or a chunk's length runs past the stream's end.  Then the sizes of the chunks — an
+ *               original chunk's length, a compressed chunk's by the codec's size query (cj_deflate_batch_sizes_* for CJ_DEFLATE_RAW,
+ *               cj_batch_sizes_* for raw LZ4 blocks and Snappy raw, cj_zstd_batch_sizes_*): the first chunk in stream order whose
+ *               size is an error, or above block_size (CJ_E_ORC_BLOCK), gives its code.  Then CJ_E_OUT_TOO_SMALL when the sizes' sum
+ *               exceeds out_cap[i].  A stream refused so far is not decoded and its slot is not written.  Every chunk then decodes
+ *               (is copied) into its own bytes of the slot, behind those of the chunks before it; the stream's result is the code of
+ *               the first chunk in stream order whose decode does not give exactly its size — a Snappy header that lies gives
+ *               CJ_E_SNAPPY_CORRUPT.  A stream with a bad chunk may have written inside its own slot, never outside it; one bad stream
+ *               never affects another.
+ *   sizes       cj_orc_sizes_*: the same up to the sum — result[i] = the decoded length or the first error.  For ZLIB, LZ4 and ZSTD
+ *               the size query walks every chunk's stream to its end; for SNAPPY the length is the header's claim, which only the
+ *               decode verifies.
+ *   compress    one stream per buffer: pieces of block_size bytes, the last one shorter, each through the codec's plain encoder
+ *               (cj_deflate_compress_batch_* with CJ_DEFLATE_RAW, cj_batch_device for LZ4 without prefix and Snappy raw,
+ *               cj_zstd_compress_batch_* without checksum); a piece whose compressed length is not below its raw length becomes an
+ *               original chunk.  An empty buffer gives an empty stream (result 0).  The bytes depend on nothing but the input.
+ *               result[i] = the stream's length; CJ_E_INPUT_TOO_LARGE for in_len[i] > 0x7E000000; CJ_E_OUT_TOO_SMALL when out_cap[i]
+ *               is below cj_orc_compress_bound(in_len[i], block_size) — decided before the first store: such a stream writes nothing.
+ *   bound       cj_orc_compress_bound(n, block_size) = n + 3 * ceil(n / block_size): every piece an original chunk; exact for
+ *               incompressible input, 0 for n == 0.  Also 0 for n > 0x7E000000 or a block_size compress does not take.  Pure
+ *               arithmetic, no device.
+ * NONE of these calls is enqueue-only, the size query included: each takes one turn at the engine's container scratch and waits for
+ * the stream ONCE (decompress, sizes: for the streams' chunk counts; compress: for the buffers' lengths and capacities); the encoder's
+ * bound-sized chunk slots are engine scratch within a fixed budget, a large batch runs in turns.  The _host calls are cj_batch_host's
+ * one-shot staging, synchronous. */
+CJ_API int cj_orc_batch_device(cj_engine* e, int what, cj_op op, uint32_t flags, uint32_t block_size, size_t n_streams,
+                               const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                               uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                               int64_t* result, void* hip_stream);
+CJ_API int cj_orc_batch_host(cj_engine* e, int what, cj_op op, uint32_t flags, uint32_t block_size, size_t n_streams,
+                             const uint8_t* const* in_ptrs, const size_t* in_lens,
+                             uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API int cj_orc_sizes_device(cj_engine* e, int what, uint32_t flags, uint32_t block_size, size_t n_streams,
+                               const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                               int64_t* result, void* hip_stream);
+CJ_API int cj_orc_sizes_host(cj_engine* e, int what, uint32_t flags, uint32_t block_size, size_t n_streams,
+                             const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+CJ_API size_t cj_orc_compress_bound(size_t n, uint32_t block_size);
 
 /* Zstandard frames — decode (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
  * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an

@@ -61,6 +61,9 @@ CJ_API uint64_t cj_debug_deflate_slot_budget(uint64_t bytes);
 /* BGZF compress (cj_bgzf_batch_* with CJ_OP_COMPRESS): the bytes of bound-sized member slots per turn, one slot of 65 312 bytes per member
  * in flight (0 = the default, 4096 slots); returns the previous value.  Tests force more than one turn with it. */
 CJ_API uint64_t cj_debug_bgzf_slot_budget(uint64_t bytes);
+/* ORC compress (cj_orc_batch_* with CJ_OP_COMPRESS): the bytes of bound-sized chunk slots per turn, one slot of the codec's bound for
+ * block_size bytes per chunk in flight (0 = the default, 256 MiB); returns the previous value.  Tests force more than one turn with it. */
+CJ_API uint64_t cj_debug_orc_slot_budget(uint64_t bytes);
 /* Zstandard decode (cj_zstd_batch_*): the bytes of literal slots per slice, one slot of 128 KiB + 32 per stream in flight (0 = the
  * default); returns the previous value */
 CJ_API uint64_t cj_debug_zstd_slot_budget(uint64_t bytes);
