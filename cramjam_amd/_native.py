@@ -196,12 +196,13 @@ def _batch_host_addr(name="cj_batch_host"):
 
 
 class Kind:
-    """One kind of batch: its four C symbols, and how `what` (a CODEC_* / FORMAT_*; Blosc chunks have none) and `params` (a BloscParams
-    or None) enter their argument lists.  i = (in_base, in_off, in_len) / (in_ptrs, in_lens); o = (out_base, out_off, out_cap)."""
+    """One kind of batch: its four C symbols, and how `what` (a CODEC_* / FORMAT_*; Blosc chunks have none), `params` (a BloscParams
+    or None) and `extra` enter their argument lists.  i = (in_base, in_off, in_len) / (in_ptrs, in_lens); o = (out_base, out_off, out_cap)."""
 
-    def __init__(self, host, device, sizes_host, sizes_device, blosc=False, dictionary=False, one_op=False):
+    def __init__(self, host, device, sizes_host, sizes_device, blosc=False, dictionary=False, one_op=False, extra=False):
         self.host, self.device, self.sizes_host, self.sizes_device, self.blosc = host, device, sizes_host, sizes_device, blosc
         self.one_op = one_op                        # the calls have one direction: their argument lists carry no `op`
+        self.extra = extra                          # the calls carry one uint32_t of their own directly behind `flags` (ORC: block_size)
         self.dictionary = dictionary                # the calls take (dict, dict_len) / (dict_len,) behind result: `params` = that tuple
 
     def read_flags(self, blosclz=False, zlib=False, zstd=False):
@@ -211,15 +212,18 @@ class Kind:
             raise ValueError("blosclz, zlib and zstd apply to Blosc chunks only")
         return (BLOSC_FLAG_READ_BLOSCLZ if blosclz else 0) | (BLOSC_FLAG_READ_ZLIB if zlib else 0) | (BLOSC_FLAG_READ_ZSTD if zstd else 0)
 
-    def device_args(self, h, what, op, flags, n, i, o, result, params, stream):
+    def _flags(self, flags, extra):
+        return (flags, extra) if self.extra else (flags,)
+
+    def device_args(self, h, what, op, flags, n, i, o, result, params, stream, extra=None):
         if self.blosc:                              # (cj_blosc_batch_device has an argument order of its own)
             return (h, op) + i + o + (result, n, C.byref(params) if params is not None else None, flags, stream)
-        head = (h, what, flags, n) if self.one_op else (h, what, op, flags, n)
+        head = ((h, what) if self.one_op else (h, what, op)) + self._flags(flags, extra) + (n,)
         return head + i + o + (result,) + (tuple(params) if self.dictionary else ()) + (stream,)
 
-    def sizes_args(self, h, what, flags, n, body, tail=(), dict_len=0):
+    def sizes_args(self, h, what, flags, n, body, tail=(), dict_len=0, extra=None):
         """body = i + (result,); tail = (stream,) for the device form; dict_len (dictionary batches only) goes between them"""
-        return ((h, flags, n) if self.blosc else (h, what, flags, n)) + body + ((dict_len,) if self.dictionary else ()) + tail
+        return ((h,) if self.blosc else (h, what)) + self._flags(flags, extra) + (n,) + body + ((dict_len,) if self.dictionary else ()) + tail
 
 
 BLOCKS = Kind("cj_batch_host", "cj_batch_device", "cj_batch_sizes_host", "cj_batch_sizes_device")
@@ -230,8 +234,9 @@ DEFLATE_COMPRESS = Kind("cj_deflate_compress_batch_host", "cj_deflate_compress_b
 ZSTD = Kind("cj_zstd_batch_host", "cj_zstd_batch_device", "cj_zstd_batch_sizes_host", "cj_zstd_batch_sizes_device")   # what = ZSTD_FRAMES
 ZSTD_COMPRESS = Kind("cj_zstd_compress_batch_host", "cj_zstd_compress_batch_device", None, None, one_op=True)      # what = ZSTD_FRAMES; no size query
 BGZF = Kind("cj_bgzf_batch_host", "cj_bgzf_batch_device", "cj_bgzf_sizes_host", "cj_bgzf_sizes_device")   # what = 0; both directions
+ORC = Kind("cj_orc_batch_host", "cj_orc_batch_device", "cj_orc_sizes_host", "cj_orc_sizes_device", extra=True)   # what = an ORC_*; extra = block_size
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
-_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BGZF, BLOSC)}
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BGZF, ORC, BLOSC)}
 
 
 class Engine:
@@ -295,30 +300,33 @@ class Engine:
         check(lib().cj_frame_batch_device(self.h, fmt, op, flags, n, in_base, in_off, in_len, out_base, out_off,
                                           out_cap, result, stream))
 
-    def _host(self, entry, codec, op, flags, args, fn, params, dictionary):
+    def _host(self, entry, codec, op, flags, args, fn, params, dictionary, extra=None):
         """entry: batch_host or batch_host_into of the CPython host layer (the engine scatters straight into the bytes objects / the buffer).
         fn: a Kind, or the name of its host entry — the call's signature is the Kind's: BLOSC takes params, the bytes of a cj_blosc_params
-        (b"" = decompress; codec is not used), DICT a dictionary, bytes-like (borrowed), DEFLATE_COMPRESS and ZSTD_COMPRESS have no op.  None: DICT with a
-        dictionary, BLOSC with params, else BLOCKS.  An argument the Kind does not take: ValueError."""
+        (b"" = decompress; codec is not used), DICT a dictionary, bytes-like (borrowed), DEFLATE_COMPRESS and ZSTD_COMPRESS have no op, ORC takes
+        extra, its block_size, an int.  None: DICT with a dictionary, BLOSC with params, else BLOCKS.  An argument the Kind does not take: ValueError."""
         from . import _cramjam
         if fn is None:
             fn = DICT if dictionary is not None else BLOSC if params is not None else BLOCKS
         kind = fn if isinstance(fn, Kind) else _HOST_KINDS[fn]
         if (params is not None and not kind.blosc) or (dictionary is not None and not kind.dictionary):
             raise ValueError("cramjam_amd: %s takes no %s" % (kind.host, "params" if params is not None and not kind.blosc else "dictionary"))
+        if (extra is not None) != kind.extra:
+            raise ValueError("cramjam_amd: %s takes %s extra word" % (kind.host, "an" if kind.extra else "no"))
         try:
             return getattr(_cramjam, entry)(self.h.value or 0, 0 if kind.blosc else int(codec), int(op), int(flags), *args, _batch_host_addr(kind.host),
-                                            params, dictionary, kind.one_op)
+                                            params, dictionary, kind.one_op, extra)
         except RuntimeError as ex:                  # (a CJ_E_* return code of the call itself, not of a chunk)
             raise EngineError(_with_hip_error(str(ex))) from None
 
-    def batch_host(self, codec, op, flags, inputs, out_caps, fn=None, params=None, dictionary=None):
+    def batch_host(self, codec, op, flags, inputs, out_caps, fn=None, params=None, dictionary=None, extra=None):
         """inputs: list of bytes-like (anything with the buffer protocol: borrowed, not copied); out_caps: list of capacities.
         Returns (results, outputs): results[i] = bytes produced or a negative CJ_E_* code, outputs[i] = bytes.
-        fn: the Kind of the batch or the name of its host entry, "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*)."""
-        return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params, dictionary)
+        fn: the Kind of the batch or the name of its host entry, "cj_frame_batch_host" for batches of framed streams (codec is then a FORMAT_*).
+        extra: the uint32_t a Kind with `extra` carries behind flags (N.ORC: the block size)."""
+        return self._host("batch_host", codec, op, flags, (inputs, out_caps), fn, params, dictionary, extra)
 
-    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn=None, params=None, dictionary=None):
+    def batch_host_into(self, codec, op, flags, inputs, out_caps, out, offsets=None, fn=None, params=None, dictionary=None, extra=None):
         """the same batch into ONE writable buffer (bytearray, numpy array, ...): chunk i at out[offsets[i] : offsets[i] + out_caps[i]],
         back to back when offsets is None.  Returns results."""
-        return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params, dictionary)
+        return self._host("batch_host_into", codec, op, flags, (inputs, out_caps, out, offsets), fn, params, dictionary, extra)

@@ -35,12 +35,12 @@ def _pick(seq, idx):
     return seq if len(idx) == len(seq) else [seq[i] for i in idx]
 
 
-def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None):
+def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None, extra=None):
     """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress),
-    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*), N.ZSTD / N.ZSTD_COMPRESS (what = ZSTD_FRAMES).
+    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*), N.ZSTD / N.ZSTD_COMPRESS (what = ZSTD_FRAMES), N.BGZF (what = 0) or N.ORC (what = an ORC_*, extra: the block size).
     out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
-    tail = {"dictionary": params} if kind is N.DICT else {"params": params}
+    tail = {"dictionary": params} if kind is N.DICT else {"extra": extra} if kind.extra else {"params": params}
     if out is None:
         return _shard(devices, n, lambda dev, idx: _engine(dev).batch_host(what, op, flags, _pick(inputs, idx), _pick(out_caps, idx), kind, **tail))
     offsets, run = [], 0
@@ -315,7 +315,7 @@ class _DeviceCall:
             v.release()
 
 
-def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, params=None, dictionary=None):
+def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, params=None, dictionary=None, extra=None):
     """dictionary (LZ4 blocks only): a device buffer — the batch goes through N.DICT with (its address, its length) behind result"""
     call = _DeviceCall(stream, sync)
     try:
@@ -327,13 +327,13 @@ def _device_batch(kind, what, op, flags, inp, in_off, in_len, out, out_off, out_
         i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
         o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
         p_res = call.result(result)
-        N.check(getattr(N.lib(), kind.device)(*kind.device_args(eng.h, what, op, flags, call.n, i, o, p_res, params, stream)))
+        N.check(getattr(N.lib(), kind.device)(*kind.device_args(eng.h, what, op, flags, call.n, i, o, p_res, params, stream, extra)))
         return call.finish(p_res, result)
     finally:
         call.close()
 
 
-def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream, sync, dictionary=None):
+def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream, sync, dictionary=None, extra=None):
     call = _DeviceCall(stream, sync)
     try:
         vin = call.buffer(inp)
@@ -343,7 +343,7 @@ def _device_sizes(kind, what, flags, inp, in_off, in_len, result, device, stream
             kind, dict_len = N.DICT, call.buffer(dictionary).nbytes
         p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
         p_res = call.result(result)
-        N.check(getattr(N.lib(), kind.sizes_device)(*kind.sizes_args(eng.h, what, flags, call.n, (vin.ptr, p_in_off, p_in_len, p_res), (stream,), dict_len)))
+        N.check(getattr(N.lib(), kind.sizes_device)(*kind.sizes_args(eng.h, what, flags, call.n, (vin.ptr, p_in_off, p_in_len, p_res), (stream,), dict_len, extra)))
         return call.finish(p_res, result)
     finally:
         call.close()
@@ -448,7 +448,7 @@ def snappy_framed_sizes_device(inp, in_off, in_len, result=None, device=None, st
     return _device_sizes(N.FRAMES, N.FORMAT_SNAPPY_FRAMED, 0, inp, in_off, in_len, result, device, stream, sync)
 
 
-def _host_sizes(kind, what, flags, buffers, devices, dict_len=0):
+def _host_sizes(kind, what, flags, buffers, devices, dict_len=0, extra=None):
     """sharded like _run: buffer i -> engine i mod G"""
     import numpy as np
 
@@ -458,7 +458,7 @@ def _host_sizes(kind, what, flags, buffers, devices, dict_len=0):
         ptrs = (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
         lens = (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
         res = np.empty(k, np.int64)
-        N.check(getattr(N.lib(), kind.sizes_host)(*kind.sizes_args(_engine(dev).h, what, flags, k, (ptrs, lens, res.ctypes.data), (), dict_len)))
+        N.check(getattr(N.lib(), kind.sizes_host)(*kind.sizes_args(_engine(dev).h, what, flags, k, (ptrs, lens, res.ctypes.data), (), dict_len, extra)))
         return ([int(x) for x in res],)
     return _shard(devices, len(buffers), work)[0]
 
@@ -739,53 +739,11 @@ def _orc_kind(codec):
         raise ValueError("codec must be 'zlib', 'snappy', 'lz4' or 'zstd', not %r" % (codec,)) from None
 
 
-def _orc_host_ptrs(buffers, idx):
-    import numpy as np
-    arrs = [np.frombuffer(buffers[i], dtype=np.uint8) for i in idx]              # borrowed, not copied
-    k = len(arrs)
-    return arrs, k, (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs]), (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
-
-
-def _orc_run(kind, op, block_size, inputs, out_caps, devices, out):
-    """cj_orc_batch_host, sharded like _run; out: as in lz4_decompress_blocks"""
-    import numpy as np
-    n = len(inputs)
-    offsets, run = [], 0
-    for c in out_caps:
-        offsets.append(run); run += int(c)
-    own = out is None
-    if own:
-        out = np.empty(max(run, 1), np.uint8)
-    dst = np.frombuffer(out, dtype=np.uint8)
-    if dst.size < run:
-        raise ValueError("cramjam_amd.batch: out holds %d bytes, %d are needed" % (dst.size, run))
-
-    def work(dev, idx):
-        arrs, k, ptrs, lens = _orc_host_ptrs(inputs, idx)
-        optrs = (_C.c_void_p * max(k, 1))(*[dst.ctypes.data + offsets[i] for i in idx])
-        caps = (_C.c_size_t * max(k, 1))(*[int(out_caps[i]) for i in idx])
-        res = np.empty(k, np.int64)
-        N.check(N.lib().cj_orc_batch_host(_engine(dev).h, kind, op, 0, block_size, k, ptrs, lens, optrs, caps, res.ctypes.data))
-        return ([int(x) for x in res],)
-    res, = _shard(devices, n, work)
-    mv = memoryview(out).cast("B")
-    outs = [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
-    return res, ([bytes(o) for o in outs] if own else outs)
-
-
 def orc_stream_sizes(streams, codec, block_size=262144, devices=None):
     """decoded sizes of many ORC compression streams held on the host (list of ints; negative = CJ_E_* code): the walk over the chunk
     headers and the codec's size query over every compressed chunk — ORC states no decoded length.  For "snappy" the chunks' sizes are
     their headers' claims, verified only by the decode."""
-    import numpy as np
-    kind = _orc_kind(codec)
-
-    def work(dev, idx):
-        arrs, k, ptrs, lens = _orc_host_ptrs(streams, idx)
-        res = np.empty(k, np.int64)
-        N.check(N.lib().cj_orc_sizes_host(_engine(dev).h, kind, 0, block_size, k, ptrs, lens, res.ctypes.data))
-        return ([int(x) for x in res],)
-    return _shard(devices, len(streams), work)[0]
+    return _host_sizes(N.ORC, _orc_kind(codec), 0, streams, devices, extra=block_size)
 
 
 def orc_decompress_streams(streams, codec, block_size=262144, output_lens=None, devices=None, out=None):
@@ -794,7 +752,7 @@ def orc_decompress_streams(streams, codec, block_size=262144, output_lens=None, 
     output_lens=None: the sizes are asked for first (orc_stream_sizes; the input then crosses the link twice): a stream the query
     rejects gets the query's code as its result and an empty output."""
     kind = _orc_kind(codec)
-    run = lambda caps: _orc_run(kind, N.OP_DECOMPRESS, block_size, streams, caps, devices, out)
+    run = lambda caps: _run(kind, N.OP_DECOMPRESS, 0, streams, caps, devices, out, N.ORC, extra=block_size)
     if output_lens is not None:
         return run(output_lens)
     return _sizes_first(orc_stream_sizes(streams, codec, block_size, devices), run)
@@ -812,41 +770,22 @@ def orc_compress_streams(buffers, codec, block_size=262144, devices=None, out=No
     in lz4_decompress_blocks; it has to hold sum(orc_compress_bound(len(buffer), block_size)) bytes."""
     kind, L = _orc_kind(codec), N.lib()
     caps = [L.cj_orc_compress_bound(memoryview(b).nbytes, block_size) for b in buffers]
-    return _orc_run(kind, N.OP_COMPRESS, block_size, buffers, caps, devices, out)
-
-
-def _orc_device(kind, op, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync):
-    call = _DeviceCall(stream, sync)
-    try:
-        vin = call.buffer(inp)
-        vout = call.buffer(out) if out is not None else None
-        eng = call.engine(device, *([vin, vout] if vout is not None else [vin]))
-        i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
-        if vout is None:                            # the size query
-            p_res = call.result(result)
-            N.check(N.lib().cj_orc_sizes_device(eng.h, kind, 0, block_size, call.n, *i, p_res, stream))
-        else:
-            o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
-            p_res = call.result(result)
-            N.check(N.lib().cj_orc_batch_device(eng.h, kind, op, 0, block_size, call.n, *i, *o, p_res, stream))
-        return call.finish(p_res, result)
-    finally:
-        call.close()
+    return _run(kind, N.OP_COMPRESS, 0, buffers, caps, devices, out, N.ORC, extra=block_size)
 
 
 def orc_decompress_streams_device(inp, in_off, in_len, out, out_off, out_cap, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
     """Decode a device-resident batch of ORC compression streams (arguments as lz4_decompress_frames_device; the call waits for the
     stream once, for the streams' chunk counts)."""
-    return _orc_device(_orc_kind(codec), N.OP_DECOMPRESS, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    return _device_batch(N.ORC, _orc_kind(codec), N.OP_DECOMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, extra=block_size)
 
 
 def orc_stream_sizes_device(inp, in_off, in_len, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
     """Decoded sizes of a device-resident batch of ORC compression streams, as orc_stream_sizes.  NOT enqueue-only: the call waits for
     the stream once, for the streams' chunk counts."""
-    return _orc_device(_orc_kind(codec), N.OP_DECOMPRESS, block_size, inp, in_off, in_len, None, None, None, result, device, stream, sync)
+    return _device_sizes(N.ORC, _orc_kind(codec), 0, inp, in_off, in_len, result, device, stream, sync, extra=block_size)
 
 
 def orc_compress_streams_device(inp, in_off, in_len, out, out_off, out_cap, codec, block_size=262144, result=None, device=None, stream=None, sync=True):
     """Compress a device-resident batch into ORC compression streams (arguments as lz4_compress_frames_device; the call waits for the
     stream once, for the buffers' lengths and capacities); out_cap[i] must be at least orc_compress_bound(in_len[i], block_size)."""
-    return _orc_device(_orc_kind(codec), N.OP_COMPRESS, block_size, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+    return _device_batch(N.ORC, _orc_kind(codec), N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, extra=block_size)

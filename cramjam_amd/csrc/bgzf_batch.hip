@@ -2,10 +2,11 @@
 // DESIGN.md §5.16): the blocked gzip of BAM, BCF, tabix-indexed VCF and every `bgzip` file.  A stream is gzip members of at most
 // 64 KiB that state their own length, so every member of every stream is one entry of a batch the engine already runs: the gzip
 // member decoder (deflate.hip) and the DEFLATE encoder (deflate_encode.hip) are the inner kernels, unchanged.  This file is the
-// container around them, frame_batch.hip's mapping: the hop walk (bgzf_grammar.hpp, one lane per stream, two passes around one
-// read-back of the member counts), the member rows, the stream-order verdict (one wavefront per stream), and for the encoder the
-// layout (one wavefront per stream) and the assembly (one wavefront per member).
-#include "blosc_filters.hpp"      // (cj_stage.hpp; declares launch_gzip_decode)
+// container around them, in the shell of cj_container.hpp (the count pass, the one read-back, the row scan; the encoder's piece turns):
+// what is BGZF's own is the hop walk (bgzf_grammar.hpp, one lane per stream, in both passes), the member rows, the stream-order verdict
+// (one wavefront per stream), and for the encoder the layout (one wavefront per stream) and the assembly (one wavefront per member).
+#include "blosc_filters.hpp"      // (declares launch_gzip_decode)
+#include "cj_container.hpp"
 #include "bgzf_grammar.hpp"
 
 
@@ -13,15 +14,13 @@ namespace cj {
 
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
 // cj_deflate_compress_bound(n, CJ_DEFLATE_GZIP), for the arithmetic that has to hold at compile time (tests compare the two)
 constexpr uint64_t gzip_bound(uint64_t n) { return n + 10u * (n / 65536u) + 5u * ((n % 65536u != 0u || n == 0u) ? 1u : 0u) + 18u; }
 // a member of p input bytes at most: the encoder's stream with its 10-byte header replaced by the 18-byte one
 constexpr uint64_t member_bound(uint64_t p) { return gzip_bound(p) - 10u + kBgzfHead; }
 // A piece below 65 536 bytes is one DEFLATE block, at worst a stored one: the largest member is 65 311 bytes and fits BSIZE
 static_assert(member_bound(kBgzfPiece) == 65311u && member_bound(kBgzfPiece) <= 65536u, "a full piece's worst case must fit BSIZE");
-constexpr uint64_t kSlotStride = (gzip_bound(kBgzfPiece) + 15u) & ~(uint64_t)15u;      // a bound-sized scratch slot per member in flight
+constexpr uint64_t kSlotStride = up16(gzip_bound(kBgzfPiece));      // a bound-sized scratch slot per member in flight
 
 constexpr uint64_t bgzf_bound(uint64_t n) {
     return (n / kBgzfPiece) * member_bound(kBgzfPiece) + (n % kBgzfPiece ? member_bound(n % kBgzfPiece) : 0u) + kBgzfMarker;
@@ -30,37 +29,30 @@ constexpr uint64_t bgzf_bound(uint64_t n) {
 }  // namespace
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------------
-// One row per stream.  row0 comes from the host's scan of the first pass.
-struct BgStream {
-    uint64_t row0, total;      // first member row; the ISIZE sum
-    int64_t err;               // the walk's error, or CJ_E_OUT_TOO_SMALL when the ISIZE sum exceeds out_cap: such a stream has no rows
-    uint64_t nmem;
-};
-
 // Pass 1, and alone the size query (st == nullptr: result[i] = the ISIZE sum or the walk's error; out_cap is not read)
 __global__ __launch_bounds__(kBlockThreads) void bgzf_count_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
-                                                                   const uint64_t* out_cap, BgStream* st, int64_t* result) {
+                                                                   const uint64_t* out_cap, StreamRow* st, int64_t* result) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     uint64_t total = 0, nm = 0;
     int64_t err = bgzf_walk(in_base + in_off[i], (size_t)in_len[i], [&](uint64_t, uint32_t, uint32_t isize) { nm++; total += isize; });
     if (st == nullptr) { result[i] = err ? err : (int64_t)total; return; }
     if (err == 0 && total > out_cap[i]) err = CJ_E_OUT_TOO_SMALL;
-    st[i] = BgStream{0, total, err, err ? 0 : nm};
+    st[i] = StreamRow{0, total, err, err ? 0 : nm};
 }
 
 // Pass 2: the same walk writes one row per member — the member in the stream, its ISIZE bytes of the caller's slot behind the members
 // before it.  The rows were counted from the same bytes; should they have changed since, a member the count does not cover or whose
 // bytes would pass the verified sum gets no room, and a row the walk no longer reaches is an empty one.
 __global__ __launch_bounds__(kBlockThreads) void bgzf_rows_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
-                                                                  const uint64_t* out_off, const BgStream* st, BatchRows r) {
+                                                                  const uint64_t* out_off, const StreamRow* st, BatchRows r) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
-    const BgStream f = st[i];
-    if (f.nmem == 0) return;
+    const StreamRow f = st[i];
+    if (f.count == 0) return;
     uint64_t k = 0, run = 0;
     bgzf_walk(in_base + in_off[i], (size_t)in_len[i], [&](uint64_t off, uint32_t len, uint32_t isize) {
-        if (k < f.nmem && run + isize <= f.total) {
+        if (k < f.count && run + isize <= f.total) {
             const uint64_t g = f.row0 + k;
             r.in_off[g] = in_off[i] + off; r.in_len[g] = len;
             r.out_off[g] = out_off[i] + run; r.out_cap[g] = isize;
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(kBlockThreads) void bgzf_rows_kernel(uint32_t n, co
             k++; run += isize;
         }
     });
-    for (; k < f.nmem; k++) {
+    for (; k < f.count; k++) {
         const uint64_t g = f.row0 + k;
         r.in_off[g] = in_off[i]; r.in_len[g] = 0; r.out_off[g] = out_off[i]; r.out_cap[g] = 0; r.result[g] = 0;
     }
@@ -77,20 +69,13 @@ __global__ __launch_bounds__(kBlockThreads) void bgzf_rows_kernel(uint32_t n, co
 // One wavefront per stream: the walk's error first, then the first failing member in stream order (the lanes stride over the member
 // results, a wave-wide minimum finds it).  A member's CJ_E_OUT_TOO_SMALL means that it holds more than its own ISIZE says: zlib's
 // "incorrect length check".
-__global__ __launch_bounds__(kBlockThreads) void bgzf_verdict_kernel(uint32_t n, const BgStream* st, const int64_t* mres, int64_t* result) {
+__global__ __launch_bounds__(kBlockThreads) void bgzf_verdict_kernel(uint32_t n, const StreamRow* st, const int64_t* mres, int64_t* result) {
     const uint32_t i = uni(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
     if (i >= n) return;
-    const BgStream f = st[i];
+    const StreamRow f = st[i];
     int64_t res = f.err ? f.err : (int64_t)f.total;
-    if (f.nmem) {
-        unsigned long long first = ~0ull;
-        for (uint64_t k = lane_id(); k < f.nmem; k += 64u)
-            if (mres[f.row0 + k] < 0) { first = k; break; }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) {
-            const unsigned long long o = __shfl_xor(first, sh, 64);
-            first = o < first ? o : first;
-        }
+    if (f.count) {
+        const unsigned long long first = first_failing_row(f.count, [&](uint64_t k) { return mres[f.row0 + k] < 0; });
         if (first != ~0ull) {
             res = mres[f.row0 + first];
             if (res == CJ_E_OUT_TOO_SMALL) res = CJ_E_DEFLATE_CHECKSUM;
@@ -129,36 +114,6 @@ __global__ __launch_bounds__(kBlockThreads) void bgzf_empty_kernel(uint32_t n, c
         if (res > 0) bgzf_put_head(out_base + out_off[i], 0x03001bu, kBgzfMarker);
     }
     if (lane_id() == 0) result[i] = res;
-}
-
-// the rows of pieces [t0, t0 + cnt): slot j of the scratch is piece t0 + j's, owner[j] its stream (the last one that begins at or
-// before the piece: streams without pieces share their successor's piece0 and lie before it)
-__global__ __launch_bounds__(kBlockThreads) void bgzf_piece_rows_kernel(uint64_t t0, uint32_t cnt, uint32_t n, const BgEnc* enc, const uint64_t* in_off,
-                                                                        const uint64_t* in_len, BatchRows r, uint32_t* owner, uint64_t stride) {
-    const uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (j >= cnt) return;
-    const uint64_t g = t0 + j;
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (enc[mid].piece0 <= g) lo = mid + 1u; else hi = mid;
-    }
-    const uint32_t i = lo - 1u;                                           // (enc[0].piece0 = 0 <= g)
-    const uint64_t at = (g - enc[i].piece0) * kBgzfPiece, len = in_len[i];
-    r.in_off[j] = in_off[i] + at;
-    r.in_len[j] = len - at < kBgzfPiece ? len - at : kBgzfPiece;
-    r.out_off[j] = (uint64_t)j * stride;
-    r.out_cap[j] = stride;
-    owner[j] = i;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane_id() >= (uint32_t)d) v += t;
-    }
-    return v;
 }
 
 // One wavefront per stream sa + w of a turn: the sizes of its members of this turn into their offsets in the stream, 64 at a time by
@@ -225,9 +180,7 @@ __global__ __launch_bounds__(kBlockThreads) void bgzf_assemble_kernel(uint64_t t
 namespace {
 
 using cj::BgEnc;
-using cj::BgStream;
-
-inline dim3 lane_grid(size_t n) { return dim3((uint32_t)((n + cj::kBlockThreads - 1) / cj::kBlockThreads)); }
+using cj::lane_grid;
 
 // bytes of bound-sized member slots per turn of a compress batch at most: 4096 slots
 cj::SlotBudget g_slot_budget{4096ull * cj::kSlotStride};
@@ -241,28 +194,17 @@ int bgzf_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const u
 
 int bgzf_decode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off,
                 const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    // One turn at the container batches' scratch, as a frame batch takes it (frame_batch.hip): held across the call's one wait
+    // One turn at the container batches' scratch, held across the call's one wait (cj_container.hpp)
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
-    const size_t tab = cj::up16(n * sizeof(BgStream));
-    int rc;
-    if ((rc = turn.reserve(e->d_fb, tab)) != 0 || (rc = turn.reserve(e->h_fb, tab)) != 0) return rc;
-    BgStream* h_st = reinterpret_cast<BgStream*>(e->h_fb.p);
-    hipLaunchKernelGGL(cj::bgzf_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap,
-                       reinterpret_cast<BgStream*>(e->d_fb.p), nullptr);
-    HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync(h_st, e->d_fb.p, n * sizeof(BgStream), hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);       // the one wait: the host sizes the member rows from the streams' member counts
-    uint64_t nb = 0;
-    for (size_t i = 0; i < n; i++) { h_st[i].row0 = nb; nb += h_st[i].nmem; }
-    if (nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    // d_fb: streams | member rows.  No data scratch: the members decode straight into the callers' slots
-    if ((rc = turn.reserve(e->d_fb, tab + 5 * 8 * (size_t)nb + 16)) != 0) return rc;
-    uint8_t* d = (uint8_t*)e->d_fb.p;
-    BgStream* st = reinterpret_cast<BgStream*>(d);
-    const cj::BatchRows r = cj::batch_rows(reinterpret_cast<uint64_t*>(d + tab), (size_t)nb);
-    HIP_TRY(hipMemcpyAsync(st, h_st, n * sizeof(BgStream), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    if (nb) {
+    cj::StreamTable t;
+    int rc = cj::stream_table(turn, e, n, 5, s, [&](cj::StreamRow* d_st) {
+        hipLaunchKernelGGL(cj::bgzf_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap, d_st, nullptr);
+    }, t);
+    if (rc != 0) return rc;
+    const cj::StreamRow* st = t.st;
+    const cj::BatchRows r = cj::batch_rows(t.rows, t.nb);
+    if (t.nb) {
         hipLaunchKernelGGL(cj::bgzf_rows_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_off, st, r);
         cj::BatchArgs a;
         cj::fill_args(a, 0, in_base, out_base, r);
@@ -278,60 +220,30 @@ int bgzf_encode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* 
     // slots inside this one (lock order: cj_engine.hpp).
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
-    const size_t tab = cj::up16(n * sizeof(BgEnc));
-    int rc;
-    if ((rc = turn.reserve(e->h_fb, 16 * n + tab)) != 0) return rc;
-    const uint64_t* h_len = reinterpret_cast<const uint64_t*>(e->h_fb.p);
-    const uint64_t* h_cap = h_len + n;
-    BgEnc* h_enc = reinterpret_cast<BgEnc*>(e->h_fb.p + 16 * n);
-    HIP_TRY(hipMemcpyAsync((void*)h_len, in_len, 8 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipMemcpyAsync((void*)h_cap, out_cap, 8 * n, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
-    HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);
-    const uint64_t per = std::max<uint64_t>(1, g_slot_budget.load() / cj::kSlotStride);      // members per turn
-    uint64_t nb = 0;
     bool second = false;
-    for (size_t i = 0; i < n; i++) {
-        BgEnc x = {};
-        x.piece0 = nb;
-        if (h_len[i] > 0x7E000000ull) x.err = CJ_E_INPUT_TOO_LARGE;
-        else x.npiece = (uint32_t)((h_len[i] + cj::kBgzfPiece - 1) / cj::kBgzfPiece);
-        nb += x.npiece;
-        if (x.npiece && h_cap[i] < cj::bgzf_bound(h_len[i])) x.mode = x.piece0 / per == (nb - 1) / per ? 1u : 2u;
+    cj::EncPlan<BgEnc> p;
+    int rc = cj::enc_plan(turn, e, n, in_len, out_cap, cj::kSlotStride, g_slot_budget, 0, s, [&](BgEnc& x, uint64_t len, uint64_t cap, uint64_t per) {
+        if (len > 0x7E000000ull) x.err = CJ_E_INPUT_TOO_LARGE;
+        else x.npiece = (uint32_t)((len + cj::kBgzfPiece - 1) / cj::kBgzfPiece);
+        if (x.npiece && cap < cj::bgzf_bound(len)) x.mode = x.piece0 / per == (x.piece0 + x.npiece - 1) / per ? 1u : 2u;
         second = second || x.mode == 2u;
-        h_enc[i] = x;
-    }
-    if (nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
-    const size_t m = (size_t)std::min(nb, per);
-    // d_fb: streams | piece rows | member offsets | owners | slots
-    const size_t o_rows = tab, o_moff = o_rows + 5 * 8 * m, o_own = o_moff + 8 * m, o_slots = cj::up16(o_own + 4 * m);
-    if ((rc = turn.reserve(e->d_fb, o_slots + m * (size_t)cj::kSlotStride + 16)) != 0) return rc;
-    uint8_t* d = (uint8_t*)e->d_fb.p;
-    BgEnc* enc = reinterpret_cast<BgEnc*>(d);
-    const cj::BatchRows r = cj::batch_rows(reinterpret_cast<uint64_t*>(d + o_rows), m);
-    uint64_t* moff = reinterpret_cast<uint64_t*>(d + o_moff);
-    uint32_t* owner = reinterpret_cast<uint32_t*>(d + o_own);
-    uint8_t* slots = d + o_slots;
-    HIP_TRY(hipMemcpyAsync(enc, h_enc, n * sizeof(BgEnc), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
-    hipLaunchKernelGGL(cj::bgzf_empty_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, enc, out_base, out_off, out_cap, result);
-    // the stream of piece g, as bgzf_piece_rows_kernel finds it
-    const auto stream_of = [&](uint64_t g) {
-        return (size_t)(std::upper_bound(h_enc, h_enc + n, g, [](uint64_t v, const BgEnc& x) { return v < x.piece0; }) - h_enc) - 1;
-    };
+    }, p);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(cj::bgzf_empty_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, p.enc, out_base, out_off, out_cap, result);
+    // the second pass skips the turns that hold no mode-2 stream
     for (uint32_t pass = 0; pass < (second ? 2u : 1u); pass++) {
-        for (uint64_t t0 = 0; t0 < nb; t0 += per) {
-            const uint32_t cnt = (uint32_t)std::min(per, nb - t0);
-            const size_t sa = stream_of(t0), sb = stream_of(t0 + cnt - 1);
-            if (pass != 0 && std::none_of(h_enc + sa, h_enc + sb + 1, [](const BgEnc& x) { return x.mode == 2u; })) continue;
-            hipLaunchKernelGGL(cj::bgzf_piece_rows_kernel, lane_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, (uint32_t)n, enc, in_off, in_len, r, owner,
-                               (uint64_t)cj::kSlotStride);
+        const auto skip = [&](const BgEnc* a, const BgEnc* b) { return pass != 0 && std::none_of(a, b, [](const BgEnc& x) { return x.mode == 2u; }); };
+        rc = cj::for_turns(p, in_off, in_len, cj::kBgzfPiece, s, skip, [&](uint64_t t0, uint32_t cnt, uint32_t sa, uint32_t ns) {
             cj::BatchArgs a;
-            cj::fill_args(a, 0, cnt, in_base, r.in_off, r.in_len, slots, r.out_off, r.out_cap, r.result);
-            if ((rc = cj::deflate_compress_device(e, CJ_DEFLATE_GZIP, a, s)) != 0) return rc;
-            hipLaunchKernelGGL(cj::bgzf_layout_kernel, cj::wave_grid(sb - sa + 1), dim3(cj::kBlockThreads), 0, s, t0, cnt, (uint32_t)sa, (uint32_t)(sb - sa + 1),
-                               pass, enc, r.result, moff, out_cap, result);
-            hipLaunchKernelGGL(cj::bgzf_assemble_kernel, cj::wave_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, enc, owner, r.result, moff, slots,
+            cj::fill_args(a, 0, cnt, in_base, p.r.in_off, p.r.in_len, p.slots, p.r.out_off, p.r.out_cap, p.r.result);
+            const int erc = cj::deflate_compress_device(e, CJ_DEFLATE_GZIP, a, s);
+            if (erc != 0) return erc;
+            hipLaunchKernelGGL(cj::bgzf_layout_kernel, cj::wave_grid(ns), dim3(cj::kBlockThreads), 0, s, t0, cnt, sa, ns, pass, p.enc, p.r.result, p.moff, out_cap, result);
+            hipLaunchKernelGGL(cj::bgzf_assemble_kernel, cj::wave_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, p.enc, p.owner, p.r.result, p.moff, p.slots,
                                (uint64_t)cj::kSlotStride, out_base, out_off);
-        }
+            return 0;
+        });
+        if (rc != 0) return rc;
     }
     return turn.done(s);
 }

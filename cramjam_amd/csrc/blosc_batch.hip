@@ -40,9 +40,8 @@ inline int bl_class(uint32_t format) {
 }
 
 constexpr uint32_t kMemcpyPiece = 1u << 20;          // a memcpyed chunk goes through the filter launch as copy rows of this size
-__host__ __device__ inline uint64_t bl_up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
 // room the LZ4 encoder asks for a stream of n bytes (lz4_encode.hip), rounded up to 16
-__host__ __device__ inline uint64_t bl_enc_room(uint32_t n) { return bl_up16((uint64_t)n + n / 255u + 16u); }
+__host__ __device__ inline uint64_t bl_enc_room(uint32_t n) { return up16((uint64_t)n + n / 255u + 16u); }
 __host__ __device__ inline uint32_t bl_block_bytes(uint32_t nbytes, uint32_t blocksize, uint32_t b) {
     const uint32_t at = b * blocksize;
     return nbytes - at < blocksize ? nbytes - at : blocksize;
@@ -222,8 +221,8 @@ namespace {
 using cj::BlChunk;
 using cj::BlCount;
 
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-inline dim3 per_lane(size_t n) { return dim3((uint32_t)((n + cj::kBlockThreads - 1) / cj::kBlockThreads)); }
+using cj::lane_grid;
+using cj::up16;
 
 // flags: any subset of CJ_BLOSC_FLAG_READ_BLOSCLZ / _ZLIB / _ZSTD for reading, 0 for writing (bits 0 and 2 and every higher bit stay reserved)
 constexpr uint32_t kReadFlags = CJ_BLOSC_FLAG_READ_BLOSCLZ | CJ_BLOSC_FLAG_READ_ZLIB | CJ_BLOSC_FLAG_READ_ZSTD;
@@ -267,7 +266,7 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     uint8_t* h_cnt = e->h_fb.p + tab;
     // the one wait: stream and block counts (decompress) / lengths (compress) size the rows, the scratch and the grids
     if (dec) {
-        hipLaunchKernelGGL(cj::bl_walk_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
+        hipLaunchKernelGGL(cj::bl_walk_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
                            (BlCount*)e->d_fb.p, (const BlChunk*)nullptr, cj::BlRows{}, (cj::BloscBlockRow*)nullptr, (uint8_t*)nullptr, rflags);
         HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
         HIP_TRY(hipMemcpyAsync(h_cnt, e->d_fb.p, cnt_bytes, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
@@ -327,7 +326,7 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     uint8_t* packed = d + o_packed;
     HIP_TRY(hipMemcpyAsync(d_tab, h_tab, n * sizeof(BlChunk), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     if (dec) {
-        hipLaunchKernelGGL(cj::bl_walk_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
+        hipLaunchKernelGGL(cj::bl_walk_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
                            (BlCount*)nullptr, (const BlChunk*)d_tab, r, blocks, scratch, rflags);
         const uint32_t flags = maxlen <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : maxlen <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : maxlen > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
         // streams of transposed blocks into the scratch, the others straight into the callers' slots
@@ -339,14 +338,14 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
         }
         cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)ta, s);
         cj::launch_copy_segments(r.cp_src + ta, out_base, r.cp_dst + ta, r.cp_len + ta, nullptr, 0, (uint32_t)td, s);
-        hipLaunchKernelGGL(cj::bl_verdict_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, r, result);
+        hipLaunchKernelGGL(cj::bl_verdict_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, r, result);
         cj::launch_blosc_filter(blocks, nb, tiles, false, result, s);
     } else {
-        hipLaunchKernelGGL(cj::bl_pieces_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, in_base, in_off, *params, r.b, blocks, scratch);
+        hipLaunchKernelGGL(cj::bl_pieces_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, in_base, in_off, *params, r.b, blocks, scratch);
         cj::launch_blosc_filter(blocks, nb, tiles, true, nullptr, s);
         if ((rc = run_rows(e, op, 0, scratch, packed, r.b, 0, sa[0], s)) != 0) return rc;
         if ((rc = run_rows(e, op, 0, in_base, packed, r.b, sa[0], sd[0], s)) != 0) return rc;
-        hipLaunchKernelGGL(cj::bl_assemble_kernel, dim3((uint32_t)((n + cj::kWavesPerBlock - 1) / cj::kWavesPerBlock)), dim3(cj::kBlockThreads), 0, s,
+        hipLaunchKernelGGL(cj::bl_assemble_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s,
                            (uint32_t)n, (const BlChunk*)d_tab, *params, r.b, in_base, in_off, scratch, packed, out_base, out_off, out_cap, result);
     }
     return turn.done(s);
@@ -406,7 +405,7 @@ int cj_blosc_chunk_sizes_device(cj_engine* e, uint32_t flags, size_t n, const ui
                                 int64_t* result, void* hip_stream) {
     if (!flags_ok(flags, true)) return CJ_E_BAD_ARG;
     return cj::device_call(e, n, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
-        hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, result, flags);
+        hipLaunchKernelGGL(cj::bl_sizes_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, result, flags);
         HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
         return 0;
     });
@@ -433,7 +432,7 @@ int cj_blosc_chunk_sizes_host(cj_engine* e, uint32_t flags, size_t n, const uint
     uint64_t* d_rows = (uint64_t*)e->d_meta.p;
     HIP_TRY(hipMemcpyAsync(e->d_in.p, e->h_in.p, 16 * n, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(d_rows, h_rows, 2 * n * 8, hipMemcpyHostToDevice, e->stream), CJ_E_NO_DEVICE);
-    hipLaunchKernelGGL(cj::bl_sizes_kernel, per_lane(n), dim3(cj::kBlockThreads), 0, e->stream, (uint32_t)n, (const uint8_t*)e->d_in.p, d_rows, d_rows + n,
+    hipLaunchKernelGGL(cj::bl_sizes_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, e->stream, (uint32_t)n, (const uint8_t*)e->d_in.p, d_rows, d_rows + n,
                        (int64_t*)(d_rows + 2 * n), flags);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     HIP_TRY(hipMemcpyAsync(result, d_rows + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream), CJ_E_NO_DEVICE);

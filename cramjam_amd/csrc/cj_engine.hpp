@@ -148,7 +148,7 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 // scratches inside it.  A frame batch and a Blosc batch hold their `fb` turn while cj::launch takes `scratch` for their LZ4 / Snappy
 // blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
 // streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
-// members, once per turn of member slots; an ORC batch (orc_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`
+// members, once per turn of member slots (cj_container.hpp: for_turns); an ORC batch (orc_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`
 // (decompress), `deflate_slots` or `zstd_enc_slots` (compress, once per turn of chunk slots).  The inner ones are taken one after another,
 // never one inside another, and no path takes two of the graph's mutexes the other way round; `dict_stage` is taken alone or under `mu` only.  The three
 // slotted scratches (`zstd_slots`, `deflate_slots`, `zstd_enc_slots`) are taken in one place, cj::slot_slices below.  The table
@@ -256,6 +256,9 @@ inline void fill_args(BatchArgs& a, uint32_t flags, const uint8_t* in_base, uint
 // ---- launches of the kernels that give every wavefront (or lane) one chunk ---------------------------------------------------------
 size_t grid_chunks();            // kGridChunks, unless cj_debug_grid_chunks has lowered it (engine.hip)
 inline dim3 wave_grid(size_t n_chunks) { return dim3((unsigned)((n_chunks + kWavesPerBlock - 1) / kWavesPerBlock)); }
+inline dim3 lane_grid(size_t n) { return dim3((unsigned)((n + kBlockThreads - 1) / kBlockThreads)); }
+// the 16-byte step of every table and slot inside a scratch buffer
+__host__ __device__ constexpr uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
 // A batch of n chunks in slices of at most `per`: launch(a) with the BatchArgs of each slice in turn — its rows begin at the slice's
 // first chunk (out_off / out_cap may be null: a size query), the base pointers are the batch's
 template <class F>

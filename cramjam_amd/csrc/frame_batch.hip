@@ -12,7 +12,7 @@ constexpr uint64_t kLz4Stride = 65824;       // LZ4_compressBound(65536) = 65809
 constexpr uint64_t kSnapStride = 76496;      // max_compress_len(65536) = 76490, rounded up to 16
 constexpr uint64_t kPiece = 65536;
 
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+using cj::up16;
 
 int frame_batch(cj_engine* e, cj_format fmt, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {

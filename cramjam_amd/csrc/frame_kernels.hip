@@ -60,8 +60,6 @@ __device__ __forceinline__ void wave_copy64(uint8_t* dst, const uint8_t* src, ui
     for (uint64_t o = 0; o < n; o += (1u << 30)) wave_copy(dst + o, src + o, (uint32_t)(n - o < (1u << 30) ? n - o : (1u << 30)));
 }
 
-__host__ __device__ inline uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
-
 // (lz4_slot_bytes, the scratch of one LZ4 block: frame_grammar.hpp)
 __global__ __launch_bounds__(kBlockThreads) void fb_walk_kernel(int fmt, uint32_t n, const uint8_t* in_base, const uint64_t* in_off,
                                                                 const uint64_t* in_len, uint64_t* cnt, FbFrame* fr, FbRows r,

@@ -1344,17 +1344,26 @@ typedef int (*blosc_host_fn)(cj_engine*, cj_op, uint32_t, size_t, const uint8_t*
 typedef int (*dict_host_fn)(cj_engine*, cj_codec, cj_op, uint32_t, size_t, const uint8_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*, const uint8_t*, size_t);
 // ... and the calls of one direction (cj_deflate_compress_batch_host): no `op` in the argument list
 typedef int (*one_op_host_fn)(cj_engine*, cj_deflate_wrap, uint32_t, size_t, const uint8_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*);
-// The three optional arguments behind fn_addr, at most one of them (None / false = not given): they choose the signature of the native call
+// ... and the calls with one word of their own directly behind flags (cj_orc_batch_host: the block size): `extra` = an integer
+typedef int (*extra_host_fn)(cj_engine*, int, cj_op, uint32_t, uint32_t, size_t, const uint8_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*);
+// The four optional arguments behind fn_addr, at most one of them (None / false = not given): they choose the signature of the native call
 struct HostTail {
     Py_buffer params = {}, dict = {};
-    bool blosc = false, dictionary = false, one_op = false;
+    bool blosc = false, dictionary = false, one_op = false, extra = false;
+    uint32_t word = 0;
     cj_blosc_params p = {};
     ~HostTail() { if (blosc) PyBuffer_Release(&params); if (dictionary) PyBuffer_Release(&dict); }
-    bool parse(PyObject* params_o, PyObject* dict_o, int one_op_) {
+    bool parse(PyObject* params_o, PyObject* dict_o, int one_op_, PyObject* extra_o) {
         one_op = one_op_ != 0;
         if (params_o != Py_None && !(blosc = PyObject_GetBuffer(params_o, &params, PyBUF_CONTIG_RO) == 0)) return false;
         if (dict_o != Py_None && !(dictionary = PyObject_GetBuffer(dict_o, &dict, PyBUF_CONTIG_RO) == 0)) return false;
-        if (blosc + dictionary + one_op > 1) { PyErr_SetString(PyExc_ValueError, "params (Blosc chunks), dictionary (LZ4 blocks) and one_op exclude each other"); return false; }
+        if ((extra = extra_o != Py_None)) {
+            const unsigned long w = PyLong_AsUnsignedLong(extra_o);
+            if (w == (unsigned long)-1 && PyErr_Occurred()) return false;
+            if (w > 0xFFFFFFFFul) { PyErr_SetString(PyExc_OverflowError, "extra must fit 32 bits"); return false; }
+            word = (uint32_t)w;
+        }
+        if (blosc + dictionary + one_op + extra > 1) { PyErr_SetString(PyExc_ValueError, "params (Blosc chunks), dictionary (LZ4 blocks), one_op and extra exclude each other"); return false; }
         if (blosc && params.len != 0 && params.len != (Py_ssize_t)sizeof(cj_blosc_params)) { PyErr_SetString(PyExc_ValueError, "params must be the bytes of a cj_blosc_params"); return false; }
         if (blosc && params.len) std::memcpy(&p, params.buf, sizeof p);
         return true;
@@ -1394,7 +1403,7 @@ struct HostBatch {
     // The native call of every kind, without the GIL.  fn_addr: the entry point in the library the engine handle came from (a tuning
     // variant loaded through CJ_HIP_LIB; 0 = the one this module links) — cj_batch_host or cj_frame_batch_host, which share a
     // signature, with `params` cj_blosc_batch_host (codec is not used), with a dictionary cj_dict_batch_host, with one_op
-    // cj_deflate_compress_batch_host (codec is a cj_deflate_wrap, op is not used).
+    // cj_deflate_compress_batch_host (codec is a cj_deflate_wrap, op is not used), with extra cj_orc_batch_host (codec is an ORC kind).
     int call(unsigned long long handle, unsigned long long fn_addr, int codec, int op, unsigned int flags, const HostTail& t) {
         int rc = 0;
         if (n > 0) {
@@ -1410,6 +1419,9 @@ struct HostBatch {
             } else if (t.one_op) {
                 const one_op_host_fn f = fn_addr ? (one_op_host_fn)(uintptr_t)fn_addr : &cj_deflate_compress_batch_host;
                 rc = f(e, (cj_deflate_wrap)codec, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
+            } else if (t.extra) {
+                const extra_host_fn f = fn_addr ? (extra_host_fn)(uintptr_t)fn_addr : &cj_orc_batch_host;
+                rc = f(e, codec, (cj_op)op, flags, t.word, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
             } else {
                 const batch_host_fn f = fn_addr ? (batch_host_fn)(uintptr_t)fn_addr : &cj_batch_host;
                 rc = f(e, (cj_codec)codec, (cj_op)op, flags, (size_t)n, in_ptrs.data(), in_lens.data(), out_ptrs.data(), out_caps.data(), res.data());
@@ -1438,10 +1450,10 @@ bool raise_rc(int rc) {
 }
 
 PyObject* root_batch_host(PyObject*, PyObject* args) {
-    unsigned long long handle, fn_addr = 0; int codec, op, one_op = 0; unsigned int flags; PyObject *inputs_o, *caps_o, *params_o = Py_None, *dict_o = Py_None;
+    unsigned long long handle, fn_addr = 0; int codec, op, one_op = 0; unsigned int flags; PyObject *inputs_o, *caps_o, *params_o = Py_None, *dict_o = Py_None, *extra_o = Py_None;
     HostTail tail;
     HostBatch b;
-    if (!PyArg_ParseTuple(args, "KiiIOO|KOOp", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr, &params_o, &dict_o, &one_op) || !tail.parse(params_o, dict_o, one_op) || !b.open(inputs_o, caps_o)) return nullptr;
+    if (!PyArg_ParseTuple(args, "KiiIOO|KOOpO", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &fn_addr, &params_o, &dict_o, &one_op, &extra_o) || !tail.parse(params_o, dict_o, one_op, extra_o) || !b.open(inputs_o, caps_o)) return nullptr;
     PyObject* outs = PyList_New(b.n);
     bool ok = outs != nullptr;
     for (Py_ssize_t i = 0; ok && i < b.n; i++) {
@@ -1474,14 +1486,14 @@ PyObject* root_batch_host(PyObject*, PyObject* args) {
 // batch_host_into(engine_handle, codec, op, flags, inputs, out_caps, out, offsets=None) -> results: the same batch into ONE writable buffer
 // of the caller's (chunk i at out[offsets[i] : offsets[i] + out_caps[i]], back to back when offsets is None) — no object per output
 PyObject* root_batch_host_into(PyObject*, PyObject* args) {
-    unsigned long long handle, fn_addr = 0; int codec, op, one_op = 0; unsigned int flags; PyObject *inputs_o, *caps_o, *out_o, *offs_o = Py_None, *params_o = Py_None, *dict_o = Py_None;
+    unsigned long long handle, fn_addr = 0; int codec, op, one_op = 0; unsigned int flags; PyObject *inputs_o, *caps_o, *out_o, *offs_o = Py_None, *params_o = Py_None, *dict_o = Py_None, *extra_o = Py_None;
     HostTail tail;
     HostBatch b;
     struct Out {
         Py_buffer view = {}; PyObject* offs = nullptr;
         ~Out() { if (view.obj) PyBuffer_Release(&view); Py_XDECREF(offs); }
     } out;
-    if (!PyArg_ParseTuple(args, "KiiIOOO|OKOOp", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &out_o, &offs_o, &fn_addr, &params_o, &dict_o, &one_op) || !tail.parse(params_o, dict_o, one_op)) return nullptr;
+    if (!PyArg_ParseTuple(args, "KiiIOOO|OKOOpO", &handle, &codec, &op, &flags, &inputs_o, &caps_o, &out_o, &offs_o, &fn_addr, &params_o, &dict_o, &one_op, &extra_o) || !tail.parse(params_o, dict_o, one_op, extra_o)) return nullptr;
     if (PyObject_GetBuffer(out_o, &out.view, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
     if (out.view.readonly) { PyErr_SetString(PyExc_ValueError, "out must be a writable buffer"); return nullptr; }
     if (!b.open(inputs_o, caps_o)) return nullptr;
@@ -1505,8 +1517,8 @@ PyObject* root_batch_host_into(PyObject*, PyObject* args) {
 }
 
 PyMethodDef root_methods[] = {
-    {"batch_host_into", (PyCFunction)Guarded<root_batch_host_into>::call, METH_VARARGS, "batch_host_into(engine_handle, codec, op, flags, inputs, out_caps, out, offsets=None, fn_addr=0, params=None, dictionary=None, one_op=False) -> results"},
-    {"batch_host", (PyCFunction)Guarded<root_batch_host>::call, METH_VARARGS, "batch_host(engine_handle, codec, op, flags, inputs, out_caps, fn_addr=0, params=None, dictionary=None, one_op=False) -> (results, outputs)"},
+    {"batch_host_into", (PyCFunction)Guarded<root_batch_host_into>::call, METH_VARARGS, "batch_host_into(engine_handle, codec, op, flags, inputs, out_caps, out, offsets=None, fn_addr=0, params=None, dictionary=None, one_op=False, extra=None) -> results"},
+    {"batch_host", (PyCFunction)Guarded<root_batch_host>::call, METH_VARARGS, "batch_host(engine_handle, codec, op, flags, inputs, out_caps, fn_addr=0, params=None, dictionary=None, one_op=False, extra=None) -> (results, outputs)"},
     {nullptr, nullptr, 0, nullptr}};
 
 PyModuleDef lz4_def = {PyModuleDef_HEAD_INIT, "cramjam_amd.lz4", "LZ4 block de/compression on MI355X", -1, lz4_methods};

@@ -7,7 +7,7 @@ batches, which the BGZF path launches unchanged.  Encode: one buffer of 16 384 x
 encoder against cj_deflate_compress_batch_device (gzip) over the same buffer as ONE chunk (one workgroup; timed on a prefix when a
 full run would take minutes: the line says so) and over the same 65 280-byte pieces as a batch.
 The kernels' own times (the walk passes bgzf_count_kernel / bgzf_rows_kernel, the assembly bgzf_layout_kernel / bgzf_assemble_kernel /
-bgzf_piece_rows_kernel) come from a kernel trace of a --quick run: rocprofv3 --kernel-trace --stats -- python tests/perf/bgzf_rates.py --quick"""
+piece_rows_kernel<BgEnc>) come from a kernel trace of a --quick run: rocprofv3 --kernel-trace --stats -- python tests/perf/bgzf_rates.py --quick"""
 import json
 import os
 import statistics

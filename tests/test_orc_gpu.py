@@ -242,6 +242,11 @@ def test_encode(eng, codec, bs):
     back, raw = batch.orc_decompress_streams(outs, codec, bs)
     assert list(back) == [len(b) for b in bufs] and [bytes(x) for x in raw] == bufs
     assert batch.orc_stream_sizes(outs, codec, bs) == [len(b) for b in bufs]
+    # two shards, both on engine 0, give the single-engine result
+    res2, outs2 = batch.orc_compress_streams(bufs, codec, bs, devices=[0, 0])
+    assert list(res2) == list(res) and [bytes(o) for o in outs2] == outs
+    back2, raw2 = batch.orc_decompress_streams(outs, codec, bs, devices=[0, 0])
+    assert list(back2) == list(back) and [bytes(x) for x in raw2] == bufs
     # the device entry in the harness: the bound suffices, one byte less is refused with nothing written
     bound = [batch.orc_compress_bound(len(b), bs) for b in bufs]
     kind, n = M.KINDS[codec], len(bufs)
@@ -270,6 +275,44 @@ def test_encode(eng, codec, bs):
     buf = bytearray(b"\xa5" * (sum(bound) + 16))
     res4, views = batch.orc_compress_streams(bufs, codec, bs, out=buf)
     assert list(res4) == list(res) and [bytes(v) for v in views] == outs and bytes(buf[sum(bound):]) == b"\xa5" * 16
+
+
+@pytest.mark.parametrize("codec", ("zlib", "lz4"))
+def test_streams_across_turns_through_the_device_entry(eng, codec):
+    """Two chunk slots a turn, and streams without a piece — empty ones, refused ones — at and next to the turn edges: pieces 0 | 1 2 3 |
+    4 5 6 7 | 8 9 of streams 1, 4, 6 and 8 go through the turns (0 1)(2 3)(4 5)(6 7)(8 9), so the piece-less streams 2, 3 share piece 1
+    with stream 4, stream 5 shares piece 4 — a turn's first — with stream 6, and stream 7 piece 8 with stream 8.  The bytes are those
+    of the host call with the default budget, one turn."""
+    from cramjam_amd import batch
+    e, N = eng
+    L, bs = N.lib(), 4096
+    text = D.words(3 * bs, 83)
+    rnd = np.random.default_rng(12).integers(0, 256, 3 * bs + 5, dtype=np.uint8).tobytes()
+    bufs = [b"", b"x", text[:2 * bs + 100], b"", text[100:3 * bs], text[:100], rnd, b"", text[7:bs + 8]]
+    refused = (2, 5)
+    assert [-(-len(b) // bs) for b in bufs] == [0, 1, 3, 0, 3, 1, 4, 0, 2]
+    res, outs = batch.orc_compress_streams(bufs, codec, bs)
+    outs = [bytes(o) for o in outs]
+    for i, (b, r, s) in enumerate(zip(bufs, res, outs)):
+        assert r == len(s), (i, r)
+        M.check_encoded(s, b, bs, codec, random_input=i == 6)
+    bound = [batch.orc_compress_bound(len(b), bs) for b in bufs]
+    caps = [c - 1 if i in refused else c for i, c in enumerate(bound)]
+    kind, n = M.KINDS[codec], len(bufs)
+    call = lambda i, o, l, out, oo, oc, r: N.check(L.cj_orc_batch_device(e.h, kind, N.OP_COMPRESS, 0, bs, n, i, o, l, out, oo, oc, r, None))
+    budget = 2 * slot_stride(L, N, codec, bs)
+    prev = L.cj_debug_orc_slot_budget(budget)
+    try:
+        got, out, ooff = DB.run_chunks(e, call, bufs, caps, out_mis=DB.out_mis)
+    finally:
+        assert L.cj_debug_orc_slot_budget(prev) == budget
+    for i, s in enumerate(outs):
+        if i in refused:
+            assert got[i] == M.OUT_TOO_SMALL and (out[ooff[i]:ooff[i] + caps[i]] == DB.FILL).all(), (i, int(got[i]))
+        else:
+            assert got[i] == len(s) and out[ooff[i]:ooff[i] + len(s)].tobytes() == s, (i, int(got[i]))
+            assert (out[ooff[i] + len(s):ooff[i] + caps[i]] == DB.FILL).all(), i
+    assert DB.guards_intact(out, ooff, caps) is None
 
 
 def test_device_entries_on_torch_tensors():
