@@ -24,7 +24,10 @@ E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
 E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
 E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -50, -51, -52, -53, -54
 E_ORC_HEADER, E_ORC_BLOCK = -60, -61
+E_PARQUET_HEADER, E_PARQUET_SIZE, E_PARQUET_CRC = -70, -71, -72
 ORC_ZLIB, ORC_SNAPPY, ORC_LZ4, ORC_ZSTD = 1, 2, 4, 5      # ORC's CompressionKind (cj_orc_batch_*)
+PARQUET_UNCOMPRESSED, PARQUET_SNAPPY, PARQUET_GZIP, PARQUET_ZSTD, PARQUET_LZ4_RAW = 0, 1, 2, 6, 7      # Parquet's CompressionCodec (cj_parquet_batch_*)
+PARQUET_FLAG_VERIFY_CRC = 1        # cj_parquet_batch_*: check the CRC-32 of every page that carries one
 ZSTD_FRAMES = 0                    # cj_zstd_format (cj_zstd_batch_*)
 ZSTD_FLAG_CHECKSUM = 1             # cj_zstd_compress_batch_*: a Content_Checksum behind the last block
 BLOSC_FLAG_READ_BLOSCLZ = 2        # cj_blosc_batch_* (decompress) / cj_blosc_chunk_sizes_*: also read chunks whose streams are BloscLZ
@@ -107,6 +110,12 @@ SYMBOLS = {
     "cj_orc_sizes_device": (_int, [_vp, _int, _u32, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_orc_sizes_host": (_int, [_vp, _int, _u32, _u32, _sz, _vp, _vp, _vp]),
     "cj_orc_compress_bound": (_sz, [_sz, _u32]),
+    "cj_parquet_batch_device": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_batch_host": (_int, [_vp, _int, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_sizes_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
+    "cj_parquet_pages_device": (_int, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_pages_host": (_int, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_bound": (_sz, [_sz, _u32]),
@@ -235,8 +244,9 @@ ZSTD = Kind("cj_zstd_batch_host", "cj_zstd_batch_device", "cj_zstd_batch_sizes_h
 ZSTD_COMPRESS = Kind("cj_zstd_compress_batch_host", "cj_zstd_compress_batch_device", None, None, one_op=True)      # what = ZSTD_FRAMES; no size query
 BGZF = Kind("cj_bgzf_batch_host", "cj_bgzf_batch_device", "cj_bgzf_sizes_host", "cj_bgzf_sizes_device")   # what = 0; both directions
 ORC = Kind("cj_orc_batch_host", "cj_orc_batch_device", "cj_orc_sizes_host", "cj_orc_sizes_device", extra=True)   # what = an ORC_*; extra = block_size
+PARQUET = Kind("cj_parquet_batch_host", "cj_parquet_batch_device", "cj_parquet_sizes_host", "cj_parquet_sizes_device")   # what = a PARQUET_*; decode only; flags: PARQUET_FLAG_VERIFY_CRC.  The pages query (cj_parquet_pages_*) has a call shape of its own: batch.parquet_pages
 BLOSC = Kind("cj_blosc_batch_host", "cj_blosc_batch_device", "cj_blosc_chunk_sizes_host", "cj_blosc_chunk_sizes_device", blosc=True)
-_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BGZF, ORC, BLOSC)}
+_HOST_KINDS = {k.host: k for k in (BLOCKS, FRAMES, DICT, DEFLATE, DEFLATE_COMPRESS, ZSTD, ZSTD_COMPRESS, BGZF, ORC, PARQUET, BLOSC)}
 
 
 class Engine:

@@ -37,7 +37,7 @@ def _pick(seq, idx):
 
 def _run(what, op, flags, inputs, out_caps, devices, out=None, kind=N.BLOCKS, params=None, extra=None):
     """kind: N.BLOCKS (what = a CODEC_*), N.FRAMES (a FORMAT_*), N.BLOSC (params: the bytes of a cj_blosc_params, b"" = decompress),
-    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*), N.ZSTD / N.ZSTD_COMPRESS (what = ZSTD_FRAMES), N.BGZF (what = 0) or N.ORC (what = an ORC_*, extra: the block size).
+    N.DICT (what = CODEC_LZ4_BLOCK, params: the dictionary, any bytes-like, borrowed) or N.DEFLATE / N.DEFLATE_COMPRESS (what = a DEFLATE_*), N.ZSTD / N.ZSTD_COMPRESS (what = ZSTD_FRAMES), N.BGZF (what = 0), N.ORC (what = an ORC_*, extra: the block size) or N.PARQUET (what = a PARQUET_*).
     out: results + memoryviews into it (one writable buffer, chunk i behind chunk i - 1's capacity): no object per output"""
     n = len(inputs)
     tail = {"dictionary": params} if kind is N.DICT else {"extra": extra} if kind.extra else {"params": params}
@@ -789,3 +789,98 @@ def orc_compress_streams_device(inp, in_off, in_len, out, out_off, out_cap, code
     """Compress a device-resident batch into ORC compression streams (arguments as lz4_compress_frames_device; the call waits for the
     stream once, for the buffers' lengths and capacities); out_cap[i] must be at least orc_compress_bound(in_len[i], block_size)."""
     return _device_batch(N.ORC, _orc_kind(codec), N.OP_COMPRESS, 0, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync, extra=block_size)
+
+
+# ---- Parquet column chunks (cj_parquet_batch_* / cj_parquet_sizes_* / cj_parquet_pages_*; DESIGN.md 5.18): decode only ------------------
+# One entry is a column chunk as it lies in the file: total_compressed_size bytes from dictionary_page_offset (data_page_offset where
+# there is no dictionary page) — pages behind Thrift compact headers, each the codec's output or, for a V2 page, its levels and the
+# codec's output for the values.  result[i] = the decoded length or a negative CJ_E_* code: -70 from the walk over the headers, then -6
+# when the pages' stated sizes' sum exceeds the capacity, then the first page's code in page order (-72 a CRC mismatch, the decoder's
+# code, -71 a page that decodes to less than it states).  The footer's total_uncompressed_size counts the header bytes too: it is an
+# upper bound on the decoded length and always suffices as a capacity.
+_PARQUET_CODEC = {"uncompressed": N.PARQUET_UNCOMPRESSED, "snappy": N.PARQUET_SNAPPY, "gzip": N.PARQUET_GZIP, "zstd": N.PARQUET_ZSTD, "lz4_raw": N.PARQUET_LZ4_RAW}
+
+
+def _parquet_codec(codec):
+    try:
+        return _PARQUET_CODEC[codec]
+    except (KeyError, TypeError):
+        raise ValueError("codec must be 'uncompressed', 'snappy', 'gzip', 'zstd' or 'lz4_raw', not %r" % (codec,)) from None
+
+
+def parquet_chunk_sizes(chunks, codec, devices=None):
+    """decoded sizes of many Parquet column chunks held on the host (list of ints; negative = CJ_E_* code): the sum of the pages'
+    uncompressed_page_size from the walk over the headers alone — claims, verified only by the decode.  The footer's
+    total_uncompressed_size is this sum plus the header bytes, so it always suffices as a capacity."""
+    return _host_sizes(N.PARQUET, _parquet_codec(codec), 0, chunks, devices)
+
+
+def parquet_decompress_chunks(chunks, codec, output_lens=None, verify_crc=False, devices=None, out=None):
+    """decode many Parquet column chunks, page-parallel; returns (results, outputs) as lz4_decompress_blocks.  codec: "uncompressed",
+    "snappy", "gzip", "zstd" or "lz4_raw" (the column's CompressionCodec); an output is the pages' decoded bytes one after another
+    (parquet_pages says where each begins).  verify_crc: check the CRC-32 of every page whose header carries one.
+    output_lens=None: the sizes are asked for first (parquet_chunk_sizes; the input then crosses the link twice): a chunk the walk
+    rejects gets the walk's code as its result and an empty output.  The footer's total_uncompressed_size is an upper bound on the
+    decoded length: it always suffices as an output_len."""
+    what, flags = _parquet_codec(codec), N.PARQUET_FLAG_VERIFY_CRC if verify_crc else 0
+    run = lambda caps: _run(what, N.OP_DECOMPRESS, flags, chunks, caps, devices, out, N.PARQUET)
+    if output_lens is not None:
+        return run(output_lens)
+    return _sizes_first(parquet_chunk_sizes(chunks, codec, devices), run)
+
+
+def parquet_pages(chunks, devices=None):
+    """the page tables of many Parquet column chunks held on the host: per chunk a (pages, 8) int64 array, or the walk's negative CJ_E_*
+    code.  A row: page type; payload offset in the chunk; compressed_page_size; uncompressed_page_size; offset in the decoded chunk;
+    num_values | num_rows << 32; encoding | def-level encoding << 8 | rep-level encoding << 16 | is_compressed << 24 | has_crc << 25;
+    definition_levels_byte_length | repetition_levels_byte_length << 32."""
+    import numpy as np
+
+    def work(dev, idx):
+        arrs = [np.frombuffer(chunks[i], dtype=np.uint8) for i in idx]          # borrowed, not copied
+        k, L, h = len(arrs), N.lib(), _engine(dev).h
+        ptrs = (_C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        lens = (_C.c_size_t * max(k, 1))(*[a.size for a in arrs])
+        cnt = np.empty(k, np.int64)
+        N.check(L.cj_parquet_pages_host(h, 0, k, ptrs, lens, None, None, cnt.ctypes.data))
+        tabs = [np.empty((max(int(c), 0), 8), np.int64) for c in cnt]
+        rows = (_C.c_void_p * max(k, 1))(*[t.ctypes.data for t in tabs])
+        caps = (_C.c_size_t * max(k, 1))(*[len(t) for t in tabs])
+        res = np.empty(k, np.int64)
+        N.check(L.cj_parquet_pages_host(h, 0, k, ptrs, lens, rows, caps, res.ctypes.data))
+        return ([t if r >= 0 else int(r) for t, r in zip(tabs, res)],)
+    return _shard(devices, len(chunks), work)[0]
+
+
+def parquet_decompress_chunks_device(inp, in_off, in_len, out, out_off, out_cap, codec, verify_crc=False, result=None, device=None, stream=None, sync=True):
+    """Decode a device-resident batch of Parquet column chunks (arguments as lz4_decompress_frames_device; the call waits for the
+    stream once, for the chunks' page counts)."""
+    flags = N.PARQUET_FLAG_VERIFY_CRC if verify_crc else 0
+    return _device_batch(N.PARQUET, _parquet_codec(codec), N.OP_DECOMPRESS, flags, inp, in_off, in_len, out, out_off, out_cap, result, device, stream, sync)
+
+
+def parquet_chunk_sizes_device(inp, in_off, in_len, codec, result=None, device=None, stream=None, sync=True):
+    """Decoded sizes of a device-resident batch of Parquet column chunks, as parquet_chunk_sizes; enqueue-only like lz4_block_sizes_device."""
+    return _device_sizes(N.PARQUET, _parquet_codec(codec), 0, inp, in_off, in_len, result, device, stream, sync)
+
+
+def parquet_pages_device(inp, in_off, in_len, rows=None, row_off=None, row_cap=None, result=None, device=None, stream=None, sync=True):
+    """The page tables of a device-resident batch of Parquet column chunks.  rows=None: result[i] = chunk i's page count (or the walk's
+    code).  Otherwise rows is a device buffer of 64-bit integers: chunk i's pages are written, eight words each as in parquet_pages, at
+    rows[8 * row_off[i]:], row_cap[i] pages at most (more: -6, nothing written), and result[i] is the page count.  Enqueue-only with
+    device-resident metadata, a result tensor and sync=False."""
+    call = _DeviceCall(stream, sync)
+    try:
+        vin = call.buffer(inp)
+        vrows = call.buffer(rows) if rows is not None else None
+        eng = call.engine(device, vin)
+        if vrows is not None and vrows.itemsize != 8:
+            raise TypeError("cramjam_amd.batch: rows must hold 64-bit integers")
+        p_in_off, p_in_len = call.meta(in_off, "in_off"), call.meta(in_len, "in_len")
+        p_off = call.meta(row_off, "row_off") if vrows is not None else None
+        p_cap = call.meta(row_cap, "row_cap") if vrows is not None else None
+        p_res = call.result(result)
+        N.check(N.lib().cj_parquet_pages_device(eng.h, 0, call.n, vin.ptr, p_in_off, p_in_len, vrows.ptr if vrows is not None else None, p_off, p_cap, p_res, stream))
+        return call.finish(p_res, result)
+    finally:
+        call.close()

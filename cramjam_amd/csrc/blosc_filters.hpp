@@ -39,7 +39,7 @@ void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
 // out_off + out_cap (the wave-decoder contract).  0 or CJ_E_*; enqueue only.
 // deflate.hip: deflate_launch for CJ_DEFLATE_ZLIB, not in size mode
 int launch_zlib_decode(const BatchArgs& a, hipStream_t s);
-// ... for CJ_DEFLATE_GZIP: the members of BGZF streams (bgzf_batch.hip), one row each
+// ... for CJ_DEFLATE_GZIP: the members of BGZF streams (bgzf_batch.hip) and the GZIP pages of Parquet chunks (parquet_batch.hip), one row each
 int launch_gzip_decode(const BatchArgs& a, hipStream_t s);
 // ... for CJ_DEFLATE_RAW: the compressed chunks of ORC streams with ZLIB (orc_batch.hip), one row each
 int launch_deflate_raw_decode(const BatchArgs& a, hipStream_t s);

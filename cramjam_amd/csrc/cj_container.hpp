@@ -1,4 +1,4 @@
-// cj_container.hpp — the shell of the container batches whose streams hold many entries each (bgzf_batch.hip, orc_batch.hip; DESIGN.md
+// cj_container.hpp — the shell of the container batches whose streams hold many entries each (bgzf_batch.hip, orc_batch.hip, parquet_batch.hip; DESIGN.md
 // §5.16a): a stream's members / chunks are entries of a batch the engine already runs, so both directions are the same protocol around
 // the format's own kernels.  Decode: a count pass (one lane per stream), ONE read-back and wait, the host's scan of the counts into row0,
 // the rows pass, the codec, a stream-order verdict.  Encode: one read-back and wait for the buffers' lengths and capacities, the pieces
@@ -35,7 +35,7 @@ __device__ __forceinline__ unsigned long long first_failing_row(uint64_t count, 
 
 // Decode: one row per stream.  The count kernel writes total, err and count; row0 is the host's scan of the counts.
 struct StreamRow {
-    uint64_t row0, total;      // first entry row; the decoded length — BGZF: the ISIZE sum, from the count kernel; ORC: 0 until the layout kernel sums the chunks' sizes
+    uint64_t row0, total;      // first entry row; the decoded length — BGZF: the ISIZE sum, Parquet: the pages' stated sizes' sum, from the count kernel; ORC: 0 until the layout kernel sums the chunks' sizes
     int64_t err;               // the walk's error; then BGZF (count kernel): CJ_E_OUT_TOO_SMALL when the ISIZE sum exceeds out_cap; ORC (layout kernel):
                                // a chunk's size error, CJ_E_ORC_BLOCK, CJ_E_OUT_TOO_SMALL
     uint64_t count;            // members / chunks the walk accepts; 0 with an error of the count kernel: such a stream has no rows
@@ -74,8 +74,10 @@ struct StreamTable {
 
 // The prologue, inside the caller's turn at e->fb: count(d_st) launches the format's count kernel into the device table; then the
 // read-back and the call's ONE wait, the scan of the counts into row0, room for the entry rows, and the table's upload.  0 or CJ_E_*.
-template <class Count>
-int stream_table(ScratchTurn& turn, cj_engine* e, size_t n, size_t words, hipStream_t s, Count&& count, StreamTable& t) {
+// seen(row) gets every stream's row as the count kernel left it, before the scan sets its row0: until then that word is the format's
+// (Parquet: the largest decoded page).
+template <class Count, class Seen>
+int stream_table(ScratchTurn& turn, cj_engine* e, size_t n, size_t words, hipStream_t s, Count&& count, StreamTable& t, Seen&& seen) {
     const size_t tab = up16(n * sizeof(StreamRow));
     int rc;
     if ((rc = turn.reserve(e->d_fb, tab)) != 0 || (rc = turn.reserve(e->h_fb, tab)) != 0) return rc;
@@ -85,7 +87,7 @@ int stream_table(ScratchTurn& turn, cj_engine* e, size_t n, size_t words, hipStr
     HIP_TRY(hipMemcpyAsync(h_st, e->d_fb.p, n * sizeof(StreamRow), hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     HIP_TRY(hipStreamSynchronize(s), CJ_E_NO_DEVICE);       // the one wait: the host sizes the entry rows from the streams' counts
     uint64_t nb = 0;
-    for (size_t i = 0; i < n; i++) { h_st[i].row0 = nb; nb += h_st[i].count; }
+    for (size_t i = 0; i < n; i++) { seen(h_st[i]); h_st[i].row0 = nb; nb += h_st[i].count; }
     if (nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
     // No data scratch: the entries decode straight into the callers' slots
     if ((rc = turn.reserve(e->d_fb, tab + words * 8 * (size_t)nb + 16)) != 0) return rc;
@@ -93,6 +95,10 @@ int stream_table(ScratchTurn& turn, cj_engine* e, size_t n, size_t words, hipStr
     t = {reinterpret_cast<StreamRow*>(d), reinterpret_cast<uint64_t*>(d + tab), (size_t)nb};
     HIP_TRY(hipMemcpyAsync(t.st, h_st, n * sizeof(StreamRow), hipMemcpyHostToDevice, s), CJ_E_NO_DEVICE);
     return 0;
+}
+template <class Count>
+int stream_table(ScratchTurn& turn, cj_engine* e, size_t n, size_t words, hipStream_t s, Count&& count, StreamTable& t) {
+    return stream_table(turn, e, n, words, s, count, t, [](const StreamRow&) {});
 }
 
 // ---- host: encode ------------------------------------------------------------------------------------------------------------------------

@@ -149,7 +149,7 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 // blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
 // streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
 // members, once per turn of member slots (cj_container.hpp: for_turns); an ORC batch (orc_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`
-// (decompress), `deflate_slots` or `zstd_enc_slots` (compress, once per turn of chunk slots).  The inner ones are taken one after another,
+// (decompress), `deflate_slots` or `zstd_enc_slots` (compress, once per turn of chunk slots); a Parquet batch (parquet_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`.  The inner ones are taken one after another,
 // never one inside another, and no path takes two of the graph's mutexes the other way round; `dict_stage` is taken alone or under `mu` only.  The three
 // slotted scratches (`zstd_slots`, `deflate_slots`, `zstd_enc_slots`) are taken in one place, cj::slot_slices below.  The table
 // of every entry's turns: DESIGN.md §2; two streams and two threads per scratch: tests/test_scratch_streams_gpu.py.
@@ -174,7 +174,7 @@ struct cj_engine {                 // (members are destroyed last to first: the 
     int big_next = 0;
     cj::DevBuf d_big, d_bigtab;    // large.hip: parse scratch / record tables of one large stream (under `mu`)
     int n_cu = 0;
-    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip, bgzf_batch.hip, orc_batch.hip: batches of framed streams / Blosc chunks / BGZF streams / ORC streams — frame table, block rows and decode slots, its staging
+    cj::Scratch fb;                // frame_batch.hip, blosc_batch.hip, bgzf_batch.hip, orc_batch.hip, parquet_batch.hip: batches of framed streams / Blosc chunks / BGZF streams / ORC streams / Parquet chunks — frame table, block rows and decode slots, its staging
     cj::DevBuf d_fb;
     cj::PinnedBuf h_fb;
     cj::Scratch dict_stage;        // lz4_dict.hip: dictionary compress — the staged `dictionary tail | chunk` slots and their rows

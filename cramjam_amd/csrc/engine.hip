@@ -475,6 +475,9 @@ const char* cj_strerror(int64_t code) {
     case CJ_E_ZSTD_DICT: return "zstd: the frame names a dictionary (libzstd: dictionary_wrong); dictionaries are not supported";
     case CJ_E_ORC_HEADER: return "orc: truncated compression stream (fewer than 3 bytes where a chunk header must stand, or a chunk runs past the stream's end)";
     case CJ_E_ORC_BLOCK: return "orc: a chunk holds more decoded bytes than the compression block size";
+    case CJ_E_PARQUET_HEADER: return "parquet: malformed page header (truncated, a bad varint or wire type, nesting too deep, a required field missing, a bad size, or a payload past the chunk's end)";
+    case CJ_E_PARQUET_SIZE: return "parquet: a page decodes to fewer bytes than its header states";
+    case CJ_E_PARQUET_CRC: return "parquet: page CRC-32 mismatch";
     case CJ_E_NO_DEVICE: return "cramjam_hip: no usable HIP device (no CPU fallback exists)";
     case CJ_E_BAD_ARG: return "cramjam_hip: bad argument";
     case CJ_E_OOM: return "cramjam_hip: out of memory";

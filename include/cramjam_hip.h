@@ -82,6 +82,12 @@ extern "C" {
 #define CJ_E_ORC_HEADER         (-60) /* ORC compression stream: fewer than 3 bytes are left where a chunk header must stand, or a chunk's
                                          length runs past the stream's end */
 #define CJ_E_ORC_BLOCK          (-61) /* ORC compression stream: a chunk, original or compressed, holds more than block_size decoded bytes */
+#define CJ_E_PARQUET_HEADER     (-70) /* Parquet column chunk: the bytes end inside a page header, a varint is longer than 10 bytes, a wire type is
+                                      * unknown or a known field has the wrong one, the nesting of a skipped field is too deep, a required field is
+                                      * missing, a size is negative, a V2 page's level lengths exceed either stated size, or a payload runs past the
+                                      * chunk's end */
+#define CJ_E_PARQUET_SIZE       (-71) /* Parquet column chunk: a page's codec stream decodes cleanly to fewer bytes than its header states */
+#define CJ_E_PARQUET_CRC        (-72) /* Parquet column chunk: a page's CRC-32 (verified on request) does not match its header's */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -526,6 +532,75 @@ CJ_API int cj_orc_sizes_device(cj_engine* e, int what, uint32_t flags, uint32_t 
 CJ_API int cj_orc_sizes_host(cj_engine* e, int what, uint32_t flags, uint32_t block_size, size_t n_streams,
                              const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
 CJ_API size_t cj_orc_compress_bound(size_t n, uint32_t block_size);
+
+/* Batches of Parquet column chunks, decode only: the page walk, the page bodies' codecs and the page CRCs.  One entry
+ * is a column chunk as it lies in the file — total_compressed_size bytes from dictionary_page_offset (data_page_offset where the
+ * chunk has no dictionary page): a run of pages that tile it exactly, each a Thrift compact PageHeader and compressed_page_size bytes.
+ * A DATA_PAGE_V2 puts its repetition and its definition levels, uncompressed, in front of the values; both stated sizes include them,
+ * and the codec applies to the values only, and only if the header's is_compressed (default true) says so.  The decoded chunk is the
+ * pages' decoded bytes one after another (V2: levels, then the decoded values).  Finding the chunks (the footer), and decoding levels
+ * and values (PLAIN, RLE_DICTIONARY, ...), are the reader's.  The footer's total_uncompressed_size counts the header bytes too: it is
+ * an upper bound on the decoded length and always suffices as a capacity.  The argument shape is cj_bgzf_batch_*'s; addressing, the
+ * 16-byte-granule rule, stream rules, e == NULL, n_chunks == 0 and the null-pointer rules are cj_deflate_batch_*'s.
+ *   what        Parquet's CompressionCodec: 0 UNCOMPRESSED (every page is copied), 1 SNAPPY (Snappy raw), 2 GZIP (one gzip member per
+ *               page), 6 ZSTD (one frame), 7 LZ4_RAW (a raw LZ4 block).  Anything else — LZO 3, BROTLI 4, the deprecated
+ *               Hadoop-framed LZ4 5 — is CJ_E_BAD_ARG.
+ *   op          CJ_OP_DECOMPRESS; anything else is CJ_E_BAD_ARG.
+ *   flags       0 or CJ_PARQUET_FLAG_VERIFY_CRC (the batch calls only; sizes and pages take 0); any other bit is CJ_E_BAD_ARG.  These
+ *               checks come first and need no device.
+ *   headers     the compact protocol as parquet_grammar.hpp states it: unknown field ids (Statistics among them) are skipped by their
+ *               type through at most 8 containers inside one another; a known id must have its type; of a known id that appears
+ *               twice the last one counts; an I32 is the low 32 bits of its zigzag varint.  PageHeader: 1 type, 2
+ *               uncompressed_page_size, 3 compressed_page_size (all three required), 4 crc, 5 DataPageHeader (num_values, encoding and
+ *               the two level encodings required), 7 DictionaryPageHeader (num_values, encoding), 8 DataPageHeaderV2 (fields 1 - 6
+ *               required).  Page types 0, 2 and 3 must carry their own struct.  A page of any other type is listed and skipped: it
+ *               adds nothing to the decoded chunk, and its payload is neither decoded nor checksummed.
+ *   decompress  result[i] = the decoded length, the sum of the read pages' uncompressed_page_size, or CJ_E_*.  First the walk over
+ *               the headers: CJ_E_PARQUET_HEADER at the first page that has it.  Then CJ_E_OUT_TOO_SMALL when the sum exceeds
+ *               out_cap[i].  A chunk refused so far is not decoded and its slot is not written.  Every page then decodes (is copied)
+ *               into its own bytes of the slot, behind those of the pages before it; the chunk's result is the code of the first page
+ *               in page order that has one: CJ_E_PARQUET_CRC (with CJ_PARQUET_FLAG_VERIFY_CRC, a page whose header carries a crc:
+ *               the CRC-32, gzip's, of the whole payload as it lies in the file, levels included); else the decoder's code
+ *               (cj_batch_device for Snappy raw and raw LZ4 blocks, cj_deflate_batch_* with CJ_DEFLATE_GZIP, cj_zstd_batch_*, each
+ *               with the stated size of the values as the capacity); else CJ_E_PARQUET_SIZE when the stream ended well with fewer
+ *               bytes than stated.  Decoding is not gated on the CRC.  A values section of 0 bytes that states 0 bytes is accepted
+ *               without asking the codec.  A page that is copied — every page of an UNCOMPRESSED chunk, a V2 page with is_compressed
+ *               false — is not checked for size: min(compressed_page_size, uncompressed_page_size) bytes are copied.  A chunk with a
+ *               bad page may have written inside its own slot, never outside it; one bad chunk never affects another.
+ *   sizes       cj_parquet_sizes_*: the walk alone — result[i] = the sum or CJ_E_PARQUET_HEADER.  The sizes are the headers' claims,
+ *               verified only by the decode.  ENQUEUE-ONLY: no wait, no read-back, no engine scratch.
+ *   pages       cj_parquet_pages_*: the walk's page table, what a device-resident reader needs to make sense of the decoded chunk.
+ *               rows == NULL: result[i] = the page count or CJ_E_PARQUET_HEADER.  Otherwise eight int64 per page are written at
+ *               rows + 8 * row_off[i] (host: at rows_ptrs[i]) and result[i] = the page count; more pages than row_cap[i] is
+ *               CJ_E_OUT_TOO_SMALL, and like a chunk with CJ_E_PARQUET_HEADER it writes nothing.  The words: 0 page type; 1 payload
+ *               offset in the chunk; 2 compressed_page_size; 3 uncompressed_page_size; 4 offset in the decoded chunk (a skipped page
+ *               takes no room there: the next page has the same offset); 5 num_values | num_rows << 32 (num_rows 0 outside V2); 6
+ *               encoding | definition_level_encoding << 8 | repetition_level_encoding << 16 | is_compressed << 24 | has_crc << 25; 7
+ *               definition_levels_byte_length | repetition_levels_byte_length << 32.  flags 0.  ENQUEUE-ONLY like the size query.
+ * cj_parquet_batch_device takes one turn at the engine's container scratch and waits for the stream ONCE, for the chunks' page counts
+ * and largest page (from which it picks CJ_FLAG_CHUNKS_LE_16K / _32K / CJ_FLAG_BIG_CHUNKS for Snappy and LZ4); the headers state every
+ * decoded size, so nothing is walked twice by a codec.  The _host calls are cj_batch_host's one-shot staging, synchronous.
+ * Not read: multi-member gzip pages (CJ_E_DEFLATE_TRAILING), page indexes, bloom filters, encrypted files. */
+#define CJ_PARQUET_FLAG_VERIFY_CRC 1u
+CJ_API int cj_parquet_batch_device(cj_engine* e, int what, cj_op op, uint32_t flags, size_t n_chunks,
+                                   const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                   uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                   int64_t* result, void* hip_stream);
+CJ_API int cj_parquet_batch_host(cj_engine* e, int what, cj_op op, uint32_t flags, size_t n_chunks,
+                                 const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                 uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API int cj_parquet_sizes_device(cj_engine* e, int what, uint32_t flags, size_t n_chunks,
+                                   const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                   int64_t* result, void* hip_stream);
+CJ_API int cj_parquet_sizes_host(cj_engine* e, int what, uint32_t flags, size_t n_chunks,
+                                 const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result);
+CJ_API int cj_parquet_pages_device(cj_engine* e, uint32_t flags, size_t n_chunks,
+                                   const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                   int64_t* rows, const uint64_t* row_off, const uint64_t* row_cap,
+                                   int64_t* result, void* hip_stream);
+CJ_API int cj_parquet_pages_host(cj_engine* e, uint32_t flags, size_t n_chunks,
+                                 const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                 int64_t* const* rows_ptrs, const size_t* row_caps, int64_t* result);
 
 /* Zstandard frames — decode (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
  * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an
