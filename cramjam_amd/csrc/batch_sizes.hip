@@ -7,7 +7,8 @@
 //                              bytes; one wavefront per chunk through the 512-byte register window for longer ones.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock — they may sit in front of a decode on the same
 // stream, or run next to a frame batch that holds the engine's frame scratch.
-#include "blosc_filters.hpp"      // (cj_stage.hpp; declares launch_block_sizes)
+#include "cj_stage.hpp"
+#include "cj_codecs.hpp"
 #include "frame_grammar.hpp"
 #include "lane_stream.hpp"
 #include "lz4_size_walk.hpp"

@@ -5,7 +5,7 @@
 // container around them, in the shell of cj_container.hpp (the count pass, the one read-back, the row scan; the encoder's piece turns):
 // what is BGZF's own is the hop walk (bgzf_grammar.hpp, one lane per stream, in both passes), the member rows, the stream-order verdict
 // (one wavefront per stream), and for the encoder the layout (one wavefront per stream) and the assembly (one wavefront per member).
-#include "blosc_filters.hpp"      // (declares launch_gzip_decode)
+#include "cj_codecs.hpp"
 #include "cj_container.hpp"
 #include "bgzf_grammar.hpp"
 
@@ -180,14 +180,13 @@ __global__ __launch_bounds__(kBlockThreads) void bgzf_assemble_kernel(uint64_t t
 namespace {
 
 using cj::BgEnc;
-using cj::lane_grid;
 
 // bytes of bound-sized member slots per turn of a compress batch at most: 4096 slots
 cj::SlotBudget g_slot_budget{4096ull * cj::kSlotStride};
 
 // enqueue only: pass 1 with the results straight into the caller's row
 int bgzf_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
-    hipLaunchKernelGGL(cj::bgzf_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, nullptr, nullptr, result);
+    hipLaunchKernelGGL(cj::bgzf_count_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, nullptr, nullptr, result);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
@@ -198,17 +197,15 @@ int bgzf_decode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* 
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
     cj::StreamTable t;
-    int rc = cj::stream_table(turn, e, n, 5, s, [&](cj::StreamRow* d_st) {
-        hipLaunchKernelGGL(cj::bgzf_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap, d_st, nullptr);
+    int rc = cj::stream_table(turn, e, n, cj::kBatchRowWords, s, [&](cj::StreamRow* d_st) {
+        hipLaunchKernelGGL(cj::bgzf_count_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap, d_st, nullptr);
     }, t);
     if (rc != 0) return rc;
     const cj::StreamRow* st = t.st;
     const cj::BatchRows r = cj::batch_rows(t.rows, t.nb);
     if (t.nb) {
-        hipLaunchKernelGGL(cj::bgzf_rows_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_off, st, r);
-        cj::BatchArgs a;
-        cj::fill_args(a, 0, in_base, out_base, r);
-        if ((rc = cj::launch_gzip_decode(a, s)) != 0) return rc;
+        hipLaunchKernelGGL(cj::bgzf_rows_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_off, st, r);
+        if ((rc = cj::inner_decode(e, cj::kInGzip, 0, in_base, out_base, r, s)) != 0) return rc;
     }
     hipLaunchKernelGGL(cj::bgzf_verdict_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, st, r.result, result);
     return turn.done(s);
@@ -216,8 +213,7 @@ int bgzf_decode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* 
 
 int bgzf_encode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off,
                 const uint64_t* out_cap, int64_t* result, hipStream_t s) {
-    // The same scratch and the same one wait, for the buffers' lengths and capacities.  The encoder takes its own turn at its record
-    // slots inside this one (lock order: cj_engine.hpp).
+    // The same scratch and the same one wait, for the buffers' lengths and capacities
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
     bool second = false;
@@ -234,9 +230,7 @@ int bgzf_encode(cj_engine* e, size_t n, const uint8_t* in_base, const uint64_t* 
     for (uint32_t pass = 0; pass < (second ? 2u : 1u); pass++) {
         const auto skip = [&](const BgEnc* a, const BgEnc* b) { return pass != 0 && std::none_of(a, b, [](const BgEnc& x) { return x.mode == 2u; }); };
         rc = cj::for_turns(p, in_off, in_len, cj::kBgzfPiece, s, skip, [&](uint64_t t0, uint32_t cnt, uint32_t sa, uint32_t ns) {
-            cj::BatchArgs a;
-            cj::fill_args(a, 0, cnt, in_base, p.r.in_off, p.r.in_len, p.slots, p.r.out_off, p.r.out_cap, p.r.result);
-            const int erc = cj::deflate_compress_device(e, CJ_DEFLATE_GZIP, a, s);
+            const int erc = cj::inner_encode(e, cj::kInGzip, in_base, p.slots, p.r, cnt, s);
             if (erc != 0) return erc;
             hipLaunchKernelGGL(cj::bgzf_layout_kernel, cj::wave_grid(ns), dim3(cj::kBlockThreads), 0, s, t0, cnt, sa, ns, pass, p.enc, p.r.result, p.moff, out_cap, result);
             hipLaunchKernelGGL(cj::bgzf_assemble_kernel, cj::wave_grid(cnt), dim3(cj::kBlockThreads), 0, s, t0, cnt, p.enc, p.owner, p.r.result, p.moff, p.slots,

@@ -13,6 +13,7 @@
 //               words and payloads (or the memcpyed chunk)
 // The grammar is blosc_grammar.hpp's, the transpositions blosc_filters.hip's.
 #include "blosc_filters.hpp"
+#include "cj_codecs.hpp"
 
 namespace cj {
 
@@ -21,23 +22,16 @@ namespace cj {
 struct BlCount { uint32_t nstr, ndir, nblk, nbytes, scratch, maxlen, tiles, format; int64_t err; };   // nblk: filtered blocks (memcpyed: copy pieces); format: kBloscFormat* of the streams
 // one row per chunk: where its streams (scratch / direct), filter blocks and scratch begin (host prefix sums)
 struct BlChunk { uint64_t strm0, dstrm0, blk0, slot0, cslot0; int64_t err; uint32_t nstr, ndir, nblk, nbytes; };
-// the per-stream rows: the engine's batch and the stored streams' copy_segments rows; rows [0, na) are the scratch streams of all
-// chunks, behind them the direct ones; either half is ordered by format — LZ4 | BloscLZ | Zlib | Zstd (bl_class) —, and the streams of
-// a chunk, which all have its one format, lie together
-struct BlRows { BatchRows b; uint64_t *cp_src, *cp_dst, *cp_len; };
-constexpr size_t kBlRowWords = 8;
-inline BlRows bl_rows(uint64_t* base, size_t ns) {
-    BlRows r;
-    r.b = batch_rows(base, ns);
-    r.cp_src = r.b.end; r.cp_dst = r.b.end + ns; r.cp_len = r.b.end + 2 * ns;
-    return r;
-}
+// the per-stream rows are CopyRows (cj_codecs.hpp): the engine's batch and the stored streams' copy_segments rows; rows [0, na) are the
+// scratch streams of all chunks, behind them the direct ones; either half is ordered by format — LZ4 | BloscLZ | Zlib | Zstd
+// (bl_class) —, and the streams of a chunk, which all have its one format, lie together
 
 // the row range of a chunk's streams by its compressor format: 0 LZ4 (and every chunk without streams), 1 BloscLZ, 2 Zlib, 3 Zstd
 constexpr int kBlClasses = 4;
 inline int bl_class(uint32_t format) {
     return format == kBloscFormatBlosclz ? 1 : format == kBloscFormatZlib ? 2 : format == kBloscFormatZstd ? 3 : 0;
 }
+constexpr Inner bl_inner(int cls) { return cls == 1 ? kInBloscLz : cls == 2 ? kInZlib : cls == 3 ? kInZstd : kInLz4Raw; }
 
 constexpr uint32_t kMemcpyPiece = 1u << 20;          // a memcpyed chunk goes through the filter launch as copy rows of this size
 // room the LZ4 encoder asks for a stream of n bytes (lz4_encode.hip), rounded up to 16
@@ -49,7 +43,7 @@ __host__ __device__ inline uint32_t bl_block_bytes(uint32_t nbytes, uint32_t blo
 
 __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
                                                                 uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
-                                                                BlCount* cnt, const BlChunk* tab, BlRows r, BloscBlockRow* blocks, uint8_t* scratch, uint32_t rflags) {
+                                                                BlCount* cnt, const BlChunk* tab, CopyRows r, BloscBlockRow* blocks, uint8_t* scratch, uint32_t rflags) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     const uint8_t* in = in_base + in_off[i];
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(kBlockThreads) void bl_walk_kernel(uint32_t n, cons
 }
 
 // result[i] = nbytes, the walk's error, or CJ_E_CORRUPT when a stream did not decode to exactly its length
-__global__ __launch_bounds__(kBlockThreads) void bl_verdict_kernel(uint32_t n, const BlChunk* tab, BlRows r, int64_t* result) {
+__global__ __launch_bounds__(kBlockThreads) void bl_verdict_kernel(uint32_t n, const BlChunk* tab, CopyRows r, int64_t* result) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     const BlChunk ch = tab[i];
@@ -235,25 +229,6 @@ int params_check(cj_op op, const cj_blosc_params* p) {
     return 0;
 }
 
-// one engine batch over rows [a0, a0 + k) of r
-int run_rows(cj_engine* e, cj_op op, uint32_t flags, const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, size_t a0, size_t k, hipStream_t s) {
-    if (k == 0) return 0;
-    cj::BatchArgs a;
-    cj::fill_args(a, flags, in_base, out_base, r.sub(a0, k));
-    return cj::launch(e, CJ_CODEC_LZ4_BLOCK, op, a, s);
-}
-
-// the streams of one of the other formats (bl_class 1 .. 3) in rows [a0, a0 + k) of r: one wavefront each
-int run_wave_rows(cj_engine* e, int cls, const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, size_t a0, size_t k, hipStream_t s) {
-    if (k == 0) return 0;
-    cj::BatchArgs a;
-    cj::fill_args(a, 0, in_base, out_base, r.sub(a0, k));
-    if (cls == 2) return cj::launch_zlib_decode(a, s);
-    if (cls == 3) return cj::launch_zstd_decode(e, a, s);           // (takes e->zstd_slots inside this call's e->fb turn: cj_engine.hpp)
-    cj::launch_blosclz_decode(a, s);
-    return 0;
-}
-
 int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                 const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, const cj_blosc_params* params, uint32_t rflags, hipStream_t s) {
     cj::ScratchTurn turn(e->fb, s);            // (the frame batches' scratch: chunk batches and frame batches on one engine run one after another)
@@ -267,7 +242,7 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     // the one wait: stream and block counts (decompress) / lengths (compress) size the rows, the scratch and the grids
     if (dec) {
         hipLaunchKernelGGL(cj::bl_walk_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
-                           (BlCount*)e->d_fb.p, (const BlChunk*)nullptr, cj::BlRows{}, (cj::BloscBlockRow*)nullptr, (uint8_t*)nullptr, rflags);
+                           (BlCount*)e->d_fb.p, (const BlChunk*)nullptr, cj::CopyRows{}, (cj::BloscBlockRow*)nullptr, (uint8_t*)nullptr, rflags);
         HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
         HIP_TRY(hipMemcpyAsync(h_cnt, e->d_fb.p, cnt_bytes, hipMemcpyDeviceToHost, s), CJ_E_NO_DEVICE);
     } else {
@@ -315,12 +290,12 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     if (ns > 0xFFFFFFF0ull || nb > 0xFFFFFFF0ull) return CJ_E_BAD_ARG;
     for (size_t i = 0; i < n; i++) { h_tab[i].strm0 += a0[cls(i)]; h_tab[i].dstrm0 += d0[cls(i)]; }
     // d_fb: chunk table | stream rows | block rows | scratch (the filtered images of chunks with transposed blocks) | compressed slots (compress)
-    const size_t o_rows = tab, o_blocks = o_rows + cj::kBlRowWords * 8 * ns, o_scr = up16(o_blocks + nb * sizeof(cj::BloscBlockRow));
+    const size_t o_rows = tab, o_blocks = o_rows + cj::kCopyRowWords * 8 * ns, o_scr = up16(o_blocks + nb * sizeof(cj::BloscBlockRow));
     const size_t o_packed = o_scr + slot + 16;
     if ((rc = turn.reserve(e->d_fb, o_packed + cslot + 16)) != 0) return rc;
     uint8_t* d = (uint8_t*)e->d_fb.p;
     BlChunk* d_tab = reinterpret_cast<BlChunk*>(d);
-    const cj::BlRows r = cj::bl_rows(reinterpret_cast<uint64_t*>(d + o_rows), ns);
+    const cj::CopyRows r = cj::copy_rows(reinterpret_cast<uint64_t*>(d + o_rows), ns);
     cj::BloscBlockRow* blocks = reinterpret_cast<cj::BloscBlockRow*>(d + o_blocks);
     uint8_t* scratch = d + o_scr;
     uint8_t* packed = d + o_packed;
@@ -328,13 +303,10 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     if (dec) {
         hipLaunchKernelGGL(cj::bl_walk_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_base, out_off, out_cap,
                            (BlCount*)nullptr, (const BlChunk*)d_tab, r, blocks, scratch, rflags);
-        const uint32_t flags = maxlen <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : maxlen <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : maxlen > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
-        // streams of transposed blocks into the scratch, the others straight into the callers' slots
-        if ((rc = run_rows(e, op, flags, in_base, scratch, r.b, a0[0], sa[0], s)) != 0) return rc;
-        if ((rc = run_rows(e, op, flags, in_base, out_base, r.b, d0[0], sd[0], s)) != 0) return rc;
-        for (int f = 1; f < cj::kBlClasses; f++) {
-            if ((rc = run_wave_rows(e, f, in_base, scratch, r.b, a0[f], sa[f], s)) != 0) return rc;
-            if ((rc = run_wave_rows(e, f, in_base, out_base, r.b, d0[f], sd[f], s)) != 0) return rc;
+        // format by format: streams of transposed blocks into the scratch, the others straight into the callers' slots
+        for (int f = 0; f < cj::kBlClasses; f++) {
+            if ((rc = cj::inner_decode(e, cj::bl_inner(f), maxlen, in_base, scratch, r.b.sub(a0[f], sa[f]), s)) != 0) return rc;
+            if ((rc = cj::inner_decode(e, cj::bl_inner(f), maxlen, in_base, out_base, r.b.sub(d0[f], sd[f]), s)) != 0) return rc;
         }
         cj::launch_copy_segments(r.cp_src, scratch, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)ta, s);
         cj::launch_copy_segments(r.cp_src + ta, out_base, r.cp_dst + ta, r.cp_len + ta, nullptr, 0, (uint32_t)td, s);
@@ -343,8 +315,8 @@ int blosc_batch(cj_engine* e, cj_op op, size_t n, const uint8_t* in_base, const 
     } else {
         hipLaunchKernelGGL(cj::bl_pieces_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, (const BlChunk*)d_tab, in_base, in_off, *params, r.b, blocks, scratch);
         cj::launch_blosc_filter(blocks, nb, tiles, true, nullptr, s);
-        if ((rc = run_rows(e, op, 0, scratch, packed, r.b, 0, sa[0], s)) != 0) return rc;
-        if ((rc = run_rows(e, op, 0, in_base, packed, r.b, sa[0], sd[0], s)) != 0) return rc;
+        if ((rc = cj::inner_encode(e, cj::kInLz4Raw, scratch, packed, r.b, (uint32_t)sa[0], s)) != 0) return rc;
+        if ((rc = cj::inner_encode(e, cj::kInLz4Raw, in_base, packed, r.b.sub(sa[0], sd[0]), (uint32_t)sd[0], s)) != 0) return rc;
         hipLaunchKernelGGL(cj::bl_assemble_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s,
                            (uint32_t)n, (const BlChunk*)d_tab, *params, r.b, in_base, in_off, scratch, packed, out_base, out_off, out_cap, result);
     }

@@ -29,30 +29,4 @@ CJ_HD inline uint32_t blosc_tiles(uint32_t typesize, uint32_t bytes) {
 // chunk with a negative one are skipped (nullptr: none are).  Enqueue only.
 void launch_blosc_filter(const BloscBlockRow* rows, size_t n_rows, uint32_t tiles_max, bool forward, const int64_t* gate, hipStream_t s);
 
-// blosclz_decode.hip: one wavefront per row of a decodes a BloscLZ stream of in_len bytes into exactly out_cap bytes: result = out_cap or
-// CJ_E_CORRUPT; a row with out_cap == 0 is skipped (result 0).  Nothing is written beyond out_off + out_cap.  Enqueue only.
-void launch_blosclz_decode(const BatchArgs& a, hipStream_t s);
-
-// The streams of Zlib / Zstd chunks (CJ_BLOSC_FLAG_READ_ZLIB / _ZSTD), one wavefront per row of a, by the decoders of the plain batches:
-// result = the decoded length (good iff it is out_cap) or a CJ_E_DEFLATE_* / CJ_E_ZSTD_* code.  A row of a stored stream (in_len and
-// out_cap 0) reads and writes nothing; its result (0 or a code) is not looked at.  Both decoders check every store against
-// out_off + out_cap (the wave-decoder contract).  0 or CJ_E_*; enqueue only.
-// deflate.hip: deflate_launch for CJ_DEFLATE_ZLIB, not in size mode
-int launch_zlib_decode(const BatchArgs& a, hipStream_t s);
-// ... for CJ_DEFLATE_GZIP: the members of BGZF streams (bgzf_batch.hip) and the GZIP pages of Parquet chunks (parquet_batch.hip), one row each
-int launch_gzip_decode(const BatchArgs& a, hipStream_t s);
-// ... for CJ_DEFLATE_RAW: the compressed chunks of ORC streams with ZLIB (orc_batch.hip), one row each
-int launch_deflate_raw_decode(const BatchArgs& a, hipStream_t s);
-// zstd.hip: the decode of cj_zstd_batch_device — its own cj::ScratchTurn on e->zstd_slots, slices by the literal-slot budget
-int launch_zstd_decode(::cj_engine* e, const BatchArgs& a, hipStream_t s);
-
-// The size queries of the plain batches over rows of a container (orc_batch.hip: ORC states no chunk's decoded length): result[i] = the
-// decoded length or the code cj_*_batch_sizes_device gives; a row with in_len 0 reads nothing.  No scratch; 0 or CJ_E_*; enqueue only.
-// deflate.hip: deflate_launch for CJ_DEFLATE_RAW in size mode
-int launch_deflate_raw_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
-// batch_sizes.hip: codec = CJ_CODEC_LZ4_BLOCK (raw blocks: the size walk) or CJ_CODEC_SNAPPY_RAW (the header's length)
-int launch_block_sizes(int codec, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
-// zstd.hip: the decoder without stores
-int launch_zstd_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s);
-
 }  // namespace cj

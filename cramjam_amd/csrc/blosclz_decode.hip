@@ -12,7 +12,7 @@
 // [0, n) of their destination and nothing else, and every length is checked against the capacity before the copy.
 //
 // Shape: as lz4_wave_decode — the grammar is parsed wave-uniformly out of the 512-byte register window, the lanes only move bytes.
-#include "blosc_filters.hpp"
+#include "cj_codecs.hpp"
 #include "blosclz_wave.hpp"
 
 namespace cj {

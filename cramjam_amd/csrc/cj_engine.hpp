@@ -145,11 +145,10 @@ void parallel_chunks(size_t n, size_t total_bytes, F&& fn) {
 }  // namespace cj
 
 // LOCK ORDER of the engine's mutexes: mu -> fb -> {scratch, zstd_slots, deflate_slots, zstd_enc_slots}.  A host batch stages under `mu` and takes the
-// scratches inside it.  A frame batch and a Blosc batch hold their `fb` turn while cj::launch takes `scratch` for their LZ4 / Snappy
-// blocks and streams (decompress); a Blosc batch also while the Zstandard launcher (cj::launch_zstd_decode) takes `zstd_slots` for the
-// streams of Zstd chunks; a BGZF compress batch while the DEFLATE encoder (cj::deflate_compress_device) takes `deflate_slots` for its
-// members, once per turn of member slots (cj_container.hpp: for_turns); an ORC batch (orc_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`
-// (decompress), `deflate_slots` or `zstd_enc_slots` (compress, once per turn of chunk slots); a Parquet batch (parquet_batch.hip) while its codec's launcher takes `scratch` or `zstd_slots`.  The inner ones are taken one after another,
+// scratches inside it.  A frame batch holds its `fb` turn while cj::launch takes `scratch` for its LZ4 / Snappy blocks (decompress).  A
+// container batch (Blosc, BGZF, ORC, Parquet) holds its `fb` turn while cj::inner_decode or cj::inner_encode (cj_codecs.hpp) takes
+// `scratch`, `zstd_slots`, `deflate_slots` or `zstd_enc_slots` for its entries, once per call — the encoders once per turn of slots
+// (cj_container.hpp: for_turns).  The inner ones are taken one after another,
 // never one inside another, and no path takes two of the graph's mutexes the other way round; `dict_stage` is taken alone or under `mu` only.  The three
 // slotted scratches (`zstd_slots`, `deflate_slots`, `zstd_enc_slots`) are taken in one place, cj::slot_slices below.  The table
 // of every entry's turns: DESIGN.md §2; two streams and two threads per scratch: tests/test_scratch_streams_gpu.py.

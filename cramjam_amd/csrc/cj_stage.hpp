@@ -166,10 +166,6 @@ int host_sizes_call(cj_engine* e, size_t n, const uint8_t* const* in_ptrs, const
                       [&](const uint8_t* d_in, uint8_t*, const BatchRows& d, hipStream_t s) { return launch(e, d_in, d, s); });
 }
 
-// deflate_encode.hip: what cj_deflate_compress_batch_device does behind its checks — one stream per chunk, its own turn (cj::slot_slices) on
-// e->deflate_slots, slices by the record-slot budget; enqueue only.  0 or CJ_E_*.
-int deflate_compress_device(cj_engine* e, int wrap, const BatchArgs& b, hipStream_t s);
-
 // The slab decoder's per-workgroup tables (launch_lz4_decode_lds2_slabs) for n_slabs slabs of at most max_rec records, in e->d_bigtab
 int reserve_slab_tabs(cj_engine* e, size_t n_slabs, uint32_t max_rec, SlabTabs& t);
 

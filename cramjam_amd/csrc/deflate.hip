@@ -5,7 +5,8 @@
 // 4 KiB of CRC-32 tables), and the launches.  The size query is the same decoder with stores and checksums compiled out.
 // The device calls only enqueue: no wait, no read-back, no engine scratch, no lock.
 #include "wave_lanes.hpp"
-#include "blosc_filters.hpp"      // (declares launch_zlib_decode, launch_gzip_decode)
+#include "cj_stage.hpp"
+#include "cj_codecs.hpp"
 #include "deflate_wave.hpp"
 
 namespace cj {
@@ -43,9 +44,11 @@ void launch_one(const cj::BatchArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((cj::deflate_kernel<WRAP, SIZE>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a);
 }
 
-// enqueue only; size: the size query (the output rows are null)
-int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
-                   const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
+}  // namespace
+
+// enqueue only; size: the size query (the output rows are null).  The containers' one DEFLATE launch too (cj_codecs.hpp)
+int cj::launch_deflate(int wrap, bool size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+                       const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     cj::for_slices(n, cj::grid_chunks(), 0u, in_base, in_off, in_len, out_base, size ? nullptr : out_off, size ? nullptr : out_cap, result, [&](const cj::BatchArgs& a) {
         switch (wrap * 2 + (size ? 1 : 0)) {
         case 0: launch_one<CJ_DEFLATE_RAW, false>(a, s); break;
@@ -60,35 +63,13 @@ int deflate_launch(int wrap, bool size, size_t n, const uint8_t* in_base, const 
     return 0;
 }
 
-}  // namespace
-
-int cj::launch_zlib_decode(const cj::BatchArgs& a, hipStream_t s) {
-    if (a.n_chunks == 0) return 0;
-    return deflate_launch(CJ_DEFLATE_ZLIB, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
-}
-
-int cj::launch_gzip_decode(const cj::BatchArgs& a, hipStream_t s) {
-    if (a.n_chunks == 0) return 0;
-    return deflate_launch(CJ_DEFLATE_GZIP, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
-}
-
-int cj::launch_deflate_raw_decode(const cj::BatchArgs& a, hipStream_t s) {
-    if (a.n_chunks == 0) return 0;
-    return deflate_launch(CJ_DEFLATE_RAW, false, a.n_chunks, a.in_base, a.in_off, a.in_len, a.out_base, a.out_off, a.out_cap, a.result, s);
-}
-
-int cj::launch_deflate_raw_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
-    if (n == 0) return 0;
-    return deflate_launch(CJ_DEFLATE_RAW, true, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
-}
-
 extern "C" {
 
 int cj_deflate_batch_device(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t flags, size_t n_chunks, const uint8_t* in_base, const uint64_t* in_off,
                             const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, void* hip_stream) {
     if (!cj::deflate_wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
-        return deflate_launch((int)wrap, false, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        return cj::launch_deflate((int)wrap, false, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
     });
 }
 
@@ -97,7 +78,7 @@ int cj_deflate_batch_host(cj_engine* e, cj_deflate_wrap wrap, cj_op op, uint32_t
     if (!cj::deflate_wrap_ok((int)wrap) || op != CJ_OP_DECOMPRESS || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine*, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return deflate_launch((int)wrap, false, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        return cj::launch_deflate((int)wrap, false, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }
 
@@ -105,14 +86,14 @@ int cj_deflate_batch_sizes_device(cj_engine* e, cj_deflate_wrap wrap, uint32_t f
                                   const uint64_t* in_len, int64_t* result, void* hip_stream) {
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
-        return deflate_launch((int)wrap, true, n_chunks, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
+        return cj::launch_deflate((int)wrap, true, n_chunks, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
     });
 }
 
 int cj_deflate_batch_sizes_host(cj_engine* e, cj_deflate_wrap wrap, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
     if (!cj::deflate_wrap_ok((int)wrap) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine*, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
-        return deflate_launch((int)wrap, true, n, d_in, d.in_off, d.in_len, nullptr, nullptr, nullptr, d.result, s);
+        return cj::launch_deflate((int)wrap, true, n, d_in, d.in_off, d.in_len, nullptr, nullptr, nullptr, d.result, s);
     });
 }
 

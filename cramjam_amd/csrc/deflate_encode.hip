@@ -10,6 +10,7 @@
 // in slices of as many streams as there are slots (cj::slot_slices).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
 #include "cj_rec_encode.hpp"
+#include "cj_codecs.hpp"
 #include "crc32_lanes.hpp"
 
 namespace cj {
@@ -117,7 +118,7 @@ int compress_wrap(cj_engine* e, const cj::BatchArgs& b, hipStream_t s) {
 
 // One turn at the engine's record slots (cj::slot_slices); enqueue only.  A slice is what the device holds at once — a launch of more
 // workgroups than that ends in a tail of a few of them (gzip, four per CU, on synth-v1: 25.7 GB/s in slices of 1280, 37.8 in slices of 1024) —
-// within the budget.  (Declared in cj_stage.hpp: the BGZF batch runs its members through it.)
+// within the budget.  (Declared in cj_codecs.hpp: the BGZF and ORC batches run their members and chunks through it.)
 int cj::deflate_compress_device(cj_engine* e, int wrap, const cj::BatchArgs& b, hipStream_t s) {
     if (wrap == CJ_DEFLATE_RAW) return compress_wrap<cj::kDfeRaw>(e, b, s);
     if (wrap == CJ_DEFLATE_ZLIB) return compress_wrap<cj::kDfeZlib>(e, b, s);

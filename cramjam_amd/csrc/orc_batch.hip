@@ -9,26 +9,15 @@
 // the encoder the layout (one wavefront per stream) and the assembly (one wavefront per chunk).
 // NOT enqueue-only, the size query included: every call takes one turn at the engine's container scratch and waits for the stream
 // once (decode, sizes: for the streams' chunk counts; compress: for the buffers' lengths and capacities).
-#include "blosc_filters.hpp"      // (declares the codecs' launchers)
+#include "cj_codecs.hpp"
 #include "cj_container.hpp"
 #include "orc_grammar.hpp"
 
 namespace cj {
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------------
-// The per-chunk rows: the codec's batch (in_base = the streams, out_base = the callers' slots) and the copy_segments rows of the original
-// chunks.  cp_src != 0 marks an original chunk: its codec row is the stored-stream convention's (in_len = out_cap = 0, result not looked at).
-struct OrcRows {
-    BatchRows b;
-    uint64_t *cp_src, *cp_dst, *cp_len;
-};
-constexpr size_t kOrcRowWords = 8;          // u64 rows per chunk
-inline OrcRows orc_rows(uint64_t* base, size_t nb) {
-    OrcRows r;
-    r.b = batch_rows(base, nb);
-    r.cp_src = r.b.end; r.cp_dst = r.b.end + nb; r.cp_len = r.b.end + 2 * nb;
-    return r;
-}
+// The per-chunk rows are CopyRows (cj_codecs.hpp): the codec's batch (in_base = the streams, out_base = the callers' slots) and the
+// copy_segments rows of the original chunks.  cp_src != 0 marks an original chunk.
 
 // Pass 1: the chunk count and the walk's error
 __global__ __launch_bounds__(kBlockThreads) void orc_count_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
@@ -44,7 +33,7 @@ __global__ __launch_bounds__(kBlockThreads) void orc_count_kernel(uint32_t n, co
 // from the same bytes; should they have changed since, a chunk the count does not cover gets no row and a row the walk no longer
 // reaches is an empty compressed one, which no size query accepts.
 __global__ __launch_bounds__(kBlockThreads) void orc_rows_kernel(uint32_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
-                                                                 const StreamRow* st, OrcRows r) {
+                                                                 const StreamRow* st, CopyRows r) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     if (i >= n) return;
     const StreamRow f = st[i];
@@ -65,7 +54,7 @@ __global__ __launch_bounds__(kBlockThreads) void orc_rows_kernel(uint32_t n, con
 // block_size refuses the stream (the codec's code / CJ_E_ORC_BLOCK); then a total above out_cap[i] does (CJ_E_OUT_TOO_SMALL).  A
 // stream that stands gets every row's place in its slot; a refused one has all its rows emptied: it decodes and copies nothing.
 // out_cap == nullptr: the size query — sizes[i] = the total or the error, no row is written.
-__global__ __launch_bounds__(kBlockThreads) void orc_layout_kernel(uint32_t n, StreamRow* st, OrcRows r, uint32_t block_size, const uint64_t* out_off,
+__global__ __launch_bounds__(kBlockThreads) void orc_layout_kernel(uint32_t n, StreamRow* st, CopyRows r, uint32_t block_size, const uint64_t* out_off,
                                                                    const uint64_t* out_cap, int64_t* sizes) {
     const uint32_t i = uni(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
     if (i >= n) return;
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(kBlockThreads) void orc_layout_kernel(uint32_t n, S
 // One wavefront per stream: the walk's or the layout's error first, then the first failing chunk in stream order (the lanes stride
 // over the chunk results, a wave-wide minimum finds it) — a compressed chunk whose decode did not give exactly its laid-out size: the
 // decoder's code, or `short_code`, the codec's "corrupt", where it ended early without one.
-__global__ __launch_bounds__(kBlockThreads) void orc_verdict_kernel(uint32_t n, const StreamRow* st, OrcRows r, int64_t short_code, int64_t* result) {
+__global__ __launch_bounds__(kBlockThreads) void orc_verdict_kernel(uint32_t n, const StreamRow* st, CopyRows r, int64_t short_code, int64_t* result) {
     const uint32_t i = uni(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
     if (i >= n) return;
     const StreamRow f = st[i];
@@ -193,105 +182,56 @@ __global__ __launch_bounds__(kBlockThreads) void orc_assemble_kernel(uint32_t cn
 namespace {
 
 using cj::OrcEnc;
-using cj::lane_grid;
 
 // bytes of bound-sized chunk slots per turn of a compress batch at most: 1024 slots at the largest block size
 cj::SlotBudget g_slot_budget{256ull << 20};
 
-// a piece's bound-sized slot: what the codec's encoder may write for block_size bytes
-uint64_t slot_stride(int kind, uint32_t block_size) {
-    const size_t b = kind == cj::kOrcZlib ? cj_deflate_compress_bound(block_size, CJ_DEFLATE_RAW)
-                   : kind == cj::kOrcSnappy ? cj_snappy_raw_max_compress_len(block_size)
-                   : kind == cj::kOrcLz4 ? cj_lz4_block_compress_bound(block_size, 0)
-                   : cj_zstd_compress_bound(block_size, 0);
-    return cj::up16(b);
-}
-
-// the codec's size query over the compressed rows: its answers into their result row.  Enqueue only
-int sizes_rows(int kind, const uint8_t* in_base, const cj::BatchRows& r, hipStream_t s) {
-    switch (kind) {
-    case cj::kOrcZlib: return cj::launch_deflate_raw_sizes(r.n, in_base, r.in_off, r.in_len, r.result, s);
-    case cj::kOrcSnappy: return cj::launch_block_sizes(CJ_CODEC_SNAPPY_RAW, r.n, in_base, r.in_off, r.in_len, r.result, s);
-    case cj::kOrcLz4: return cj::launch_block_sizes(CJ_CODEC_LZ4_BLOCK, r.n, in_base, r.in_off, r.in_len, r.result, s);
-    default: return cj::launch_zstd_sizes(r.n, in_base, r.in_off, r.in_len, r.result, s);
-    }
-}
-
-// one codec launch over the compressed rows, straight into the callers' slots.  block_size is known here, the chunks' sizes only on
-// the device: the engine's size classes are hints a chunk may break
-int decode_rows(cj_engine* e, int kind, uint32_t block_size, const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, hipStream_t s) {
-    cj::BatchArgs a;
-    if (kind == cj::kOrcLz4 || kind == cj::kOrcSnappy) {
-        const uint32_t flags = block_size <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : block_size <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : block_size > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
-        cj::fill_args(a, flags, in_base, out_base, r);
-        return cj::launch(e, kind == cj::kOrcLz4 ? CJ_CODEC_LZ4_BLOCK : CJ_CODEC_SNAPPY_RAW, CJ_OP_DECOMPRESS, a, s);      // (takes e->scratch inside this call's e->fb turn)
-    }
-    cj::fill_args(a, 0, in_base, out_base, r);
-    if (kind == cj::kOrcZlib) return cj::launch_deflate_raw_decode(a, s);
-    return cj::launch_zstd_decode(e, a, s);                                                                                 // (takes e->zstd_slots inside it)
-}
-
-int64_t short_code(int kind) {
-    return kind == cj::kOrcZlib ? CJ_E_DEFLATE_CORRUPT : kind == cj::kOrcSnappy ? CJ_E_SNAPPY_CORRUPT : kind == cj::kOrcLz4 ? CJ_E_CORRUPT : CJ_E_ZSTD_CORRUPT;
-}
-
 // out_cap == nullptr: the size query — result[i] = the sum of the chunks' sizes or the first error; nothing is decoded
-int orc_decode(cj_engine* e, int kind, uint32_t block_size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+int orc_decode(cj_engine* e, cj::Inner codec, uint32_t block_size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     // One turn at the container batches' scratch, held across the call's one wait (cj_container.hpp)
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
     cj::StreamTable t;
-    int rc = cj::stream_table(turn, e, n, cj::kOrcRowWords, s, [&](cj::StreamRow* d_st) {
-        hipLaunchKernelGGL(cj::orc_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, d_st);
+    int rc = cj::stream_table(turn, e, n, cj::kCopyRowWords, s, [&](cj::StreamRow* d_st) {
+        hipLaunchKernelGGL(cj::orc_count_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, d_st);
     }, t);
     if (rc != 0) return rc;
     // the original chunks are copied, like the others decode, straight into the callers' slots
     cj::StreamRow* st = t.st;
     const size_t nb = t.nb;
-    const cj::OrcRows r = cj::orc_rows(t.rows, nb);
+    const cj::CopyRows r = cj::copy_rows(t.rows, nb);
     if (nb) {
-        hipLaunchKernelGGL(cj::orc_rows_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, st, r);
-        if ((rc = sizes_rows(kind, in_base, r.b, s)) != 0) return rc;
+        hipLaunchKernelGGL(cj::orc_rows_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, st, r);
+        if ((rc = cj::inner_sizes(codec, in_base, r.b, s)) != 0) return rc;
     }
     hipLaunchKernelGGL(cj::orc_layout_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, st, r, block_size, out_off, out_cap, result);
     if (out_cap != nullptr) {
         if (nb) {
-            if ((rc = decode_rows(e, kind, block_size, in_base, out_base, r.b, s)) != 0) return rc;
+            if ((rc = cj::inner_decode(e, codec, block_size, in_base, out_base, r.b, s)) != 0) return rc;
             cj::launch_copy_segments(r.cp_src, out_base, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)nb, s);
         }
-        hipLaunchKernelGGL(cj::orc_verdict_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, st, r, short_code(kind), result);
+        hipLaunchKernelGGL(cj::orc_verdict_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, st, r, cj::inner_short_code(codec), result);
     }
     return turn.done(s);
 }
 
-// the pieces of a turn through the codec's encoder into their slots.  Each takes its own turn at its scratch inside this call's
-// e->fb turn (lock order: cj_engine.hpp)
-int encode_rows(cj_engine* e, int kind, const uint8_t* in_base, uint8_t* slots, const cj::BatchRows& r, uint32_t cnt, hipStream_t s) {
-    if (kind == cj::kOrcZstd)
-        return cj_zstd_compress_batch_device(e, CJ_ZSTD_FRAMES, 0u, cnt, in_base, r.in_off, r.in_len, slots, r.out_off, r.out_cap, r.result, (void*)s);
-    cj::BatchArgs a;
-    cj::fill_args(a, 0, cnt, in_base, r.in_off, r.in_len, slots, r.out_off, r.out_cap, r.result);
-    if (kind == cj::kOrcZlib) return cj::deflate_compress_device(e, CJ_DEFLATE_RAW, a, s);
-    return cj::launch(e, kind == cj::kOrcLz4 ? CJ_CODEC_LZ4_BLOCK : CJ_CODEC_SNAPPY_RAW, CJ_OP_COMPRESS, a, s);
-}
-
-int orc_encode(cj_engine* e, int kind, uint32_t block_size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
+int orc_encode(cj_engine* e, cj::Inner codec, uint32_t block_size, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
                const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, hipStream_t s) {
     // The same scratch and the same one wait, for the buffers' lengths and capacities
     cj::ScratchTurn turn(e->fb, s);
     if (turn.rc != 0) return turn.rc;
     cj::EncPlan<OrcEnc> p;
-    int rc = cj::enc_plan(turn, e, n, in_len, out_cap, slot_stride(kind, block_size), g_slot_budget, 1, s, [&](OrcEnc& x, uint64_t len, uint64_t cap, uint64_t) {
+    int rc = cj::enc_plan(turn, e, n, in_len, out_cap, cj::up16(cj::inner_bound(codec, block_size)), g_slot_budget, 1, s, [&](OrcEnc& x, uint64_t len, uint64_t cap, uint64_t) {
         if (len > 0x7E000000ull) x.err = CJ_E_INPUT_TOO_LARGE;
         else if (cap < cj::orc_bound(len, block_size)) x.err = CJ_E_OUT_TOO_SMALL;      // decided before any store: nothing is written
         else x.npiece = (uint32_t)((len + block_size - 1) / block_size);
     }, p);
     if (rc != 0) return rc;
     uint32_t* pick = p.extra;                   // the chunks' header words
-    hipLaunchKernelGGL(cj::orc_empty_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, p.enc, result);
+    hipLaunchKernelGGL(cj::orc_empty_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, p.enc, result);
     rc = cj::for_turns(p, in_off, in_len, block_size, s, [](const OrcEnc*, const OrcEnc*) { return false; }, [&](uint64_t t0, uint32_t cnt, uint32_t sa, uint32_t ns) {
-        const int erc = encode_rows(e, kind, in_base, p.slots, p.r, cnt, s);
+        const int erc = cj::inner_encode(e, codec, in_base, p.slots, p.r, cnt, s);
         if (erc != 0) return erc;
         hipLaunchKernelGGL(cj::orc_enc_layout_kernel, cj::wave_grid(ns), dim3(cj::kBlockThreads), 0, s, t0, cnt, sa, ns, p.enc, p.r.in_len, p.r.result, p.moff, pick, result);
         hipLaunchKernelGGL(cj::orc_assemble_kernel, cj::wave_grid(cnt), dim3(cj::kBlockThreads), 0, s, cnt, p.owner, pick, p.moff, in_base, p.r.in_off, p.slots, p.stride,
@@ -320,7 +260,7 @@ int cj_orc_batch_device(cj_engine* e, int what, cj_op op, uint32_t flags, uint32
                         const uint64_t* in_len, uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap, int64_t* result, void* hip_stream) {
     if (!orc_args_ok(what, op, flags, block_size)) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_streams, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return (op == CJ_OP_DECOMPRESS ? orc_decode : orc_encode)(e, what, block_size, n_streams, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
+        return (op == CJ_OP_DECOMPRESS ? orc_decode : orc_encode)(e, cj::orc_inner(what), block_size, n_streams, in_base, in_off, in_len, out_base, out_off, out_cap, result, s);
     });
 }
 
@@ -329,7 +269,7 @@ int cj_orc_batch_host(cj_engine* e, int what, cj_op op, uint32_t flags, uint32_t
     if (!orc_args_ok(what, op, flags, block_size)) return CJ_E_BAD_ARG;
     return cj::host_call(e, n, in_ptrs, in_lens, out_ptrs, out_caps, result, -1, false,
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
-        return (op == CJ_OP_DECOMPRESS ? orc_decode : orc_encode)(e, what, block_size, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
+        return (op == CJ_OP_DECOMPRESS ? orc_decode : orc_encode)(e, cj::orc_inner(what), block_size, n, d_in, d.in_off, d.in_len, d_out, d.out_off, d.out_cap, d.result, s);
     });
 }
 
@@ -337,14 +277,14 @@ int cj_orc_sizes_device(cj_engine* e, int what, uint32_t flags, uint32_t block_s
                         const uint64_t* in_len, int64_t* result, void* hip_stream) {
     if (!size_args_ok(what, flags, block_size)) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_streams, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
-        return orc_decode(e, what, block_size, n_streams, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
+        return orc_decode(e, cj::orc_inner(what), block_size, n_streams, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, s);
     });
 }
 
 int cj_orc_sizes_host(cj_engine* e, int what, uint32_t flags, uint32_t block_size, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
     if (!size_args_ok(what, flags, block_size)) return CJ_E_BAD_ARG;
     return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine* e, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
-        return orc_decode(e, what, block_size, n, d_in, d.in_off, d.in_len, nullptr, nullptr, nullptr, d.result, s);
+        return orc_decode(e, cj::orc_inner(what), block_size, n, d_in, d.in_off, d.in_len, nullptr, nullptr, nullptr, d.result, s);
     });
 }
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/cramjam_hip.h"
+#include "cj_codecs.hpp"
 
 #if defined(__HIPCC__)
 #define CJ_HD __host__ __device__
@@ -24,6 +25,8 @@ constexpr uint32_t kOrcEncBlockMax = 262144u;         // the largest block this 
 // PostScript.compression (CompressionKind); LZO (3), BROTLI (6) and NONE (0) are not read
 constexpr int kOrcZlib = 1, kOrcSnappy = 2, kOrcLz4 = 4, kOrcZstd = 5;
 CJ_HD inline bool orc_kind_ok(int kind) { return kind == kOrcZlib || kind == kOrcSnappy || kind == kOrcLz4 || kind == kOrcZstd; }
+// the stream a compressed chunk is (of a kind that orc_kind_ok accepts)
+constexpr Inner orc_inner(int kind) { return kind == kOrcZlib ? kInDeflateRaw : kind == kOrcSnappy ? kInSnappyRaw : kind == kOrcLz4 ? kInLz4Raw : kInZstd; }
 
 // n + 3 * ceil(n / block_size): every piece as an original chunk.  Exact for incompressible input; an empty buffer is an empty stream.
 CJ_HD inline uint64_t orc_bound(uint64_t n, uint64_t block_size) { return n + kOrcHead * ((n + block_size - 1u) / block_size); }

@@ -8,7 +8,7 @@
 // page) and the page-order verdict (one wavefront per chunk).
 // The size query and the pages query are the walk alone and only enqueue.  A decode takes one turn at the engine's container scratch and
 // waits for the stream once, for the chunks' page counts and largest page.
-#include "blosc_filters.hpp"      // (declares the codecs' launchers)
+#include "cj_codecs.hpp"
 #include "cj_container.hpp"
 #include "crc32_lanes.hpp"
 #include "parquet_grammar.hpp"
@@ -22,19 +22,16 @@ __device__ const Crc32Tables d_pq_crc32_tables = make_crc32_tables();
 // The per-page rows: the codec's batch (in_base = the chunks, out_base = the callers' slots: the values sections; a page the codec does
 // not see has the stored-stream convention's row, in_len = out_cap = 0, result not looked at), the copy_segments rows (V2 levels; the
 // whole payload of a page that is copied), the checksummed bytes and the page's word.
-struct PqRows {
-    BatchRows b;
-    uint64_t *cp_src, *cp_dst, *cp_len;
+struct PqRows : CopyRows {
     uint64_t *ck_off, *ck_len;              // the payload, from in_base
     uint64_t* word;                         // the stated crc | kPq* bits << 32
 };
-constexpr size_t kPqRowWords = 11;          // u64 rows per page
+constexpr size_t kPqRowWords = kCopyRowWords + 3;      // u64 rows per page
 constexpr uint64_t kPqCoded = 1ull << 32, kPqHasCrc = 1ull << 33, kPqCrcBad = 1ull << 34;
 inline PqRows pq_rows(uint64_t* base, size_t nb) {
     PqRows r;
-    r.b = batch_rows(base, nb);
-    uint64_t* p = r.b.end;
-    r.cp_src = p; r.cp_dst = p + nb; r.cp_len = p + 2 * nb; r.ck_off = p + 3 * nb; r.ck_len = p + 4 * nb; r.word = p + 5 * nb;
+    static_cast<CopyRows&>(r) = copy_rows(base, nb);
+    r.ck_off = r.cp_len + nb; r.ck_len = r.cp_len + 2 * nb; r.word = r.cp_len + 3 * nb;
     return r;
 }
 
@@ -155,11 +152,9 @@ __global__ __launch_bounds__(kBlockThreads) void pq_pages_kernel(uint32_t n, con
 
 namespace {
 
-using cj::lane_grid;
-
 // enqueue only: pass 1 with the results straight into the caller's row
 int pq_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
-    hipLaunchKernelGGL(cj::pq_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, nullptr, nullptr, result);
+    hipLaunchKernelGGL(cj::pq_count_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, nullptr, nullptr, result);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
 }
@@ -167,23 +162,10 @@ int pq_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uin
 // enqueue only
 int pq_pages(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* tab, const uint64_t* off, const uint64_t* cap,
              uint32_t off_unit, uint32_t cap_div, uint32_t res_unit, int64_t* result, hipStream_t s) {
-    hipLaunchKernelGGL(cj::pq_pages_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, tab, off, cap, off_unit, cap_div,
+    hipLaunchKernelGGL(cj::pq_pages_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, tab, off, cap, off_unit, cap_div,
                        res_unit, result);
     HIP_TRY(hipGetLastError(), CJ_E_NO_DEVICE);
     return 0;
-}
-
-// one codec launch over the coded rows, straight into the callers' slots.  `largest` bounds every row's capacity
-int decode_rows(cj_engine* e, int codec, uint64_t largest, const uint8_t* in_base, uint8_t* out_base, const cj::BatchRows& r, hipStream_t s) {
-    cj::BatchArgs a;
-    if (codec == cj::kPqLz4Raw || codec == cj::kPqSnappy) {
-        const uint32_t flags = largest <= 16384u ? CJ_FLAG_CHUNKS_LE_16K : largest <= 32768u ? CJ_FLAG_CHUNKS_LE_32K : largest > 65536u ? CJ_FLAG_BIG_CHUNKS : 0u;
-        cj::fill_args(a, flags, in_base, out_base, r);
-        return cj::launch(e, codec == cj::kPqLz4Raw ? CJ_CODEC_LZ4_BLOCK : CJ_CODEC_SNAPPY_RAW, CJ_OP_DECOMPRESS, a, s);      // (takes e->scratch inside this call's e->fb turn)
-    }
-    cj::fill_args(a, 0, in_base, out_base, r);
-    if (codec == cj::kPqGzip) return cj::launch_gzip_decode(a, s);
-    return cj::launch_zstd_decode(e, a, s);                                                                                  // (takes e->zstd_slots inside it)
 }
 
 int pq_decode(cj_engine* e, int codec, bool verify, size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, uint8_t* out_base,
@@ -194,14 +176,14 @@ int pq_decode(cj_engine* e, int codec, bool verify, size_t n, const uint8_t* in_
     cj::StreamTable t;
     uint64_t largest = 0;
     int rc = cj::stream_table(turn, e, n, cj::kPqRowWords, s, [&](cj::StreamRow* d_st) {
-        hipLaunchKernelGGL(cj::pq_count_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap, d_st, nullptr);
+        hipLaunchKernelGGL(cj::pq_count_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, in_base, in_off, in_len, out_cap, d_st, nullptr);
     }, t, [&](const cj::StreamRow& f) { largest = std::max(largest, f.row0); });
     if (rc != 0) return rc;
     const cj::PqRows r = cj::pq_rows(t.rows, t.nb);
     if (t.nb) {
-        hipLaunchKernelGGL(cj::pq_rows_kernel, lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, codec, in_base, in_off, in_len, out_off, t.st, r);
+        hipLaunchKernelGGL(cj::pq_rows_kernel, cj::lane_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, codec, in_base, in_off, in_len, out_off, t.st, r);
         if (verify) hipLaunchKernelGGL(cj::pq_crc_kernel, cj::wave_grid(t.nb), dim3(cj::kBlockThreads), 0, s, (uint32_t)t.nb, in_base, r);
-        if (codec != cj::kPqUncompressed && (rc = decode_rows(e, codec, largest, in_base, out_base, r.b, s)) != 0) return rc;
+        if (codec != cj::kPqUncompressed && (rc = cj::inner_decode(e, cj::pq_inner(codec), largest, in_base, out_base, r.b, s)) != 0) return rc;
         cj::launch_copy_segments(r.cp_src, out_base, r.cp_dst, r.cp_len, nullptr, 0, (uint32_t)t.nb, s);
     }
     hipLaunchKernelGGL(cj::pq_verdict_kernel, cj::wave_grid(n), dim3(cj::kBlockThreads), 0, s, (uint32_t)n, t.st, r, result);

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/cramjam_hip.h"
+#include "cj_codecs.hpp"
 
 #if defined(__HIPCC__)
 #define CJ_HD __host__ __device__
@@ -29,6 +30,8 @@ namespace cj {
 // Parquet's CompressionCodec; LZO (3), BROTLI (4) and the deprecated Hadoop-framed LZ4 (5) are not read
 constexpr int kPqUncompressed = 0, kPqSnappy = 1, kPqGzip = 2, kPqZstd = 6, kPqLz4Raw = 7;
 CJ_HD inline bool pq_codec_ok(int c) { return c == kPqUncompressed || c == kPqSnappy || c == kPqGzip || c == kPqZstd || c == kPqLz4Raw; }
+// the stream a coded page is (of a codec that pq_codec_ok accepts, but for kPqUncompressed: no page is coded)
+constexpr Inner pq_inner(int c) { return c == kPqSnappy ? kInSnappyRaw : c == kPqGzip ? kInGzip : c == kPqLz4Raw ? kInLz4Raw : kInZstd; }
 
 // PageType
 constexpr int32_t kPqDataPage = 0, kPqIndexPage = 1, kPqDictPage = 2, kPqDataPageV2 = 3;

@@ -6,9 +6,8 @@
 // the same decoder without stores and uses no scratch.  The device calls only enqueue (a decode that grows the slots waits for their
 // previous user while it reallocates).
 #include "wave_lanes.hpp"
-#include "blosc_filters.hpp"      // (declares launch_zstd_decode)
-
-
+#include "cj_stage.hpp"
+#include "cj_codecs.hpp"
 #include "zstd_wave.hpp"
 
 namespace cj {
@@ -41,8 +40,10 @@ cj::SlotBudget g_slot_budget{4096ull * cj::kZsSlotBytes};
 
 bool fmt_ok(int fmt) { return fmt == CJ_ZSTD_FRAMES; }
 
+}  // namespace
+
 // the size query: enqueue only, no scratch
-int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
+int cj::launch_zstd_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
     cj::for_slices(n, cj::grid_chunks(), 0u, in_base, in_off, in_len, nullptr, nullptr, nullptr, result, [&](const cj::BatchArgs& a) {
         hipLaunchKernelGGL((cj::zstd_kernel<true>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, (uint8_t*)nullptr);
     });
@@ -50,25 +51,13 @@ int sizes_launch(size_t n, const uint8_t* in_base, const uint64_t* in_off, const
     return 0;
 }
 
-// One turn at the engine's literal slots (cj::slot_slices); enqueue only.  A caller may hold the e->fb turn (blosc_batch.hip), never
+// One turn at the engine's literal slots (cj::slot_slices); enqueue only.  A caller may hold the e->fb turn (cj::inner_decode), never
 // the other way round: the lock order is written down where cj_engine declares the scratches
-int decode_device(cj_engine* e, const cj::BatchArgs& b, hipStream_t s) {
+int cj::launch_zstd_decode(cj_engine* e, const cj::BatchArgs& b, hipStream_t s) {
     return cj::slot_slices(e->zstd_slots, e->d_zstd_slots, cj::kZsSlotBytes, g_slot_budget.load(), cj::grid_chunks(), b, s,
                            [&](const cj::BatchArgs& a, uint8_t* slots) {
         hipLaunchKernelGGL((cj::zstd_kernel<false>), cj::wave_grid(a.n_chunks), dim3(cj::kBlockThreads), 0, s, a, slots);
     });
-}
-
-}  // namespace
-
-int cj::launch_zstd_decode(cj_engine* e, const cj::BatchArgs& a, hipStream_t s) {
-    if (a.n_chunks == 0) return 0;
-    return decode_device(e, a, s);
-}
-
-int cj::launch_zstd_sizes(size_t n, const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len, int64_t* result, hipStream_t s) {
-    if (n == 0) return 0;
-    return sizes_launch(n, in_base, in_off, in_len, result, s);
 }
 
 extern "C" {
@@ -79,7 +68,7 @@ int cj_zstd_batch_device(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t fl
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
         cj::BatchArgs a;
         cj::fill_args(a, 0, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
-        return decode_device(e, a, s);
+        return cj::launch_zstd_decode(e, a, s);
     });
 }
 
@@ -90,7 +79,7 @@ int cj_zstd_batch_host(cj_engine* e, cj_zstd_format fmt, cj_op op, uint32_t flag
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         cj::BatchArgs a;
         cj::fill_args(a, 0, d_in, d_out, d);
-        return decode_device(e, a, s);
+        return cj::launch_zstd_decode(e, a, s);
     });
 }
 
@@ -98,14 +87,14 @@ int cj_zstd_batch_sizes_device(cj_engine* e, cj_zstd_format fmt, uint32_t flags,
                                const uint64_t* in_len, int64_t* result, void* hip_stream) {
     if (!fmt_ok((int)fmt) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, result}, hip_stream, [&](cj_engine*, hipStream_t s) {
-        return sizes_launch(n_chunks, in_base, in_off, in_len, result, s);
+        return cj::launch_zstd_sizes(n_chunks, in_base, in_off, in_len, result, s);
     });
 }
 
 int cj_zstd_batch_sizes_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags, size_t n, const uint8_t* const* in_ptrs, const size_t* in_lens, int64_t* result) {
     if (!fmt_ok((int)fmt) || flags != 0u) return CJ_E_BAD_ARG;
     return cj::host_sizes_call(e, n, in_ptrs, in_lens, result, [&](cj_engine*, const uint8_t* d_in, const cj::BatchRows& d, hipStream_t s) {
-        return sizes_launch(n, d_in, d.in_off, d.in_len, d.result, s);
+        return cj::launch_zstd_sizes(n, d_in, d.in_off, d.in_len, d.result, s);
     });
 }
 

@@ -10,6 +10,7 @@
 // in slices of as many frames as there are slots (cj::slot_slices).  The device call only enqueues (a call that grows the scratch
 // waits for its previous user while it reallocates).
 #include "cj_rec_encode.hpp"
+#include "cj_codecs.hpp"
 
 namespace cj {
 
@@ -97,8 +98,13 @@ namespace {
 // would only be memory the engine keeps
 cj::SlotBudget g_slot_budget{1024ull * cj::kZseSlotBytes};
 
+bool args_ok(cj_zstd_format fmt, uint32_t flags) { return fmt == CJ_ZSTD_FRAMES && (flags & ~CJ_ZSTD_FLAG_CHECKSUM) == 0u; }
+
+}  // namespace
+
 // One turn at the engine's slots (cj::slot_slices); enqueue only.  A slice is what the device holds at once, within the budget.
-int compress_device(cj_engine* e, uint32_t flags, const cj::BatchArgs& b, hipStream_t s) {
+// (Declared in cj_codecs.hpp: the ORC batch runs its ZSTD chunks through it.)
+int cj::zstd_compress_device(cj_engine* e, uint32_t flags, const cj::BatchArgs& b, hipStream_t s) {
     constexpr auto kernel = &cj::zstd_encode_kernel;
     uint64_t limit;
     if (const int rc = cj::resident_limit<kernel>(e, cj::kRecEncThreads, limit)) return rc;
@@ -106,10 +112,6 @@ int compress_device(cj_engine* e, uint32_t flags, const cj::BatchArgs& b, hipStr
         hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(cj::kRecEncThreads), 0, s, a, slots, flags);
     });
 }
-
-bool args_ok(cj_zstd_format fmt, uint32_t flags) { return fmt == CJ_ZSTD_FRAMES && (flags & ~CJ_ZSTD_FLAG_CHECKSUM) == 0u; }
-
-}  // namespace
 
 extern "C" {
 
@@ -125,7 +127,7 @@ int cj_zstd_compress_batch_device(cj_engine* e, cj_zstd_format fmt, uint32_t fla
     return cj::device_call(e, n_chunks, {in_base, in_off, in_len, out_base, out_off, out_cap, result}, hip_stream, [&](cj_engine* e, hipStream_t s) {
         cj::BatchArgs a;
         cj::fill_args(a, 0, n_chunks, in_base, in_off, in_len, out_base, out_off, out_cap, result);
-        return compress_device(e, flags, a, s);
+        return cj::zstd_compress_device(e, flags, a, s);
     });
 }
 
@@ -136,7 +138,7 @@ int cj_zstd_compress_batch_host(cj_engine* e, cj_zstd_format fmt, uint32_t flags
                          [&](cj_engine* e, const uint8_t* d_in, uint8_t* d_out, const cj::BatchRows& d, hipStream_t s) {
         cj::BatchArgs a;
         cj::fill_args(a, 0, d_in, d_out, d);
-        return compress_device(e, flags, a, s);
+        return cj::zstd_compress_device(e, flags, a, s);
     });
 }
 

@@ -277,7 +277,7 @@ def test_encode(eng, codec, bs):
     assert list(res4) == list(res) and [bytes(v) for v in views] == outs and bytes(buf[sum(bound):]) == b"\xa5" * 16
 
 
-@pytest.mark.parametrize("codec", ("zlib", "lz4"))
+@pytest.mark.parametrize("codec", CODECS)
 def test_streams_across_turns_through_the_device_entry(eng, codec):
     """Two chunk slots a turn, and streams without a piece — empty ones, refused ones — at and next to the turn edges: pieces 0 | 1 2 3 |
     4 5 6 7 | 8 9 of streams 1, 4, 6 and 8 go through the turns (0 1)(2 3)(4 5)(6 7)(8 9), so the piece-less streams 2, 3 share piece 1
