@@ -234,6 +234,7 @@ CJ_API int  cj_engine_device(const cj_engine* e);
 
 /* Device-resident batch: every pointer is a DEVICE pointer on the engine's GPU.
  * chunk i reads  in_base + in_off[i] .. + in_len[i]   and writes  out_base + out_off[i] .. + out_cap[i];
+ * in_off / out_off are full 64-bit byte offsets: a batch may span more than 4 GiB, and a chunk may lie across a 4 GiB boundary.
  * result[i] = bytes produced (>= 0) or CJ_E_* (< 0); one bad chunk never affects another.
  * hip_stream: a hipStream_t (NULL = the engine's own stream).  Asynchronous: returns after enqueue;
  * call cj_engine_sync (or synchronise the stream yourself) before reading results.

@@ -7,7 +7,10 @@ they import torch before cramjam_amd on purpose (tests/device_api_child.py says 
 What every run gets: the whole output filled with 0xA5 before the call, the result row filled with 0x5A5A5A5A5A5A5A5A (a result that is
 never written reads back as that, never as an expected 0), every buffer freed in `finally`, and a device error ends the session
 (pytest.exit: no later test starts another GPU call).  What stays the caller's choice: the output slots' misalignment, whether
-[result, cap) must stay untouched, and `written` for a refused chunk that may write inside its slot."""
+[result, cap) must stay untouched, and `written` for a refused chunk that may write inside its slot.
+
+The far placement (far_layout / far_buffers / run_far, below) puts a case list around 2^31 and 2^32 of two allocations made once per
+module: 6.06 GiB each, a peak of about 12.2 GiB of device memory (of the MI355X's 288 GB)."""
 import contextlib
 import subprocess
 import sys
@@ -184,6 +187,7 @@ def check_results(res, want, tag):
 # ---- lists of cases --------------------------------------------------------------------------------------------------------------------------------
 # A case is a dict: `bytes` (the input), `cap`, `result` and `out` (the expected bytes; None: `sha`, their sha256); optional `after`
 # (pack), `written` (untouched; without it a refused chunk may write anywhere inside its slot) and `sized` (a size query: no output).
+# The far runner also takes result = None with `at_least` and `verify`: any result from at_least to cap whose bytes verify(bytes) accepts.
 _packs, _slots = {}, {}
 
 
@@ -226,6 +230,280 @@ def run_cases(eng, key, cases, call, tag, packed=None, more=0, dictionary=None, 
         assert (b.tobytes() == c["out"]) if c.get("out") is not None else (hashlib.sha256(bytes(b)).hexdigest() == c["sha"]), ("bytes", tag(i, int(res[i])))
     assert not with_input or (got[2] == blob).all(), ("the input was written", key)
     return res, out, ooff
+
+
+# ---- the far placement -----------------------------------------------------------------------------------------------------------------------------
+# A device entry addresses chunk i as in_base + in_off[i] and out_base + out_off[i] with 64-bit rows.  The far placement puts a case
+# list around a LINE of `bits` bits (32 on the GPU, 20 on the CPU stand-in) inside two allocations made once per module, each of
+# far_size(bits) = 2^(bits-1) + 2^bits + 2^(bits-6) bytes (bits = 32: 2 GiB + 4 GiB + 64 MiB = 6.06 GiB each, 12.2 GiB at the peak).
+# THE INVARIANT: the base handed to the entry is allocation start + 2^(bits-1), so offsets -2^(bits-1) .. 2^bits + 2^(bits-6) are memory
+# of the allocation; an address whose low `bits` bits were cut out of a 64-bit offset and zero-extended lies at o mod 2^bits, one that was
+# sign-extended at o - 2^bits for o mod 2^bits >= 2^(bits-1): both inside the allocation for every byte of every slot.  So a kernel with
+# such an address reads a decoy or writes a shadow window — an assertion here, never a GPU fault.  far_layout() asserts it byte by byte.
+#
+# The cases of a list are dealt round-robin over four places: A around 2^(bits-1) and B around 2^bits (in both the longest input, and
+# the output slot with the largest positive result, has its first byte below the line and its last byte above it), C with its first
+# slot exactly at 2^bits, D from 2^bits + 2^(bits-7) + 5.  B's straddling chunk occupies the byte at 2^bits where C's first slot
+# begins, so one list is two calls of the entry: FAR_CALLS.  Inside a place the inputs keep pack()'s misalignments and gaps, the
+# output slots out_slots()'s 64 guard bytes.  Only windows are ever filled, uploaded or read back.
+PLACES = "ABCD"
+FAR_CALLS = (("A", "B", "D"), ("C",))
+FAR_MARGIN = 1 << 20                     # bytes of 0xA5 around a place's output slots (the stand-in passes a smaller one)
+
+
+def far_size(bits):
+    return (1 << (bits - 1)) + (1 << bits) + (1 << (bits - 6))
+
+
+def far_pieces(lo, hi, bits):
+    """[lo, hi) cut at the two lines: (a, b, where a lies with its low `bits` bits zero-extended, where sign-extended) per piece"""
+    H, L = 1 << (bits - 1), 1 << bits
+    cuts = sorted({lo, hi} | {x for x in (H, L) if lo < x < hi})
+    for a, b in zip(cuts, cuts[1:]):
+        z = a % L
+        yield a, b, z, z - L if z >= H else z
+
+
+def _shadows(lo, hi, bits):
+    """the windows where a truncated address of a byte of [lo, hi) lies: (shadow lo, shadow hi, lo of the bytes it shadows, kind)"""
+    for a, b, z, s in far_pieces(lo, hi, bits):
+        if z == s != a:
+            yield z, z + b - a, a, "zero/sign"
+        else:
+            if z != a:
+                yield z, z + b - a, a, "zero"
+            if s != a:
+                yield s, s + b - a, a, "sign"
+
+
+def _straddle(off, sizes, align=1):
+    """(which slot, how many of its bytes lie below the line): the largest slot, cut near its middle (align: so that the place begins
+    on a multiple of it); None when no slot has two bytes"""
+    s = int(np.argmax(sizes))
+    n = int(sizes[s])
+    if n < 2:
+        return None
+    ks = [k for k in range(1, n) if (int(off[s]) + k) % align == 0] or [n // 2]
+    return s, min(ks, key=lambda k: abs(k - n // 2))
+
+
+def _origin(place, bits, off, sizes, first, align=1):
+    """where a place's run begins so that A and B straddle their line, C's slot 0 (`first` bytes into the run) lies at 2^bits, D's at 2^bits + 2^(bits-7) + 5"""
+    H, L = 1 << (bits - 1), 1 << bits
+    if place in "AB":
+        line, st = (H if place == "A" else L), _straddle(off, sizes, align)
+        return line - int(off[st[0]]) - st[1] if st else line - first - 16
+    return (L if place == "C" else L + (1 << (bits - 7)) + 5) - first
+
+
+def _view(real, decoy, o, bits, kind):
+    """what a read of len(real) bytes at offset o sees when every byte's address is truncated in the `kind` way"""
+    out = bytearray(real)
+    for a, b, z, s in far_pieces(o, o + len(real), bits):
+        if (z if kind == "zero" else s) != a:
+            out[a - o:b - o] = decoy[a - o:b - o]
+    return bytes(out)
+
+
+class FarLayout:
+    """one call of a far list: idx (the cases of this call, as indices of the list), the four rows in_off / in_len / out_off / out_cap
+    relative to the base, want, the input windows [(address, bytes)] with the decoys among them, the output windows [(address, size)]
+    with the shadow windows among them, out_shadows [(lo, hi, chunk, kind)], decoys {chunk: (case, bytes)}, places, straddlers"""
+
+
+_far = {}
+
+
+def far_layout(key, cases, bits, places, margin=FAR_MARGIN):
+    """the layout of the cases that fall into `places`, once per (key, places), with the invariant asserted"""
+    if (key, bits, places) in _far:
+        assert _far[(key, bits, places)].n_all == len(cases), ("one key, two case lists", key)
+        return _far[(key, bits, places)]
+    H, L, end = 1 << (bits - 1), 1 << bits, far_size(bits) - (1 << (bits - 1))
+    F = FarLayout()
+    F.n_all, F.bits, F.places = len(cases), bits, places
+    F.idx = [i for i in range(len(cases)) if PLACES[i % 4] in places]
+    n = len(F.idx)
+    F.in_off, F.out_off = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    F.in_len = np.array([len(cases[i]["bytes"]) for i in F.idx], np.uint64)
+    F.caps = np.array([cases[i]["cap"] for i in F.idx], np.uint64)
+    F.unknown = [k for k, i in enumerate(F.idx) if cases[i]["result"] is None]          # `verify` cases: at_least <= result <= cap, the bytes to verify()
+    F.want = np.array([cases[i]["at_least"] if cases[i]["result"] is None else cases[i]["result"] for i in F.idx], np.int64)
+    F.in_windows, F.out_places, F.straddlers = [], [], {}
+    for p in places:
+        loc = [k for k, i in enumerate(F.idx) if PLACES[i % 4] == p]
+        cs = [cases[F.idx[k]] for k in loc]
+        blob, off, lens = pack([c["bytes"] for c in cs], [c.get("after", b"") for c in cs])
+        org = _origin(p, bits, off, lens, 0, 16)
+        F.in_off[loc] = off + np.uint64(org)
+        F.in_windows.append((org - G, np.concatenate([np.zeros(G, np.uint8), blob])))
+        ooff, total = out_slots(F.caps[loc])
+        real = [0 if c.get("sized") else c["at_least"] if c["result"] is None else max(int(c["result"]), 0) for c in cs]
+        oo = _origin(p, bits, ooff, real if max(real) >= 2 else F.caps[loc], G)
+        F.out_off[loc] = ooff + np.uint64(oo)
+        F.out_places.append((oo - margin, total + 2 * margin, loc, ooff + np.uint64(margin)))
+        line = H if p == "A" else L                  # (first byte below the line, last byte on or above it)
+        F.straddlers[p] = ([k for k in loc if int(F.in_off[k]) < line < int(F.in_off[k]) + int(F.in_len[k])],
+                           [k for k in loc if not cases[F.idx[k]].get("sized") and int(F.out_off[k]) < line < int(F.out_off[k]) + int(F.want[k])])
+    # the decoys: behind every truncated address of an input byte lie the bytes of another case of the list
+    F.decoys, F.in_shadows = {}, []
+    for k, i in enumerate(F.idx):
+        o, real = int(F.in_off[k]), cases[i]["bytes"]
+        sh = list(_shadows(o, o + len(real), bits))
+        if not sh:
+            continue
+        moved = [kind for kind in ("zero", "sign") if any(s[3] in (kind, "zero/sign") for s in sh)]
+        differs = lambda decoy: len(decoy) == len(real) and all(_view(real, decoy, o, bits, kind) != real for kind in moved)
+        for j, tail in [((i + d) % len(cases), t) for t in (False, True) for d in range(1, len(cases))]:
+            other = cases[j]["bytes"]              # the next case of the list whose head differs (tiled when it is shorter); cuts of one stream: whose tail does
+            decoy = other[-len(real):] if tail else (other * (len(real) // max(len(other), 1) + 1))[:len(real)]
+            if differs(decoy):
+                break
+        else:
+            raise AssertionError(("no other case of the list differs from this one", key, i))
+        F.decoys[k] = (j, decoy)
+        for lo, hi, a, kind in sh:
+            F.in_shadows.append((lo, hi, k, kind))
+            F.in_windows.append((lo, np.frombuffer(decoy[a - o:a - o + hi - lo], np.uint8)))
+    # the shadows of every output slot and its guards, merged into windows
+    F.out_shadows = [(lo, hi, k, kind) for k in range(n) for lo, hi, _, kind in _shadows(int(F.out_off[k]) - G, int(F.out_off[k]) + int(F.caps[k]) + G, bits)]
+    F.shadow_windows = []
+    for lo, hi in sorted((lo, hi) for lo, hi, _, _ in F.out_shadows):
+        if F.shadow_windows and lo <= F.shadow_windows[-1][1] + 4096:
+            F.shadow_windows[-1][1] = max(hi, F.shadow_windows[-1][1])
+        else:
+            F.shadow_windows.append([lo, hi])
+    # the invariant, and that no window lies on another
+    for k in range(n):
+        for lo, hi in ((int(F.in_off[k]), int(F.in_off[k]) + int(F.in_len[k])), (int(F.out_off[k]) - G, int(F.out_off[k]) + int(F.caps[k]) + G)):
+            assert 0 <= lo <= hi <= end, ("a slot outside the allocation", key, F.idx[k])
+            for a, b, z, s in far_pieces(lo, hi, bits):                   # (every byte of a piece moves by the same distance)
+                assert -H <= min(z, s) and max(z, s) + b - a <= end, ("a truncated address outside the allocation", key, F.idx[k])
+    for lo, hi, _, _ in F.in_shadows + F.out_shadows:
+        assert -H <= lo <= hi <= end, ("a shadow outside the allocation", key)
+    ins = sorted((a, a + len(b)) for a, b in F.in_windows if len(b))
+    assert all(x[1] <= y[0] for x, y in zip(ins, ins[1:])) and -H <= ins[0][0] and ins[-1][1] <= end, ("two input windows overlap", key, ins)
+    outs = sorted([(a, a + sz) for a, sz, _, _ in F.out_places] + [tuple(w) for w in F.shadow_windows])
+    assert all(x[1] <= y[0] for x, y in zip(outs, outs[1:])) and -H <= outs[0][0] and outs[-1][1] <= end, ("two output windows overlap", key, outs)
+    _far[(key, bits, places)] = F
+    return F
+
+
+class Far:
+    """the two allocations of a module: d_in and d_out are the BASES (allocation start + 2^(bits-1))"""
+
+
+@contextlib.contextmanager
+def far_buffers(eng, bits=32):
+    """the two far allocations, freed whatever happens.  On a card that cannot hold them (12.2 GiB for bits = 32) the tests that ask
+    for them are skipped — decided here, before any call runs under device_batch()'s "a device error ends the session"."""
+    f, live = Far(), []
+    f.bits, f.size = bits, far_size(bits)
+    try:
+        try:
+            for _ in range(2):
+                live.append(eng.alloc(f.size))
+        except _device_error() as ex:
+            import pytest
+            pytest.skip("the far placement needs two device allocations of %d bytes (%.2f GiB each): %s" % (f.size, f.size / 2.0 ** 30, ex))
+        f.d_in, f.d_out = (p + (1 << (bits - 1)) for p in live)
+        yield f
+    finally:
+        for p in live:
+            eng.free(p)
+
+
+def _named_kind(hits, clean_sign_only):
+    """one word for a list of dirty kinds: a shadow that only a sign extension reaches decides for it, one that both reach is a zero
+    extension when a sign-only shadow that a sign extension would have hit stayed clean"""
+    if "sign" in hits:
+        return "sign"
+    return "zero" if "zero" in hits or clean_sign_only else "zero/sign"
+
+
+def run_far(eng, far, key, cases, call, tag, dictionary=None, margin=FAR_MARGIN, calls=FAR_CALLS):
+    """a case list at the far places: per FAR_CALLS one call(idx, d_in, in_off, in_len, d_out, out_off, out_cap, result[, d_dict]) on the
+    module's two allocations (idx: the cases of this call, as indices of the list), held to every case's result and bytes, to [result, cap) and the guards and margin around every slot, to
+    every shadow window still 0xA5, and to input windows read back unchanged.  tag(i, got) names case i of the list; calls: the
+    places of each call, where a caller wants other ones than FAR_CALLS."""
+    import hashlib
+    bits = far.bits
+    for places in calls:
+        F = far_layout(key, cases, bits, places, margin)
+        n = len(F.idx)
+        if not n:
+            continue
+        b = _Batch(eng, n)
+        try:
+            for a, data in F.in_windows:
+                if len(data):
+                    eng.h2d(far.d_in + a, data)
+            for a, sz in [(a, sz) for a, sz, _, _ in F.out_places] + [(lo, hi - lo) for lo, hi in F.shadow_windows]:
+                eng.memset(far.d_out + a, FILL, sz)
+            m = b.rows(F.in_off, F.in_len, F.out_off, F.caps, np.full(n, UNWRITTEN, np.uint64))
+            d_dict = None
+            if dictionary is not None:
+                d_dict = b.buffer(len(dictionary) + 32) + 3
+                if len(dictionary):
+                    eng.h2d(d_dict, np.frombuffer(dictionary, np.uint8))
+            eng.sync()
+            call(*((list(F.idx), far.d_in, m[0], m[1], far.d_out, m[2], m[3], m[4]) + ((d_dict,) if dictionary is not None else ())))
+            eng.sync()
+            res = b.read_row(m[4])
+            outs = [eng.d2h(far.d_out + a, sz) for a, sz, _, _ in F.out_places]
+            shadows = [(lo, eng.d2h(far.d_out + lo, hi - lo)) for lo, hi in F.shadow_windows]
+            back = [eng.d2h(far.d_in + a, len(data)) for a, data in F.in_windows]
+        except _device_error() as ex:
+            import pytest
+            pytest.exit("device error in %r: %s" % (key, ex), 1)
+        finally:
+            b.free()
+        name = lambda k: tag(F.idx[k], int(res[k]))
+        want = F.want.copy()
+        for k in F.unknown:                                  # (an encoder without a byte-exact model: any length its own verify() accepts)
+            assert F.want[k] <= res[k] <= F.caps[k], ("result", name(k))
+            want[k] = res[k]
+        # a write at a truncated out_off: the most telling failure first
+        dirty = []
+        for lo, hi, k, kind in F.out_shadows:
+            base, w = next((a, w) for a, w in shadows if a <= lo and hi <= a + len(w))
+            dirty.append((w[lo - base:hi - base] != FILL).any())
+        hits = [(k, kind) for (_, _, k, kind), d in zip(F.out_shadows, dirty) if d]
+        if hits:
+            wrote = lambda k: want[k] > 0 and not cases[F.idx[k]].get("sized")
+            clean = any(kind == "sign" and wrote(k) and not d for (_, _, k, kind), d in zip(F.out_shadows, dirty))
+            raise AssertionError("chunk %r written at its offset truncated to %d bits (%s)" % (name(hits[0][0]), bits, _named_kind([h[1] for h in hits], clean)))
+        # results and bytes; a chunk that came out as its decoy was read at a truncated in_off
+        got = {}
+        for (a, sz, loc, _), out in zip(F.out_places, outs):
+            for k in loc:
+                lo = int(F.out_off[k]) - a
+                got[k] = out[lo:lo + max(int(want[k]), 0)]
+        reads = {}
+        for k, (j, decoy) in F.decoys.items():
+            o, real = int(F.in_off[k]), cases[F.idx[k]]["bytes"]
+            reads[k] = {kind: _view(real, decoy, o, bits, kind) for kind in ("zero", "sign")}
+        copied = [[kind for kind, v in reads[k].items() if v != cases[F.idx[k]]["bytes"] and got[k].tobytes() == v] for k in sorted(reads)]
+        if any(copied):
+            k = next(k for k, c in zip(sorted(reads), copied) if c)
+            kinds = ["/".join(c) for c in copied if c]
+            sign_only = any(reads[k]["sign"] != reads[k]["zero"] and not c for k, c in zip(sorted(reads), copied))
+            raise AssertionError("chunk %r read at its offset truncated to %d bits (%s)" % (name(k), bits, _named_kind(kinds, sign_only)))
+        note = lambda k: name(k) + (("in place", PLACES[F.idx[k] % 4]) + (("its truncated in_off holds case", F.decoys[k][0]) if k in F.decoys else ()),)
+        bad = np.nonzero(res != want)[0]
+        assert len(bad) == 0, (len(bad), [note(int(k)) for k in bad[:6]])
+        for k in np.nonzero(want > 0)[0]:
+            c = cases[F.idx[k]]
+            if c.get("verify"):
+                c["verify"](got[k].tobytes())
+            elif not c.get("sized"):
+                assert (got[k].tobytes() == c["out"]) if c.get("out") is not None else (hashlib.sha256(bytes(got[k])).hexdigest() == c["sha"]), ("bytes", note(int(k)))
+        for (a, sz, loc, at), out in zip(F.out_places, outs):
+            cs = [cases[F.idx[k]] for k in loc]
+            keep = untouched(at, want[loc], sz, written=[c.get("written", c["cap"]) for c in cs], sized=[bool(c.get("sized")) for c in cs])
+            check_mask(out, keep, at, lambda q: name(loc[q]), "a guard byte or a byte outside [0, result) changed")
+        for (a, data), now in zip(F.in_windows, back):
+            assert (now == data).all(), ("the input was written", key, a)
 
 
 # ---- children ------------------------------------------------------------------------------------------------------------------------------------

@@ -243,3 +243,180 @@ def test_run_child(tmp_path):
         DB.run_child(_script(tmp_path, "print('it: ok')\nsys.exit(3)\n"), "it: ok", 60)
     with pytest.raises(AssertionError):
         DB.run_child(_script(tmp_path, "print('it: almost')\nsys.exit(0)\n"), "it: ok", 60)
+
+
+# ---- the far placement -----------------------------------------------------------------------------------------------------------------------------
+BITS, MARGIN = 20, 256                              # the stand-in's line: 2^20, so its two allocations are 1.5 MiB + 16 KiB each
+H, L = 1 << (BITS - 1), 1 << BITS
+FAR_LENS = (40, 300, 33, 90, 17, 1, 64, 129, 250, 31, 2, 77, 100, 210, 5, 0, 55, 16, 48, 9)
+FAR = [dict(bytes=bytes((i * 37 + j * (i + 3)) % 250 + 1 for j in range(n)), cap=n + (i % 3) * 7, result=n) for i, n in enumerate(FAR_LENS)]
+for _c in FAR:
+    _c["out"] = _c["bytes"]
+FAR[7] = dict(FAR[7], cap=100, result=-3, out=b"")  # (place D) does not fit: refused
+far_tag = lambda i, got: ("case", i, "got", got)
+sext = lambda v: v % L - L if v % L >= H else v % L
+
+
+def far_kernel(eng, in_at=lambda o, k: o + k, out_at=lambda o, k: o + k):
+    """copies chunk by chunk, byte k of a chunk at in_at(in_off, k) and out_at(out_off, k): the right kernel, or one wrong address"""
+    def call(idx, d_in, in_off, in_len, d_out, out_off, out_cap, result):
+        n = len(idx)
+        row = lambda p: [int(v) for v in eng.d2h(p, 8 * n, "int64")]
+        for i, (o, ln, oo, cap) in enumerate(zip(row(in_off), row(in_len), row(out_off), row(out_cap))):
+            for k in range(ln if ln <= cap else 0):
+                eng.mem[d_out + out_at(oo, k)] = eng.mem[d_in + in_at(o, k)]
+            eng.h2d(result + 8 * i, np.int64(ln if ln <= cap else -3))
+    return call
+
+
+def far_run(key="far", **addr):
+    eng = Engine()
+    with DB.far_buffers(eng, BITS) as far:
+        assert far.size == H + L + (1 << 14) and len(eng.live) == 2
+        DB.run_far(eng, far, key, FAR, far_kernel(eng, **addr), far_tag, margin=MARGIN)
+        assert len(eng.live) == 2
+    assert not eng.live
+
+
+def test_the_far_layout():
+    assert DB.far_size(32) == (2 << 30) + (4 << 30) + (64 << 20) and DB.FAR_CALLS == (("A", "B", "D"), ("C",))
+    seen = set()
+    for places in DB.FAR_CALLS:
+        F = DB.far_layout("far", FAR, BITS, places, MARGIN)
+        assert [i % 4 for i in F.idx] == [DB.PLACES.index(p) for _ in range(len(F.idx) // len(places)) for p in places]
+        seen |= set(F.idx)
+        place = lambda p: [k for k, i in enumerate(F.idx) if DB.PLACES[i % 4] == p]
+        for p, line in (("A", H), ("B", L)):
+            if p in places:
+                s_in, s_out = F.straddlers[p]
+                assert len(s_in) == 1 and len(s_out) == 1, "one chunk of the place has its first byte below the line and its last byte above it"
+                k = s_in[0]
+                assert int(F.in_off[k]) < line <= int(F.in_off[k]) + int(F.in_len[k]) - 1 and F.in_len[k] == max(F.in_len[place(p)])
+                k = s_out[0]
+                assert int(F.out_off[k]) < line <= int(F.out_off[k]) + int(F.want[k]) - 1 and F.want[k] > 0
+                assert min(F.in_off[place(p)]) < line < max(F.in_off[place(p)]) and min(F.out_off[place(p)]) < line < max(F.out_off[place(p)])
+        if "C" in places:
+            assert int(F.in_off[place("C")[0]]) == L and int(F.out_off[place("C")[0]]) == L
+        if "D" in places:
+            assert int(F.in_off[place("D")[0]]) == L + (1 << (BITS - 7)) + 5 and int(F.out_off[place("D")[0]]) == L + (1 << (BITS - 7)) + 5
+        if "A" in places:                           # inside a place: pack()'s residues, out_slots()'s guards
+            ks = place("A")
+            assert [int(F.in_off[k] - F.in_off[ks[0]]) % 16 for k in ks] == [DB.in_mis(q) for q in range(len(ks))]
+            assert all(int(F.out_off[b]) - int(F.out_off[a]) - int(F.caps[a]) == DB.G for a, b in zip(ks, ks[1:]))
+        # every decoy differs from the chunk it shadows, under each truncation that moves the chunk
+        for k, (j, decoy) in F.decoys.items():
+            real, o = FAR[F.idx[k]]["bytes"], int(F.in_off[k])
+            assert j != F.idx[k] and len(decoy) == len(real) and decoy != real
+            moved = [kind for kind in ("zero", "sign") if any(a != (z if kind == "zero" else s) for a, _, z, s in DB.far_pieces(o, o + len(real), BITS))]
+            assert moved and all(DB._view(real, decoy, o, BITS, kind) != real for kind in moved)
+        far_in_place = [k for k, i in enumerate(F.idx) if F.in_len[k] and int(F.in_off[k]) >= H]
+        assert set(far_in_place) <= set(F.decoys), "every non-empty chunk on or above 2^(bits-1) has a decoy"
+        # every wrong address inside the allocation: offsets -2^(bits-1) .. 2^bits + 2^(bits-6)
+        end = DB.far_size(BITS) - H
+        for k in range(len(F.idx)):
+            for lo, n in ((int(F.in_off[k]), int(F.in_len[k])), (int(F.out_off[k]), int(F.caps[k]))):
+                for at in range(lo, lo + n):
+                    assert 0 <= at < end and -H <= at % L < end and -H <= sext(at) < end
+        assert all(-H <= lo < hi <= end for lo, hi, _, _ in F.in_shadows + F.out_shadows)
+        kinds = {kind for _, _, _, kind in F.out_shadows}
+        assert kinds == {"sign", "zero/sign"}      # (the call of place C: the guard in front of its first slot lies below the line)
+    assert seen == set(range(len(FAR)))
+
+
+def test_far_pieces_are_cut_at_both_lines():
+    assert list(DB.far_pieces(H - 2, H + 3, BITS)) == [(H - 2, H, H - 2, H - 2), (H, H + 3, H, -H)]
+    assert list(DB.far_pieces(L - 1, L + 1, BITS)) == [(L - 1, L, L - 1, -1), (L, L + 1, 0, 0)]
+    assert list(DB.far_pieces(L + 9, L + 9, BITS)) == []
+    assert list(DB._shadows(L - 1, L + 1, BITS)) == [(-1, 0, L - 1, "sign"), (0, 1, L, "zero/sign")]
+    assert list(DB._shadows(7, H, BITS)) == []
+
+
+def test_the_right_kernel_passes_at_the_far_places():
+    far_run()
+
+
+def far_failure(**addr):
+    with pytest.raises(AssertionError) as ex:
+        far_run(**addr)
+    return str(ex.value.args[0])
+
+
+def _case_of(msg):
+    return int(msg.split("('case', ")[1].split(",")[0])
+
+
+def test_in_off_cut_to_the_line_and_zero_extended():
+    msg = far_failure(in_at=lambda o, k: o % L + k)
+    assert msg.startswith("chunk ('case', ") and msg.endswith("read at its offset truncated to 20 bits (zero)")
+    assert _case_of(msg) % 4 in (1, 3), "a chunk of place B above the line, or of place D"
+
+
+def test_in_off_cut_to_the_line_and_sign_extended():
+    msg = far_failure(in_at=lambda o, k: sext(o) + k)
+    assert msg.endswith("read at its offset truncated to 20 bits (sign)") and _case_of(msg) == 1, "the first chunk of place B lies in [2^19, 2^20): sign-extended, just below the base"
+
+
+def test_out_off_cut_to_the_line_and_zero_extended():
+    msg = far_failure(out_at=lambda o, k: o % L + k)
+    assert msg.startswith("chunk ('case', ") and msg.endswith("written at its offset truncated to 20 bits (zero)")
+    assert _case_of(msg) % 4 in (1, 3)
+
+
+def test_out_off_cut_to_the_line_and_sign_extended():
+    msg = far_failure(out_at=lambda o, k: sext(o) + k)
+    assert msg.endswith("written at its offset truncated to 20 bits (sign)") and _case_of(msg) == 1
+
+
+wrap = lambda o, k: o - o % L + (o + k) % L        # right for a chunk's first byte, no carry out of the low 20 bits behind it
+
+
+@pytest.mark.parametrize("side", ("in_at", "out_at"))
+def test_an_offset_added_in_the_lines_bits_behind_the_first_byte(side):
+    """only the chunk that straddles 2^20 in place B sees it"""
+    F = DB.far_layout("far", FAR, BITS, DB.FAR_CALLS[0], MARGIN)
+    k = F.straddlers["B"][side == "out_at"][0]
+    msg = far_failure(**{side: wrap})
+    assert msg.endswith("%s at its offset truncated to 20 bits (zero)" % ("read" if side == "in_at" else "written")) and _case_of(msg) == F.idx[k]
+
+
+def test_a_card_too_small_for_the_far_allocations_skips_and_leaks_nothing():
+    from cramjam_amd import _native as N
+
+    class Small(Engine):
+        def alloc(self, nbytes):
+            if self.live:
+                raise N.EngineError("out of memory")
+            return Engine.alloc(self, nbytes)
+    eng = Small()
+    with pytest.raises(pytest.skip.Exception) as ex:
+        with DB.far_buffers(eng, BITS):
+            raise RuntimeError("not reached")
+    assert "%d bytes" % DB.far_size(BITS) in str(ex.value) and not eng.live
+
+
+def test_a_far_call_that_raises_leaves_only_the_two_allocations():
+    eng = Engine()
+    def call(*a):
+        raise ValueError("the call failed")
+    with DB.far_buffers(eng, BITS) as far:
+        with pytest.raises(ValueError):
+            DB.run_far(eng, far, "far", FAR, call, far_tag, margin=MARGIN)
+        assert len(eng.live) == 2
+    assert not eng.live
+
+
+def test_a_case_without_expected_bytes_is_held_to_its_own_verify():
+    """result None: any length from at_least to the capacity, and the bytes go to verify()"""
+    seen = []
+    cases = [dict(c) for c in FAR]
+    cases[5] = dict(cases[5], result=None, at_least=1, out=None, verify=seen.append)
+    eng = Engine()
+    with DB.far_buffers(eng, BITS) as far:
+        DB.run_far(eng, far, "far-verify", cases, far_kernel(eng), far_tag, margin=MARGIN)
+        assert seen == [FAR[5]["bytes"]]
+        cases[5]["at_least"] = len(FAR[5]["bytes"]) + 1
+        DB._far.clear()
+        with pytest.raises(AssertionError) as ex:
+            DB.run_far(eng, far, "far-verify", cases, far_kernel(eng), far_tag, margin=MARGIN)
+        assert ex.value.args[0][0] == "result" and ex.value.args[0][1][:2] == ("case", 5)
+    DB._far.clear()
