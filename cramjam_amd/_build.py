@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libcramjam_hip.so")
-SOURCES = ["engine.hip", "lz4_decode.hip", "lz4_decode_lanes.hip", "lz4_decode_lds.hip", "big_chunks.hip", "lz4_encode.hip", "snappy_decode.hip", "snappy_encode.hip", "frame_kernels.hip", "frame.hip", "frame_batch.hip", "batch_sizes.hip", "blosc_filters.hip", "blosclz_decode.hip", "blosc_batch.hip", "lz4_dict.hip", "deflate.hip", "deflate_encode.hip", "bgzf_batch.hip", "orc_batch.hip", "parquet_batch.hip", "zstd.hip", "zstd_encode.hip", "large.hip", "big_parse.hip", "bench_util.hip"]
-HEADERS = ["lds_shared.hpp", "big_chunks.hpp", "cj_common.hpp", "cj_engine.hpp", "cj_stage.hpp", "cj_container.hpp", "cj_codecs.hpp", "cj_match.hpp", "cj_enc2.hpp", "cj_rec_encode.hpp", "crc32c_lanes.hpp", "crc32_lanes.hpp", "wave_lanes.hpp", "wave_window.hpp", "deflate_wave.hpp", "zstd_wave.hpp", "deflate_enc_wave.hpp", "zstd_enc_wave.hpp", "zstd_fse_enc.h", "lane_stream.hpp", "snappy_records.hpp", "parse_grammar.hpp", "big_parse.hpp", "xxh32_host.hpp", "frame_grammar.hpp", "blosc_grammar.hpp", "bgzf_grammar.hpp", "orc_grammar.hpp", "parquet_grammar.hpp", "blosc_filters.hpp", "blosclz_wave.hpp", "lz4_wave.hpp", "snappy_wave.hpp", "lz4_lane_walk.hpp", "lz4_size_walk.hpp", os.path.join("..", "..", "include", "cramjam_hip.h"), os.path.join("..", "..", "include", "cramjam_hip_debug.h")]
+SOURCES = ["engine.hip", "lz4_decode.hip", "lz4_decode_lanes.hip", "lz4_decode_lds.hip", "big_chunks.hip", "lz4_encode.hip", "snappy_decode.hip", "snappy_encode.hip", "frame_kernels.hip", "frame.hip", "frame_batch.hip", "batch_sizes.hip", "blosc_filters.hip", "blosclz_decode.hip", "blosc_batch.hip", "lz4_dict.hip", "deflate.hip", "deflate_encode.hip", "bgzf_batch.hip", "orc_batch.hip", "parquet_batch.hip", "parquet_write.hip", "zstd.hip", "zstd_encode.hip", "large.hip", "big_parse.hip", "bench_util.hip"]
+HEADERS = ["lds_shared.hpp", "big_chunks.hpp", "cj_common.hpp", "cj_engine.hpp", "cj_stage.hpp", "cj_container.hpp", "cj_codecs.hpp", "cj_match.hpp", "cj_enc2.hpp", "cj_rec_encode.hpp", "crc32c_lanes.hpp", "crc32_lanes.hpp", "wave_lanes.hpp", "wave_window.hpp", "deflate_wave.hpp", "zstd_wave.hpp", "deflate_enc_wave.hpp", "zstd_enc_wave.hpp", "zstd_fse_enc.h", "lane_stream.hpp", "snappy_records.hpp", "parse_grammar.hpp", "big_parse.hpp", "xxh32_host.hpp", "frame_grammar.hpp", "blosc_grammar.hpp", "bgzf_grammar.hpp", "orc_grammar.hpp", "parquet_grammar.hpp", "parquet_write.hpp", "blosc_filters.hpp", "blosclz_wave.hpp", "lz4_wave.hpp", "snappy_wave.hpp", "lz4_lane_walk.hpp", "lz4_size_walk.hpp", os.path.join("..", "..", "include", "cramjam_hip.h"), os.path.join("..", "..", "include", "cramjam_hip_debug.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"] + os.environ.get("CJ_EXTRA_HIPCC_FLAGS", "").split()
 

@@ -24,7 +24,7 @@ E_BLOSC_HEADER, E_BLOSC_UNSUPPORTED = -30, -31
 E_DEFLATE_CORRUPT, E_DEFLATE_HEADER, E_DEFLATE_CHECKSUM, E_DEFLATE_EOF, E_DEFLATE_TRAILING = -40, -41, -42, -43, -44
 E_ZSTD_HEADER, E_ZSTD_CORRUPT, E_ZSTD_CHECKSUM, E_ZSTD_SRC_SIZE, E_ZSTD_DICT = -50, -51, -52, -53, -54
 E_ORC_HEADER, E_ORC_BLOCK = -60, -61
-E_PARQUET_HEADER, E_PARQUET_SIZE, E_PARQUET_CRC = -70, -71, -72
+E_PARQUET_HEADER, E_PARQUET_SIZE, E_PARQUET_CRC, E_PARQUET_TABLE = -70, -71, -72, -73
 ORC_ZLIB, ORC_SNAPPY, ORC_LZ4, ORC_ZSTD = 1, 2, 4, 5      # ORC's CompressionKind (cj_orc_batch_*)
 PARQUET_UNCOMPRESSED, PARQUET_SNAPPY, PARQUET_GZIP, PARQUET_ZSTD, PARQUET_LZ4_RAW = 0, 1, 2, 6, 7      # Parquet's CompressionCodec (cj_parquet_batch_*)
 PARQUET_FLAG_VERIFY_CRC = 1        # cj_parquet_batch_*: check the CRC-32 of every page that carries one
@@ -116,6 +116,9 @@ SYMBOLS = {
     "cj_parquet_sizes_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp]),
     "cj_parquet_pages_device": (_int, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_parquet_pages_host": (_int, [_vp, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_compress_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_compress_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cj_parquet_compress_bound": (_sz, [_int, _sz, _sz]),
     "cj_zstd_compress_batch_device": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_batch_host": (_int, [_vp, _int, _u32, _sz, _vp, _vp, _vp, _vp, _vp]),
     "cj_zstd_compress_bound": (_sz, [_sz, _u32]),
@@ -156,6 +159,7 @@ BENCH_SYMBOLS = {
     "cj_debug_deflate_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_bgzf_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_orc_slot_budget": (C.c_uint64, [C.c_uint64]),
+    "cj_debug_parquet_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_zstd_enc_slot_budget": (C.c_uint64, [C.c_uint64]),
     "cj_debug_grid_chunks": (C.c_uint64, [C.c_uint64]),

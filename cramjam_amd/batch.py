@@ -884,3 +884,89 @@ def parquet_pages_device(inp, in_off, in_len, rows=None, row_off=None, row_cap=N
         return call.finish(p_res, result)
     finally:
         call.close()
+
+
+# ---- Parquet column chunks, written (cj_parquet_compress_* / cj_parquet_compress_bound) ----------------------------------
+# The input of one entry is a DECODED chunk — what parquet_decompress_chunks gives — and its page table in parquet_pages' layout, so
+# decode -> parquet_pages -> parquet_compress_chunks with another codec is Parquet-to-Parquet recompression.  The writer reads word 0
+# (the type; its high half is V2's num_nulls, which parquet_pages leaves 0), 3, 5, 6 (the encodings; bit 25: write a crc) and 7.
+# result[i] = the chunk's length or a negative CJ_E_* code: -73 an inconsistent table, -1 a chunk above 0x7E000000 bytes, the encoder's
+# code of a V1 or dictionary page, -6 a chunk that does not fit its capacity; a chunk with a code writes nothing.
+_PARQUET_ROW_CRC = 1 << 25
+
+
+def parquet_compress_bound(codec, n, pages):
+    """the capacity that suffices for a decoded chunk of n bytes in `pages` pages, however the pages cut it: pages * (57 + K) + n + g(n)
+    (cramjam_hip.h); 0 above 0x7E000000 bytes.  No device."""
+    return N.lib().cj_parquet_compress_bound(_parquet_codec(codec), n, pages)
+
+
+def _parquet_table(t, write_crc):
+    import numpy as np
+    a = np.array(t, dtype=np.int64).reshape(-1, 8) if write_crc is not None else np.ascontiguousarray(np.asarray(t, dtype=np.int64).reshape(-1, 8))
+    if write_crc is not None:
+        a[:, 6] = (a[:, 6] | _PARQUET_ROW_CRC) if write_crc else (a[:, 6] & ~_PARQUET_ROW_CRC)
+    return a
+
+
+def parquet_compress_chunks(buffers, tables, codec, write_crc=None, devices=None, out=None):
+    """write many Parquet column chunks, page-parallel: buffers[i] is a decoded chunk, tables[i] its (pages, 8) int64 page table as
+    parquet_pages returns it; returns (results, chunks) as lz4_compress_blocks.  codec: as in parquet_decompress_chunks.  Per page a
+    Thrift compact PageHeader (no Statistics), a V2 page's levels, and the values through the codec — a V2 page whose values do not
+    shrink carries them raw with is_compressed = false.  write_crc: True / False sets / clears bit 25 of every row (a copy of the table)
+    before the call, None leaves the rows' own bits.  out: as in lz4_decompress_blocks; it has to hold
+    sum(parquet_compress_bound(codec, len(buffer), len(table))) bytes."""
+    import numpy as np
+    what, n = _parquet_codec(codec), len(buffers)
+    if len(tables) != n:
+        raise ValueError("cramjam_amd.batch: %d tables for %d buffers" % (len(tables), n))
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in buffers]                  # borrowed, not copied
+    tabs = [_parquet_table(t, write_crc) for t in tables]
+    L = N.lib()
+    caps = [L.cj_parquet_compress_bound(what, a.size, len(t)) for a, t in zip(arrs, tabs)]
+    offsets, run = [], 0
+    for c in caps:
+        offsets.append(run); run += int(c)
+    if out is None:
+        dst = np.empty(run, np.uint8)
+    else:
+        dst = np.frombuffer(out, dtype=np.uint8)
+        if dst.size < run:
+            raise ValueError("cramjam_amd.batch: out holds %d bytes, the bounds need %d" % (dst.size, run))
+
+    def work(dev, idx):
+        k, h = len(idx), _engine(dev).h
+        ptrs = (_C.c_void_p * max(k, 1))(*[arrs[i].ctypes.data if arrs[i].size else None for i in idx])
+        lens = (_C.c_size_t * max(k, 1))(*[arrs[i].size for i in idx])
+        rows = (_C.c_void_p * max(k, 1))(*[tabs[i].ctypes.data if len(tabs[i]) else None for i in idx])
+        cnts = (_C.c_size_t * max(k, 1))(*[len(tabs[i]) for i in idx])
+        outs = (_C.c_void_p * max(k, 1))(*[dst.ctypes.data + offsets[i] if caps[i] else None for i in idx])
+        ocap = (_C.c_size_t * max(k, 1))(*[caps[i] for i in idx])
+        res = np.empty(k, np.int64)
+        N.check(L.cj_parquet_compress_host(h, what, 0, k, ptrs, lens, rows, cnts, outs, ocap, res.ctypes.data))
+        return ([int(r) for r in res],)
+    res, = _shard(devices, n, work)
+    mv = memoryview(dst)
+    views = [mv[offsets[i]:offsets[i] + max(res[i], 0)] for i in range(n)]
+    return res, (views if out is not None else [bytes(v) for v in views])
+
+
+def parquet_compress_chunks_device(inp, in_off, in_len, rows, row_off, row_cnt, out, out_off, out_cap, codec, result=None, device=None, stream=None, sync=True):
+    """Write a device-resident batch of decoded chunks as Parquet column chunks (arguments as parquet_decompress_chunks_device; rows is
+    a device buffer of 64-bit integers: chunk i's table is row_cnt[i] rows of eight words at rows[8 * row_off[i]:], as
+    parquet_pages_device writes them).  The call waits for the stream once, for the chunks' plans; a capacity below
+    parquet_compress_bound is allowed — a chunk that does not fit gets -6 and writes nothing."""
+    call = _DeviceCall(stream, sync)
+    try:
+        vin, vrows, vout = call.buffer(inp), call.buffer(rows), call.buffer(out)
+        eng = call.engine(device, vin, vout)
+        if vrows.itemsize != 8:
+            raise TypeError("cramjam_amd.batch: rows must hold 64-bit integers")
+        i = (vin.ptr, call.meta(in_off, "in_off"), call.meta(in_len, "in_len"))
+        t = (vrows.ptr, call.meta(row_off, "row_off"), call.meta(row_cnt, "row_cnt"))
+        o = (vout.ptr, call.meta(out_off, "out_off"), call.meta(out_cap, "out_cap"))
+        p_res = call.result(result)
+        N.check(N.lib().cj_parquet_compress_device(eng.h, _parquet_codec(codec), 0, call.n, *i, *t, *o, p_res, stream))
+        return call.finish(p_res, result)
+    finally:
+        call.close()

@@ -478,6 +478,7 @@ const char* cj_strerror(int64_t code) {
     case CJ_E_PARQUET_HEADER: return "parquet: malformed page header (truncated, a bad varint or wire type, nesting too deep, a required field missing, a bad size, or a payload past the chunk's end)";
     case CJ_E_PARQUET_SIZE: return "parquet: a page decodes to fewer bytes than its header states";
     case CJ_E_PARQUET_CRC: return "parquet: page CRC-32 mismatch";
+    case CJ_E_PARQUET_TABLE: return "parquet: inconsistent page table (a page type outside 0, 2, 3, a negative size, bad level lengths, sizes that do not sum to the chunk's length, or too many rows)";
     case CJ_E_NO_DEVICE: return "cramjam_hip: no usable HIP device (no CPU fallback exists)";
     case CJ_E_BAD_ARG: return "cramjam_hip: bad argument";
     case CJ_E_OOM: return "cramjam_hip: out of memory";

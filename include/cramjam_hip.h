@@ -88,6 +88,9 @@ extern "C" {
                                       * chunk's end */
 #define CJ_E_PARQUET_SIZE       (-71) /* Parquet column chunk: a page's codec stream decodes cleanly to fewer bytes than its header states */
 #define CJ_E_PARQUET_CRC        (-72) /* Parquet column chunk: a page's CRC-32 (verified on request) does not match its header's */
+#define CJ_E_PARQUET_TABLE      (-73) /* Parquet writer: the page table is inconsistent — a page type outside {0, 2, 3}, a negative size, level
+                                      * lengths on a page that is not V2 or above the page's size, sizes whose sum is not the chunk's length,
+                                      * or more rows than 0xFFFFFFF0 */
 #define CJ_E_NO_DEVICE         (-100) /* no HIP device / HIP runtime failure (see cj_last_hip_error) */
 #define CJ_E_BAD_ARG           (-101)
 #define CJ_E_OOM               (-102) /* device or pinned-host allocation failed */
@@ -602,6 +605,60 @@ CJ_API int cj_parquet_pages_device(cj_engine* e, uint32_t flags, size_t n_chunks
 CJ_API int cj_parquet_pages_host(cj_engine* e, uint32_t flags, size_t n_chunks,
                                  const uint8_t* const* in_ptrs, const size_t* in_lens,
                                  int64_t* const* rows_ptrs, const size_t* row_caps, int64_t* result);
+
+/* Batches of decoded Parquet column chunks INTO column chunks: the writer beside cj_parquet_batch_*.  The caller has
+ * the pages' DECODED bytes one after another (V2: repetition levels, definition levels, values) — exactly what cj_parquet_batch_*
+ * writes — and the chunk's page table in the layout of cj_parquet_pages_*, so a decoded chunk's table can be passed straight back
+ * (Parquet-to-Parquet recompression: decode, pages, compress with another codec).  Everything else runs on the device in one call: the
+ * codec over every values section, per V2 page whether compression paid, the CRC-32 of every payload, the Thrift compact PageHeaders,
+ * the layout and the assembly.  Addressing, the 16-byte-granule rule, stream rules, e == NULL, n_chunks == 0 and the null-pointer
+ * rules are cj_parquet_batch_*'s (rows, row_off and row_cnt count among the rows that must be present).
+ *   what        Parquet's CompressionCodec as cj_parquet_batch_* takes it: 0, 1, 2, 6, 7; anything else is CJ_E_BAD_ARG.
+ *   flags       0; any bit set is CJ_E_BAD_ARG.  These two checks come first and need no device.
+ *   table       chunk i's pages are row_cnt[i] rows of eight int64 at rows + 8 * row_off[i] (host: at rows_ptrs[i]).  Read: word 0 —
+ *               the low 32 bits the page type (0, 2 or 3), the high 32 bits V2's num_nulls (the pages query leaves them 0: a caller
+ *               who has the value puts it there) —, word 3 uncompressed_page_size, word 5 num_values | num_rows << 32, word 6 the
+ *               three encodings and bit 25, "write a crc for this page" (bit 24, is_compressed, is ignored: the writer decides it),
+ *               word 7 the level lengths.  Words 1, 2 and 4 are ignored: a page's offset in the decoded chunk is the sum of word 3
+ *               of the pages before it.
+ *   result[i]   the written chunk's length or CJ_E_*, in this order: CJ_E_PARQUET_TABLE for row_cnt[i] > 0xFFFFFFF0;
+ *               CJ_E_INPUT_TOO_LARGE for in_len[i] > 0x7E000000; CJ_E_PARQUET_TABLE at the first row in page order with a type
+ *               outside {0, 2, 3}, a word 3 below 0 (or above 2^31 - 1), level lengths on a page that is not V2, or level lengths
+ *               above word 3; CJ_E_PARQUET_TABLE when the sum of word 3 is not in_len[i]; the encoder's code of the first V1 or
+ *               dictionary page in page order that has one; CJ_E_OUT_TOO_SMALL when the chunk would exceed out_cap[i].  All of it is
+ *               decided before the chunk's first store: a chunk with a code writes NOTHING, and a capacity below the bound is allowed.
+ *               A chunk of 0 pages and 0 bytes is an empty chunk, result 0.  One bad chunk never affects another.
+ *   written     per page a PageHeader with its fields in ascending order and short form — 1 type, 2 uncompressed_page_size,
+ *               3 compressed_page_size, 4 crc where asked for, then 5 DataPageHeader, 7 DictionaryPageHeader (without is_sorted) or
+ *               8 DataPageHeaderV2 (is_compressed always written), no Statistics; 57 bytes at most (a V2 page: type 2; the sizes and
+ *               the crc 6 each; the struct's header 1; num_values, num_nulls, num_rows 6 each; encoding 3; the level lengths 6 each;
+ *               is_compressed 1; two stops) —, then a V2 page's levels copied from the input, then the values: 0 bytes for a values
+ *               section of 0 bytes (the codec is not asked; is_compressed false); the bytes themselves for UNCOMPRESSED; else the
+ *               codec's output (cj_batch_device for Snappy raw and raw LZ4 blocks, cj_deflate_compress_batch_* with CJ_DEFLATE_GZIP,
+ *               cj_zstd_compress_batch_* without checksum) — but a V2 page whose output is not shorter than its values, or whose
+ *               encoder reported an error, carries the raw values and is_compressed = false.  V1 and dictionary pages have no such
+ *               flag and always carry the output.  The crc is gzip's CRC-32 of the payload as written, levels included.  The bytes
+ *               depend on nothing but the input and the table.
+ *   bound       cj_parquet_compress_bound(what, n_bytes, n_pages) = n_pages * (57 + K) + n_bytes + g(n_bytes), an upper bound over
+ *               every way of cutting n_bytes into n_pages pages: a maximal header, the levels, and the codec's bound of the values,
+ *               from the encoders' own bounds v + g(v) + K' with K' <= K — LZ4_RAW g = v / 255, K = 16; SNAPPY v / 6, 32; GZIP
+ *               10 (v / 65536), 23; ZSTD 3 (v / 65536), 13; UNCOMPRESSED 0, 0.  0 for a bad `what`, n_bytes > 0x7E000000 or
+ *               n_pages > 0xFFFFFFF0.  Pure arithmetic, no device.
+ * NOT enqueue-only: a call takes one turn at the engine's container scratch and waits for the stream ONCE, for the chunks' plans
+ * (page counts, pages the codec sees, slot bytes); the bound-sized page slots are engine scratch within a fixed budget, a large batch
+ * runs in turns of whole chunks.  The _host call is cj_batch_host's one-shot staging, synchronous; a table of more rows than
+ * 0x7E000000 / 64 that is not above 0xFFFFFFF0 is CJ_E_BAD_ARG there.  cj_parquet_batch_* with CJ_OP_COMPRESS stays CJ_E_BAD_ARG.
+ * Not written: Statistics, footers, page indexes, bloom filters, Hadoop-framed LZ4, LZO, BROTLI; levels and values are not encoded. */
+CJ_API int cj_parquet_compress_device(cj_engine* e, int what, uint32_t flags, size_t n_chunks,
+                                      const uint8_t* in_base, const uint64_t* in_off, const uint64_t* in_len,
+                                      const int64_t* rows, const uint64_t* row_off, const uint64_t* row_cnt,
+                                      uint8_t* out_base, const uint64_t* out_off, const uint64_t* out_cap,
+                                      int64_t* result, void* hip_stream);
+CJ_API int cj_parquet_compress_host(cj_engine* e, int what, uint32_t flags, size_t n_chunks,
+                                    const uint8_t* const* in_ptrs, const size_t* in_lens,
+                                    const int64_t* const* rows_ptrs, const size_t* row_cnts,
+                                    uint8_t* const* out_ptrs, const size_t* out_caps, int64_t* result);
+CJ_API size_t cj_parquet_compress_bound(int what, size_t n_bytes, size_t n_pages);
 
 /* Zstandard frames — decode (RFC 8878; Parquet, ORC, Arrow IPC and Zarr v3 pages and chunks).  One chunk is what ONE call of
  * libzstd's ZSTD_decompress(dst, out_cap[i], src, in_len[i]) reads: one or more frames back to back, skippable frames skipped, an

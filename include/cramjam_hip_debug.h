@@ -64,6 +64,10 @@ CJ_API uint64_t cj_debug_bgzf_slot_budget(uint64_t bytes);
 /* ORC compress (cj_orc_batch_* with CJ_OP_COMPRESS): the bytes of bound-sized chunk slots per turn, one slot of the codec's bound for
  * block_size bytes per chunk in flight (0 = the default, 256 MiB); returns the previous value.  Tests force more than one turn with it. */
 CJ_API uint64_t cj_debug_orc_slot_budget(uint64_t bytes);
+/* Parquet compress (cj_parquet_compress_*): the bytes of bound-sized page slots per turn of whole chunks, one 16-byte-rounded slot of
+ * the codec's bound per page whose values the codec sees (0 = the default, 256 MiB); a chunk above it takes a turn alone; returns the
+ * previous value.  Tests force more than one turn with it. */
+CJ_API uint64_t cj_debug_parquet_slot_budget(uint64_t bytes);
 /* Zstandard decode (cj_zstd_batch_*): the bytes of literal slots per slice, one slot of 128 KiB + 32 per stream in flight (0 = the
  * default); returns the previous value */
 CJ_API uint64_t cj_debug_zstd_slot_budget(uint64_t bytes);
